@@ -507,7 +507,7 @@ Staging g_staging;
 }  // namespace
 
 // job classes of a multi call
-enum { J_SKIP = 0, J_ZERO = 1, J_DENSE = 2, J_PAIRS = 3, J_TILE = 4 };
+enum { J_SKIP = 0, J_ZERO = 1, J_DENSE = 2, J_PAIRS = 3, J_TILE = 4, J_WIDE = 5 };
 
 // rows from which a rulebook's tile jobs take the LDS-staged kernel even when pair lists are at hand (measurement aid:
 // DODA_WDMA_MIN_ROWS)
@@ -519,6 +519,10 @@ static int wdma_min_rows() {
 static int classify(const doda_wgrad_job &j) {
     if (j.n_rows == 0 && j.dw && j.K > 0 && j.ca > 0 && j.cb > 0)
         return (j.flags & DODA_WGRAD_ACCUMULATE) ? J_SKIP : J_ZERO;
+    // a tilebook of the job's table and 48 .. 224 channels on both sides: the wide LDS-staged kernel (spconv_wwide.hip).  It
+    // takes 48 / 64-channel layers before wgrad_dma16, whose 16 x 16 blocks re-stage the tile once per block, and
+    // only jobs that would otherwise run the gather-table kernel, whose sums it reproduces (jobs with pair lists keep them)
+    if (doda_wwide::eligible(j) && !doda_pairs::eligible(j)) return J_WIDE;
     // a tilebook of the job's table: the LDS-staged kernel (bf16, K = 27; 16 -> 16, and — round 4 — 16 .. 64 channels on
     // either side as 16 x 16 channel blocks over row-strided slices)
     if (j.tilebook && j.tbl && j.elem_bytes == 2 && j.ca % 16 == 0 && j.ca <= 64 && j.cb % 16 == 0 && j.cb <= 64 &&
@@ -537,6 +541,13 @@ static int classify(const doda_wgrad_job &j) {
     return J_DENSE;
 }
 
+// row chunks of the gather-table kernel's plan for a wide job: the wide kernel sums over the same chunks (same bits)
+static std::vector<int> wide_chunks(const doda_wgrad_job *jobs_h, const std::vector<int> &idx) {
+    std::vector<int> rpc;
+    for (int k : idx) rpc.push_back(make_plan(jobs_h[k].K, jobs_h[k].ca, jobs_h[k].cb, jobs_h[k].n_rows, 2, true).rows_per_chunk);
+    return rpc;
+}
+
 static size_t tile_blocks(const doda_wgrad_job &j) { return (size_t)(j.ca / 16) * (j.cb / 16); }
 
 static bool dense_needs_partial(const JobPlan &jp, const doda_wgrad_job &j) {
@@ -546,8 +557,10 @@ static bool dense_needs_partial(const JobPlan &jp, const doda_wgrad_job &j) {
 extern "C" size_t doda_spconv_wgrad_multi_workspace_bytes(const doda_wgrad_job *jobs_h, int32_t n_jobs) {
     if (!jobs_h || n_jobs <= 0) return 0;
     size_t total = 0;
+    std::vector<int> wide_jobs;
     for (int k = 0; k < n_jobs; ++k) {
         const int cls = classify(jobs_h[k]);
+        if (cls == J_WIDE) { wide_jobs.push_back(k); continue; }
         if (cls == J_PAIRS) { total += doda_pairs::partial_bytes(jobs_h[k]); continue; }
         if (cls == J_TILE) { total += tile_blocks(jobs_h[k]) * align_up(doda_wdma::partial_bytes(jobs_h[k].n_rows), 256); continue; }
         if (cls != J_DENSE) continue;
@@ -555,12 +568,15 @@ extern "C" size_t doda_spconv_wgrad_multi_workspace_bytes(const doda_wgrad_job *
         if (!plan_job(jobs_h[k], &jp)) continue;
         if (dense_needs_partial(jp, jobs_h[k])) total += align_up((size_t)jp.p.R * jp.n_elem * 4, 256);
     }
+    const std::vector<int> rpc = wide_chunks(jobs_h, wide_jobs);
+    total += doda_wwide::partial_bytes(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size());
     return total < 256 ? 256 : total;
 }
 
 extern "C" size_t doda_spconv_wgrad_multi_desc_bytes(int32_t n_jobs) {
-    const size_t per = sizeof(WJob) + sizeof(RJob) > doda_pairs::desc_bytes_per_job()
-                           ? sizeof(WJob) + sizeof(RJob) : doda_pairs::desc_bytes_per_job();
+    size_t per = sizeof(WJob) + sizeof(RJob) > doda_pairs::desc_bytes_per_job()
+                     ? sizeof(WJob) + sizeof(RJob) : doda_pairs::desc_bytes_per_job();
+    if (per < doda_wwide::desc_bytes_per_job()) per = doda_wwide::desc_bytes_per_job();
     return n_jobs <= 0 ? 0 : align_up((size_t)n_jobs * per + 256, 256);
 }
 
@@ -570,7 +586,7 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     if (desc_bytes < doda_spconv_wgrad_multi_desc_bytes(n_jobs)) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     std::vector<JobPlan> plans(n_jobs);
-    std::vector<int> keys, cls(n_jobs), pair_jobs, tile_jobs;
+    std::vector<int> keys, cls(n_jobs), pair_jobs, tile_jobs, wide_jobs;
     size_t off = 0;
     for (int k = 0; k < n_jobs; ++k) {
         plans[k].key = -1;
@@ -582,6 +598,7 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
         if (cls[k] == J_SKIP) continue;
         if (cls[k] == J_PAIRS) { pair_jobs.push_back(k); continue; }
         if (cls[k] == J_TILE) { tile_jobs.push_back(k); continue; }
+        if (cls[k] == J_WIDE) { wide_jobs.push_back(k); continue; }
         if (!plan_job(jobs_h[k], &plans[k])) return DODA_ERR_INVALID;
         plans[k].ws_off = off;
         if (dense_needs_partial(plans[k], jobs_h[k])) off += align_up((size_t)plans[k].p.R * plans[k].n_elem * 4, 256);
@@ -620,6 +637,17 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
             if (st != DODA_OK) return st;
             off += bytes;
         }
+    }
+    // wide tile jobs: one launch for all of them, their partials behind the rest
+    std::vector<unsigned char> wide_desc;
+    int wide_wgs = 0, wide_red = 0;
+    if (!wide_jobs.empty()) {
+        const std::vector<int> rpc = wide_chunks(jobs_h, wide_jobs);
+        const size_t bytes = doda_wwide::partial_bytes(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size());
+        if (ws_bytes < off + bytes) return DODA_ERR_WORKSPACE;
+        doda_wwide::prepare(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size(), (char *)ws + off, wide_desc, &wide_wgs,
+                            &wide_red);
+        off += bytes;
     }
     if (ws_bytes < off) return DODA_ERR_WORKSPACE;
 
@@ -668,7 +696,8 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     }
     const size_t wbytes = wj.size() * sizeof(WJob), rbytes = rj.size() * sizeof(RJob);
     const size_t pair_off = align_up(wbytes + rbytes, 16), pbytes = prep.desc.size();
-    const size_t total_desc = pair_off + pbytes;
+    const size_t wide_off = align_up(pair_off + pbytes, 16), wdbytes = wide_desc.size();
+    const size_t total_desc = wide_off + wdbytes;
     if (total_desc > desc_bytes) return DODA_ERR_WORKSPACE;
     if (total_desc > 0) {
         std::lock_guard<std::mutex> lock(g_staging.mu);
@@ -687,6 +716,7 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
         if (wbytes) memcpy(st.host, wj.data(), wbytes);
         if (rbytes) memcpy((char *)st.host + wbytes, rj.data(), rbytes);
         if (pbytes) memcpy((char *)st.host + pair_off, prep.desc.data(), pbytes);
+        if (wdbytes) memcpy((char *)st.host + wide_off, wide_desc.data(), wdbytes);
         if (hipMemcpyAsync(desc_dev, st.host, total_desc, hipMemcpyHostToDevice, s) != hipSuccess) return DODA_ERR_LAUNCH;
         hipEventRecord(st.ev, s);
         st.pending = true;
@@ -702,6 +732,10 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     if (st != DODA_OK) return st;
     if (!pair_jobs.empty()) {
         st = doda_pairs::launch(prep, (const char *)desc_dev + pair_off, s);
+        if (st != DODA_OK) return st;
+    }
+    if (!wide_jobs.empty()) {
+        st = doda_wwide::launch((const char *)desc_dev + wide_off, (int)wide_jobs.size(), wide_wgs, wide_red, s);
         if (st != DODA_OK) return st;
     }
     if (!rj.empty()) {

@@ -44,3 +44,15 @@ struct Block { const void *x, *dy; float *dw; int x_stride, dy_stride, ldo, ldc,
 int launch(const Block *blocks, int n_blocks, const int32_t *tbl, int ld, int n_rows, const void *tilebook, void *part,
            hipStream_t s);
 }  // namespace doda_wdma
+
+// LDS-staged weight gradient over a tilebook for wide channels (spconv_wwide.hip): bf16 K = 27 layers of 48 .. 224 channels,
+// every such job of a call in one launch (idx: the call's job indices of this class; rows_per_chunk: the gather-table
+// kernel's row chunks of each, whose sums the kernel reproduces bit for bit)
+namespace doda_wwide {
+bool eligible(const doda_wgrad_job &j);
+size_t partial_bytes(const doda_wgrad_job *jobs, const int *idx, const int *rows_per_chunk, int n);
+size_t desc_bytes_per_job();
+void prepare(const doda_wgrad_job *jobs, const int *idx, const int *rows_per_chunk, int n, void *part,
+             std::vector<unsigned char> &desc, int *wgs, int *red_blocks);
+int launch(const void *desc_dev, int n, int wgs, int red_blocks, hipStream_t s);
+}  // namespace doda_wwide

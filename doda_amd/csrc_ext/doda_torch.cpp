@@ -381,7 +381,7 @@ typedef std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<i
 // pairs_min_rows < 0: no lists; else lists for rulebooks of at least that many rows.
 std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vector<int64_t> shape, int64_t batch,
                                         int64_t n_levels, int64_t pairs_min_rows, int64_t tile_min_rows,
-                                        int64_t tile_levels) {
+                                        int64_t tile_levels, int64_t wgrad_tile_levels) {
     TORCH_CHECK(indices_in.is_cuda() && indices_in.scalar_type() == at::kInt && indices_in.dim() == 2 &&
                 indices_in.size(1) == 4 && shape.size() == 3, "doda build_pyramid: indices must be int32 [M,4] on the GPU");
     std::vector<PyramidLevel> out;
@@ -404,7 +404,13 @@ std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vecto
         at::Tensor ws = pempty({(int64_t)(wsb > 256 ? wsb : 256)}, iopt.dtype(at::kByte));
         // tilebooks for the finest `tile_levels` levels: DODA's 16- and 32-channel bf16 layers (2) or the 16-channel
         // fp32 layers (1) — rows of 32 or 64 bytes, what the tile kernel stages
-        const bool tiled = lvl < tile_levels && tile_min_rows >= 0 && m >= tile_min_rows;
+        // and, for the weight gradient only, the coarser levels below `wgrad_tile_levels` (48 .. 224-channel bf16 layers:
+        // csrc/spconv_wwide.hip; the forward kernels take a tilebook for 16 / 32 channels only).  Independent of
+        // tile_min_rows and of the finest levels' overflow backoff: a coarse tile above the list capacity is served from the
+        // dense table inside the kernel.
+        // (a rulebook that gets pair lists keeps them: its layers stay on the pair-list kernel)
+        const bool tiled = (lvl < tile_levels && tile_min_rows >= 0 && m >= tile_min_rows) ||
+                           (lvl >= tile_levels && lvl < wgrad_tile_levels && m > 0 && !(pairs_min_rows >= 0 && m >= pairs_min_rows));
         at::Tensor nbr = tiled ? table_with_tilebook(27, m, iopt) : pempty({27, m}, iopt);
         check(doda_rulebook_subm((const int32_t *)indices.data_ptr(), m, shp, (int32_t)batch, 3,
                                  (int32_t *)nbr.data_ptr(), m, ws.data_ptr(), (size_t)ws.numel(), st),
@@ -1886,13 +1892,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("build_pyramid", &build_pyramid,
           "all SubM k3 and k2s2 rulebooks of an n-level U-Net in one call (13 native builds, 6 size read-backs)",
           py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("n_levels"), py::arg("pairs_min_rows") = -1,
-          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2,
+          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::arg("wgrad_tile_levels") = 0,
           py::call_guard<py::gil_scoped_release>());   // its size read-backs block: let other Python threads run
     m.def("build_pyramid_probe", [](const at::Tensor &indices, std::vector<int64_t> shape, int64_t batch, int64_t n_levels,
-                                    int64_t pairs_min_rows, int64_t tile_min_rows, int64_t tile_levels) {
+                                    int64_t pairs_min_rows, int64_t tile_min_rows, int64_t tile_levels,
+                                    int64_t wgrad_tile_levels) {
               // build_pyramid + the finest tilebook's overflow counters (tiles, above the 64-byte capacity, above the list)
               // in ONE call without the GIL: the rulebook thread's read-back does not stall the issuing thread
-              auto levels = build_pyramid(indices, shape, batch, n_levels, pairs_min_rows, tile_min_rows, tile_levels);
+              auto levels = build_pyramid(indices, shape, batch, n_levels, pairs_min_rows, tile_min_rows, tile_levels,
+                                          wgrad_tile_levels);
               int64_t nt = -1, o64 = 0, o32 = 0;
               if (!levels.empty()) {
                   const at::Tensor &tbl = std::get<0>(levels[0]);
@@ -1914,7 +1922,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               }
               return std::make_tuple(levels, nt, o64, o32);
           }, py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("n_levels"), py::arg("pairs_min_rows") = -1,
-          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::call_guard<py::gil_scoped_release>());
+          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::arg("wgrad_tile_levels") = 0,
+          py::call_guard<py::gil_scoped_release>());
     m.def("with_tilebook", [](const at::Tensor &tbl) {
               TORCH_CHECK(tbl.is_cuda() && tbl.scalar_type() == at::kInt && tbl.dim() == 2, "doda with_tilebook: int32 [K, M] table");
               at::Tensor out = table_with_tilebook(tbl.size(0), tbl.size(1), tbl.options());

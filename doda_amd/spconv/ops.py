@@ -77,6 +77,10 @@ TILE_KERNEL = os.environ.get("DODA_NO_TILE", "0") != "1"
 TILE_OVERFLOW_MAX = 0.25
 TILE_BACKOFF = 64
 _tile_state = {"skip": 0, "last": None}   # batches still to skip; (tiles, over 64-byte capacity, over list capacity)
+# bf16 training: the SubM rulebooks of the coarser levels up to this one also get a tilebook, for the weight gradient only
+# (48 .. 224 channels: csrc/spconv_wwide.hip).  Their overflow does not feed the backoff above: a coarse tile above the
+# list capacity is served from the dense table inside that kernel.  0: none (DODA_WGRAD_TILE_LEVELS).
+WGRAD_TILE_LEVELS = int(os.environ.get("DODA_WGRAD_TILE_LEVELS", "7"))
 
 
 def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", first_level=1, with_pairs=False,
@@ -100,13 +104,15 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
         # (one call without the GIL: the builds, their six size read-backs and the tilebook's overflow counters)
         levels, nt, over64, over32 = _ext.build_pyramid_probe(indices, [int(v) for v in shape], int(tensor.batch_size),
                                                               int(n_levels), PAIRS_MIN_ROWS if with_pairs else -1,
-                                                              TILE_MIN_ROWS if tiles_on else -1, n_tile_levels)
+                                                              TILE_MIN_ROWS if tiles_on else -1, n_tile_levels,
+                                                              WGRAD_TILE_LEVELS if (with_pairs and n_tile_levels > 0) else 0)
         if tiles_on and nt >= 0:
             _tile_state["last"] = (nt, over64, over32)
             if over32 > TILE_OVERFLOW_MAX * nt:
                 _tile_state["skip"] = TILE_BACKOFF
                 # this batch too: plain copies of the tables (no tilebook behind them) keep it on the dense kernels
-                levels = [((lv[0].clone() if _ext.has_tilebook(lv[0]) else lv[0]),) + tuple(lv[1:]) for lv in levels]
+                levels = [((lv[0].clone() if k < n_tile_levels and _ext.has_tilebook(lv[0]) else lv[0]),) + tuple(lv[1:])
+                          for k, lv in enumerate(levels)]
         for k, (nbr, outids, child, par_off, oshape, sp, sn, sh, dp, dn, dh) in enumerate(levels):   # s*/d*: lists, counts, segments
             lvl = first_level + k
             data = tensor.indice_dict[subm_key % lvl] = IndiceData("subm", indices, indices, list(shape),

@@ -1,4 +1,5 @@
-// Point head + loss without the point-level score matrix (ABI 11: doda_head_ce_fwd / _bwd).
+// Point head + loss without the point-level score matrix (ABI 11: doda_head_ce_fwd / _bwd); the self-training confidence
+// (doda_st_voxel_confidence, include/doda_selftrain.h) shares its logit code.
 //
 // reference model/unet.py:62-64,107-108,196: feats_pt = out.features[p2v]; scores = Linear(feats_pt); loss =
 // CrossEntropyLoss(ignore_index)(scores, labels) — a [N points, n_cls] fp32 matrix (62 MB at 781 k points x 20 classes) that the
@@ -15,6 +16,7 @@
 // bf16 features: the weights are rounded to bf16 first, as the gather-GEMM's pre-pack does; accumulation in fp32.
 #include "common.hpp"
 #include "spconv_common.hpp"
+#include "../../include/doda_selftrain.h"
 
 namespace {
 constexpr int HD_BLOCK = 256;
@@ -133,6 +135,29 @@ __global__ __launch_bounds__(HD_BLOCK, 4) void head_ce_fwd(const void *__restric
     }
 }
 
+// self-training confidence (include/doda_selftrain.h): pred[v] = argmax_k z_v[k] through the same hd_logits as head_ce_fwd (same
+// bits), conf[v] = 1 / sum_k exp(z_v[k] - max) — the largest softmax probability — with the accurate expf (no point-level matrix)
+template <int ESZ, int C, int NK>
+__global__ __launch_bounds__(HD_BLOCK, 4) void st_voxel_conf(const void *__restrict__ feats, int m, const float *__restrict__ weight,
+                                                          const float *__restrict__ bias, int n_cls, int32_t *__restrict__ pred,
+                                                          float *__restrict__ conf) {
+    __shared__ float w[HD_MAX_K][HD_MAX_C], b[HD_MAX_K];
+    hd_stage_weights<ESZ>(weight, bias, n_cls, C, w, b);
+#pragma unroll 1
+    for (long long v = (long long)blockIdx.x * HD_BLOCK + threadIdx.x; v < m; v += (long long)gridDim.x * HD_BLOCK) {
+        asm volatile("" ::: "memory");
+        float f[C], z[NK], mx;
+        int arg;
+        hd_load_row<ESZ, C>(feats, v, f);
+        hd_logits<C, NK>(w, b, n_cls, f, z, mx, arg);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) s += expf(z[k] - mx);      // (padding classes: exp(-inf) = 0; the argmax term: exactly 1)
+        pred[v] = arg;
+        conf[v] = 1.f / s;
+    }
+}
+
 // out[0] = sum(loss) / max(n_valid, 1), out[1] = n_valid (fixed order, fp64).  1024 threads: two or three partial rows each — one
 // round trip instead of the 37 dependent ones a single wave needed over 2349 rows (11 us)
 __global__ __launch_bounds__(1024) void head_ce_final(const float *__restrict__ partial, int nblocks, float *__restrict__ out) {
@@ -210,14 +235,17 @@ __global__ __launch_bounds__(HD_BLOCK) void head_ce_bwd(const void *__restrict__
         for (int c = 0; c < C; ++c) df[c] = 0.f;
         char *dzr = (char *)dz_out + (size_t)v * n_cls * ESZ;
 #pragma unroll 1
-        for (int k = 0; k < n_cls; k += 2) {      // two classes per step: one 4- / 8-byte store of dz
+        for (int k = 0; k < n_cls; k += 2) {      // two classes per step: one 4- / 8-byte store of dz (even n_cls)
             const float g0 = sz[k][tid], g1 = k + 1 < n_cls ? sz[k + 1][tid] : 0.f;
 #pragma unroll
             for (int c = 0; c < C; ++c) df[c] = __builtin_fmaf(g0, w[k][c], df[c]);
             if (k + 1 < n_cls) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) df[c] = __builtin_fmaf(g1, w[k + 1][c], df[c]);
-                if constexpr (ESZ == 2)
+                if (n_cls & 1) {      // (odd rows start at odd elements: a paired store would be misaligned)
+                    HdRow<ESZ>::store(dzr + (size_t)k * ESZ, g0);
+                    HdRow<ESZ>::store(dzr + (size_t)(k + 1) * ESZ, g1);
+                } else if constexpr (ESZ == 2)
                     *reinterpret_cast<unsigned *>(dzr + (size_t)k * 2) = (unsigned)f2bf(g0) | ((unsigned)f2bf(g1) << 16);
                 else
                     *reinterpret_cast<f32x2 *>(dzr + (size_t)k * 4) = (f32x2){g0, g1};
@@ -336,6 +364,22 @@ inline int hd_blocks(int m) {
             else hipLaunchKernelGGL((KERNEL<4, 16, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
         }                                                                                                          \
     } while (0)
+// the same class-count buckets with 32 feature channels (the reference configs' `mid_channel: 16 # or 32`): self-training confidence only
+#define ST_DISPATCH32(KERNEL, ...)                                                                                 \
+    do {                                                                                                           \
+        const int nk = (n_cls + 3) / 4 * 4;                                                                        \
+        if (elem_bytes == 2) {                                                                                     \
+            if (nk <= 12) hipLaunchKernelGGL((KERNEL<2, 32, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
+            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<2, 32, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
+            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<2, 32, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
+            else hipLaunchKernelGGL((KERNEL<2, 32, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
+        } else {                                                                                                   \
+            if (nk <= 12) hipLaunchKernelGGL((KERNEL<4, 32, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
+            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<4, 32, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
+            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<4, 32, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
+            else hipLaunchKernelGGL((KERNEL<4, 32, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
+        }                                                                                                          \
+    } while (0)
 inline bool hd_bad(const void *feats, int m, int c, int esz, const float *weight, int n_cls, const int32_t *v2p, int v2p_ld,
                    const int64_t *labels) {
     return m < 0 || (esz != 2 && esz != 4) || n_cls <= 0 || v2p_ld < 1 || !feats || !weight || !v2p || !labels;
@@ -370,6 +414,18 @@ extern "C" int doda_head_ce_bwd(const void *feats, int32_t m, int32_t c, int32_t
     hipStream_t s = as_stream(stream);
     HD_DISPATCH(head_ce_bwd, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index, out, grad,
                 d_feats, dz, db_partial);
+    return doda_check_launch();
+}
+
+extern "C" int doda_st_voxel_confidence(const void *feats, int32_t m, int32_t c, int32_t elem_bytes, const float *weight,
+                                        const float *bias, int32_t n_cls, int32_t *pred, float *conf, doda_stream_t stream) {
+    if (m < 0 || (elem_bytes != 2 && elem_bytes != 4) || !weight || !pred || !conf || (m > 0 && !feats)) return DODA_ERR_INVALID;
+    if ((c != 16 && c != 32) || n_cls < 2 || n_cls > DODA_ST_MAX_CLASSES) return DODA_ERR_UNSUPPORTED;
+    if (m == 0) return DODA_OK;
+    hipStream_t s = as_stream(stream);
+    const int n_blocks = hd_blocks(m);
+    if (c == 16) HD_DISPATCH(st_voxel_conf, feats, m, weight, bias, n_cls, pred, conf);
+    else ST_DISPATCH32(st_voxel_conf, feats, m, weight, bias, n_cls, pred, conf);
     return doda_check_launch();
 }
 

@@ -75,15 +75,30 @@ class SyntheticScenes(torch.utils.data.Dataset):
     def __init__(self, paths, length, voxel_scale, seed, augment=True):
         self.paths, self.length, self.voxel_scale, self.seed, self.augment = list(paths), int(length), int(voxel_scale), int(seed), augment
         self._mem = {}
+        self.labels = None      # set_labels: per base scene, labels that replace the file's (pseudo labels)
 
     def __len__(self):
         return self.length
+
+    def set_labels(self, labels):
+        """labels: one int32 array [points of base scene k] per base scene (or None: the files' labels again)."""
+        if labels is not None:
+            if len(labels) != len(self.paths):
+                raise ValueError("set_labels: %d label arrays for %d base scenes" % (len(labels), len(self.paths)))
+            labels = [np.ascontiguousarray(np.asarray(a), dtype=np.int32) for a in labels]
+        self.labels = labels
+        self._mem = {}
 
     def _base(self, k):
         v = self._mem.get(k)
         if v is None:
             with np.load(self.paths[k]) as f:
-                v = self._mem[k] = (np.ascontiguousarray(f["xyz_mid"].T, dtype=np.float32), f["labels"].astype(np.int32))
+                v = (np.ascontiguousarray(f["xyz_mid"].T, dtype=np.float32), f["labels"].astype(np.int32))
+            if self.labels is not None:
+                if self.labels[k].shape != v[1].shape:
+                    raise ValueError("label override of %s: %s labels for %s points" % (self.paths[k], self.labels[k].shape, v[1].shape))
+                v = (v[0], self.labels[k])
+            self._mem[k] = v
         return v
 
     def __getitem__(self, i):
@@ -310,6 +325,12 @@ class DeviceScenes:
                 self.xyz.append(torch.from_numpy(np.ascontiguousarray(f["xyz_mid"], dtype=np.float32)).to(self.device))
                 self.lab.append(torch.from_numpy(f["labels"].astype(np.int32)).to(self.device))
         self.gen = torch.Generator(device=self.device)
+
+    def set_labels(self, labels):
+        """Replace the base scenes' labels: one device int32 tensor [points of base scene k] per base scene (pseudo labels)."""
+        if len(labels) != len(self.lab) or any(a.numel() != b.numel() for a, b in zip(labels, self.lab)):
+            raise ValueError("set_labels: one label per point of every base scene")
+        self.lab = [t.to(self.device, torch.int32).contiguous() for t in labels]
 
     def set_epoch(self, epoch):
         self.sampler.set_epoch(epoch)

@@ -672,14 +672,27 @@ class SparseConvNet(nn.Module):
         self.voxel_pred = pred
         return loss
 
-    def forward(self, input, input_map, return_mid_feat=False, v2p_map=None, v2p_map_t=None, labels=None, ignore_index=255):
+    def _trunk(self, input):
         if input.features.is_cuda and input.indices.shape[0] > 0:
             # all 13 rulebooks up front (+ their pair lists when a bf16 backward pass will follow)
             spconv.ops.build_pyramid(input, len(self.unet.nPlanes), with_pairs=(
                 spconv.functional.WGRAD_PAIRS and torch.is_grad_enabled() and self.training
                 and input.features.dtype == torch.bfloat16),
                 with_tiles=tile_levels_for(input.features.dtype))   # tilebooks serve inference as well
-        out = self.output_layer(self.unet(self.input_conv(input)))
+        return self.output_layer(self.unet(self.input_conv(input)))
+
+    @torch.no_grad()
+    def voxel_confidence(self, input):
+        """Pseudo-label inputs of the self-training stage (reference model/unet.py:115-132: softmax(Linear(feats[p2v])).max(1)) at
+        VOXEL level, without the point-score matrix: trunk, output layer, then doda_st_voxel_confidence.  -> (pred int32 [m],
+        conf float32 [m]); every point of voxel v has pred[v] / conf[v].  No fallback: a head outside the kernel's range (16 / 32
+        channels, 2-32 classes, device tensors) raises."""
+        feats = self._trunk(input).features
+        return _ops.voxel_confidence(feats.contiguous(), self.linear.weight.detach(),
+                                     self.linear.bias.detach() if self.linear.bias is not None else None)
+
+    def forward(self, input, input_map, return_mid_feat=False, v2p_map=None, v2p_map_t=None, labels=None, ignore_index=255):
+        out = self._trunk(input)
         feats = out.features
         if labels is not None and not return_mid_feat:      # the caller wants the loss: head + loss at voxel level
             loss = self.head_loss(feats, v2p_map, labels, ignore_index)
@@ -909,6 +922,21 @@ def voxelize_and_run(cfg, model, batch, device, feature_dtype=torch.float32, fus
     inputs_ready: the batch is resident on `device` with no copy or kernel still producing it, so the
     rulebooks may be built on a side stream ahead of the main stream's queue (_prebuild_pyramid).
     pyramid: (indices int32, indice_dict) of this batch from PyramidPrefetcher.take."""
+    inp, p2v, v2p = sparse_input(cfg, model, batch, device, feature_dtype, inputs_ready, pyramid)
+    if fused_head:
+        v2p_t = batch.get("v2p_map_t")
+        if labels is not None:   # -> the LOSS (head + CrossEntropyLoss at voxel level when the fused form applies)
+            return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None,
+                         labels=labels, ignore_index=ignore_index)
+        return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None)
+    if labels is not None:
+        return cross_entropy(model(inp, p2v), labels, ignore_index)
+    return model(inp, p2v)
+
+
+def sparse_input(cfg, model, batch, device, feature_dtype=torch.float32, inputs_ready=False, pyramid=None):
+    """(network input SparseConvTensor, p2v, v2p) of a collated batch: H2D, voxel mean-pooling and the rulebooks (the first half
+    of voxelize_and_run; reference model/unet.py:72-99)."""
     voxel_coords = batch["voxel_locs"].to(device, non_blocking=True)
     p2v = batch["p2v_map"].to(device, non_blocking=True)
     v2p = batch["v2p_map"].to(device, non_blocking=True)
@@ -937,12 +965,4 @@ def voxelize_and_run(cfg, model, batch, device, feature_dtype=torch.float32, fus
     else:
         inp = spconv.SparseConvTensor(voxel_feats.to(feature_dtype), voxel_coords.int(),
                                       batch["spatial_shape"], batch_size)
-    if fused_head:
-        v2p_t = batch.get("v2p_map_t")
-        if labels is not None:   # -> the LOSS (head + CrossEntropyLoss at voxel level when the fused form applies)
-            return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None,
-                         labels=labels, ignore_index=ignore_index)
-        return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None)
-    if labels is not None:
-        return cross_entropy(model(inp, p2v), labels, ignore_index)
-    return model(inp, p2v)
+    return inp, p2v, v2p

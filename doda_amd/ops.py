@@ -908,6 +908,76 @@ def head_dw(feats, dz):
     return spconv_wgrad(feats.contiguous(), dz, ident, m)[0].t()
 
 
+# ---- self-training pseudo labels (include/doda_selftrain.h) --------------------------------------------
+def voxel_confidence(feats, weight, bias):
+    """(pred int32 [m], conf float32 [m]) of the Linear head on the voxel rows: the argmax class (bit-identical to head_ce_fwd's
+    pred) and its softmax probability 1 / sum_k exp(z_k - z_max) (doda_st_voxel_confidence).  feats bf16 / fp32 [m, 16 | 32]."""
+    _feat_ok(feats, "feats")
+    _need_cuda(weight)
+    if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] != feats.shape[1]:
+        raise RuntimeError("voxel_confidence: weight float32 [n_cls, c]")
+    if bias is not None:
+        _need_cuda(bias)
+        if bias.dtype != torch.float32 or bias.numel() != weight.shape[0]:
+            raise RuntimeError("voxel_confidence: bias float32 [n_cls]")
+    m, c = feats.shape
+    pred = torch.empty(m, dtype=torch.int32, device=feats.device)
+    conf = torch.empty(m, dtype=torch.float32, device=feats.device)
+    check(lib().doda_st_voxel_confidence(_p(feats), m, c, feats.element_size(), _p(weight.contiguous()),
+                                         _p(bias.contiguous()) if bias is not None else None, weight.shape[0], _p(pred), _p(conf),
+                                         _stream()), "doda_st_voxel_confidence")
+    return pred, conf
+
+
+def st_point_store(pred, conf, p2v, store_cls, store_conf, offset, n_cls, hist=None):
+    """store_cls / store_conf[offset + i] = pred / conf[p2v[i]] for every point i (doda_st_point_store); hist: int64 [n_cls, 256]
+    to ADD the level-0 radix histogram of those points to, or None."""
+    for t in (pred, conf, p2v, store_cls, store_conf):
+        _need_cuda(t)
+    if (pred.dtype != torch.int32 or conf.dtype != torch.float32 or p2v.dtype != torch.int32 or store_cls.dtype != torch.uint8
+            or store_conf.dtype != torch.float32 or store_cls.shape != store_conf.shape or pred.shape != conf.shape):
+        raise RuntimeError("st_point_store: pred int32 / conf float32 [m], p2v int32 [n], store uint8 / float32 [len]")
+    for t in (pred, conf, p2v, store_cls, store_conf):
+        if not t.is_contiguous():
+            raise RuntimeError("st_point_store: contiguous tensors only")
+    if hist is not None:
+        _need_cuda(hist)
+        if hist.dtype != torch.int64 or hist.shape != (n_cls, 256) or not hist.is_contiguous():
+            raise RuntimeError("st_point_store: hist int64 [n_cls, 256]")
+    check(lib().doda_st_point_store(_p(pred), _p(conf), pred.numel(), _p(p2v), p2v.numel(), int(n_cls), _p(store_cls), _p(store_conf),
+                                    store_cls.numel(), int(offset), _p(hist), _stream()), "doda_st_point_store")
+
+
+def st_radix_hist(store_cls, store_conf, n_cls, level, prefix=None):
+    """int64 [n_cls, 256]: radix level `level` of the stored confidences per class, restricted to the keys whose higher bits equal
+    prefix[c] (int32 device tensor [n_cls]; -1 = class done; unused at level 0) (doda_st_radix_hist)."""
+    _need_cuda(store_cls, store_conf)
+    if store_cls.dtype != torch.uint8 or store_conf.dtype != torch.float32 or store_cls.shape != store_conf.shape:
+        raise RuntimeError("st_radix_hist: store uint8 / float32 [len]")
+    if prefix is not None:
+        _need_cuda(prefix)
+        if prefix.dtype != torch.int32 or prefix.numel() != n_cls:
+            raise RuntimeError("st_radix_hist: prefix int32 [n_cls]")
+    hist = torch.zeros((n_cls, 256), dtype=torch.int64, device=store_cls.device)
+    check(lib().doda_st_radix_hist(_p(store_cls.contiguous()), _p(store_conf.contiguous()), store_cls.numel(), int(n_cls), int(level),
+                                   _p(prefix.contiguous()) if prefix is not None else None, _p(hist), _stream()), "doda_st_radix_hist")
+    return hist
+
+
+def st_label(store_cls, store_conf, thres32, ignore):
+    """(labels uint8 [len], kept int64 [n_cls]): labels = conf > thres32[cls] ? cls : ignore, kept = points kept per class
+    (doda_st_label).  thres32: float32 device tensor [n_cls] of strict lower bounds."""
+    _need_cuda(store_cls, store_conf, thres32)
+    if store_cls.dtype != torch.uint8 or store_conf.dtype != torch.float32 or thres32.dtype != torch.float32:
+        raise RuntimeError("st_label: store uint8 / float32 [len], thres float32 [n_cls]")
+    n_cls = thres32.numel()
+    labels = torch.empty(store_cls.shape, dtype=torch.uint8, device=store_cls.device)
+    kept = torch.zeros(n_cls, dtype=torch.int64, device=store_cls.device)
+    check(lib().doda_st_label(_p(store_cls.contiguous()), _p(store_conf.contiguous()), store_cls.numel(), n_cls,
+                              _p(thres32.contiguous()), int(ignore), _p(labels), _p(kept), _stream()), "doda_st_label")
+    return labels, kept
+
+
 # ---- optimizer step -------------------------------------------------------------------------------
 class _SgdTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("n", C.c_int64),

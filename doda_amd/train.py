@@ -75,7 +75,8 @@ def build_parser():
                         "Z-order renumbering, or decided from the first batch's tile overflow (per-point outputs do not depend on it)")
     p.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="feature storage dtype")
     p.add_argument("--self_train", action="store_true", default=False,
-                   help="tool/st.py step: a source pass and a target pass per optimizer step")
+                   help="step-shape benchmark of tool/st.py: a source pass and a target pass per optimizer step, the target pass "
+                        "trained on the target split's GROUND-TRUTH labels (self-training with pseudo labels: python -m doda_amd.st)")
     p.add_argument("--output_root", type=str, default=None, help="default: <cfg root>/output")
     p.add_argument("--max_iters", type=int, default=None, help="stop after this many iterations (smoke runs)")
     p.add_argument("--timing_warmup", type=int, default=10, help="iterations of an epoch before its steady-state clock starts")
@@ -88,8 +89,8 @@ def build_parser():
     return p
 
 
-def parse_config(argv=None):
-    args = build_parser().parse_args(argv)
+def parse_config(argv=None, parser=None):
+    args = (parser or build_parser()).parse_args(argv)
     cfg = Config()
     cfg_from_yaml_file(args.cfg_file, cfg)
     cfg.TAG = Path(args.cfg_file).stem
@@ -323,7 +324,7 @@ class Trainer:
         self.n_levels = len(net.unet.nPlanes)
         self.prefetch = PyramidPrefetcher(device, self.n_levels) if device.type == "cuda" else None
         self.iters_done = 0
-        self._loaders = {}
+        self._loaders, self._datasets, self._labels = {}, {}, {}
         self.step_times = []      # (iterations, seconds) of the steady part of every epoch (see train_epoch)
 
     # one forward + backward of one batch; `domain`: None | "source" | "target" (DSNorm statistics)
@@ -356,6 +357,7 @@ class Trainer:
             ddist.barrier()
             if self.rank != 0:
                 ds = synthetic_dataset(self.cfg, self.args, split)
+            self._datasets[split] = ds
             seed = self.args.manual_seed or 0
             fs0 = self.cfg.DATA_CONFIG.DATA_PROCESSOR.get("full_scale", [128, 512])[0]
             if self.args.host_loader:   # (same sampler seed and the same spatial-shape clip as the HBM-resident loader below)
@@ -366,7 +368,36 @@ class Trainer:
                                    self.device, augment=ds.augment, shuffle=split != "val",
                                    full_scale0=fs0)
                 self._loaders[split] = (dsc, dsc)
+            if split in self._labels:
+                self._apply_labels(split)
         return self._loaders[split]
+
+    def split_paths(self, split):
+        """The base scene files of a split (made on first use, as the split's loader is)."""
+        self._loader(split)
+        return list(self._datasets[split].paths)
+
+    def set_split_labels(self, split, labels):
+        """Replace the labels of a split's base scenes (one device int32 tensor per base scene, in split_paths order): every
+        augmented sample drawn from base scene k then carries labels[k] — the pseudo labels of the self-training stage
+        (doda_amd.st), never the split's ground truth.  Needs the resident or the worker loader (not --inline_loader)."""
+        if self.args.inline_loader:
+            raise RuntimeError("split label override: --inline_loader draws scenes outside the base-scene pool")
+        self._labels[split] = [t.to(self.device, torch.int32) for t in labels]
+        if split in self._loaders:
+            self._apply_labels(split)
+
+    def _apply_labels(self, split):
+        labels = self._labels[split]
+        dl, sampler = self._loaders[split]
+        if isinstance(dl, torch.utils.data.DataLoader):
+            # worker processes hold a pickled copy of the dataset: a fresh loader carries the new labels to them
+            self._datasets[split].set_labels([t.cpu().numpy() for t in labels])
+            if getattr(dl, "_iterator", None) is not None:
+                del self._loaders[split]
+                self._loader(split)
+        else:
+            dl.set_labels(labels)
 
     def _batches(self, epoch, split):
         """(batch, prebuilt rulebooks): worker processes produce the scenes, a feeder thread collates them on the device and
@@ -480,9 +511,9 @@ class Trainer:
         return miou
 
 
-def main(argv=None):
+def setup(args, cfg):
+    """Process group, device, NUMA pinning, per-rank batch size, epochs and seeds (tool/train.py:271-300) -> (world, rank, device)."""
     from . import dist as ddist
-    args, cfg = parse_config(argv)
     world, rank, local_rank = (1, 0, 0)
     if args.launcher != "none":
         world, rank, local_rank = ddist.setup()
@@ -503,19 +534,18 @@ def main(argv=None):
         np.random.seed(args.manual_seed)
         torch.manual_seed(args.manual_seed)
         torch.cuda.manual_seed_all(args.manual_seed)
-    root = Path(args.output_root) if args.output_root else Path(os.getcwd()) / "output"
-    output_dir = root / cfg.EXP_GROUP_PATH / cfg.TAG / args.extra_tag
-    ckpt_dir = output_dir / "ckpt"
-    if rank == 0:
-        ckpt_dir.mkdir(parents=True, exist_ok=True)
-    ddist.barrier()
+    return world, rank, device
 
+
+def rank_logger(rank):
     def log(msg):
         if rank == 0:
             print(msg, flush=True)
+    return log
 
-    trainer = Trainer(args, cfg, device, rank, world, log)
-    log("#classifier parameters: %d" % sum(p.nelement() for p in trainer.model.parameters()))
+
+def restore(trainer, args, ckpt_dir, log):
+    """--weight, --resume or the newest train_epoch_*.pth of ckpt_dir, and the best metric so far -> (best_miou, best_epoch)."""
     best_miou, best_epoch = 0.0, 0
     if args.weight:
         load_params_from_pretrain(args.weight, trainer.model, strict=not args.pretrain_not_strict, logger=log)
@@ -529,6 +559,11 @@ def main(argv=None):
         best_miou, best_epoch = load_metric_from_ckpt(str(ckpt_dir / "best_train.pth"))
         best_miou = best_miou or 0.0
     log("optimizer LR: %s" % trainer.optimizer.param_groups[0]["lr"])
+    return best_miou, best_epoch
+
+
+def run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch):
+    """tool/train.py:235-268: epochs from args.start_epoch, checkpoints, evaluation and the best checkpoint."""
     for epoch in range(args.start_epoch, args.epochs):
         trainer.train_epoch(epoch, args.epochs)
         epoch_log = epoch + 1
@@ -548,6 +583,12 @@ def main(argv=None):
         log("Best epoch: %d, best mIoU: %s" % (best_epoch, best_miou))
         if args.max_iters is not None and trainer.iters_done >= args.max_iters:
             break
+    return best_miou, best_epoch
+
+
+def finish(trainer, args, rank, world):
+    """Stop the helper threads and the reducer, write --timing_json / --curve_json, final barrier."""
+    from . import dist as ddist
     if trainer.prefetch is not None:
         trainer.prefetch.shutdown()
     if trainer.reducer is not None:
@@ -570,6 +611,27 @@ def main(argv=None):
             json.dump({"dtype": args.dtype, "seed": args.manual_seed, "batch_size_per_gpu": args.batch_size, "world": world,
                        "scenes_per_epoch": args.synthetic_scenes, "voxels_per_scene": args.synthetic_voxels, "curve": trainer.curve}, f)
     ddist.barrier()
+
+
+def output_root(args):
+    return Path(args.output_root) if args.output_root else Path(os.getcwd()) / "output"
+
+
+def main(argv=None):
+    from . import dist as ddist
+    args, cfg = parse_config(argv)
+    world, rank, device = setup(args, cfg)
+    output_dir = output_root(args) / cfg.EXP_GROUP_PATH / cfg.TAG / args.extra_tag
+    ckpt_dir = output_dir / "ckpt"
+    if rank == 0:
+        ckpt_dir.mkdir(parents=True, exist_ok=True)
+    ddist.barrier()
+    log = rank_logger(rank)
+    trainer = Trainer(args, cfg, device, rank, world, log)
+    log("#classifier parameters: %d" % sum(p.nelement() for p in trainer.model.parameters()))
+    best_miou, best_epoch = restore(trainer, args, ckpt_dir, log)
+    run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch)
+    finish(trainer, args, rank, world)
 
 
 if __name__ == "__main__":

@@ -325,7 +325,8 @@ class UBlock(nn.Module):
     # ---- the subtree as executor steps (csrc_ext coarse_ublock) ----
     def _coarse_modules(self):
         """Static part: [("rb", block) | ("down", seq, level) | ("up", seq, level)] in execution order, or False when a
-        module of the subtree is not the plain reference form (model/unet_block.py:9-37,55-100)."""
+        module of the subtree is not the plain reference form (model/unet_block.py:9-37,55-100) or a BatchNorm of it is wider
+        than the op list takes (ops.CX_BN_MAX_C: width 32 carries 320 / 384 / 448 channels at levels 5-7)."""
         plan = self.__dict__.get("_doda_coarse")
         if plan is not None:
             return plan
@@ -351,11 +352,13 @@ class UBlock(nn.Module):
                         and mods[2].indice_key == mods[5].indice_key and len(sk) == 1
                         and (type(sk[0]) is nn.Identity or _plain_conv(sk[0], spconv.SubMConv3d, [1, 1, 1]))
                         and not (m._forward_hooks or m._forward_pre_hooks or m.conv_branch._forward_hooks or m.i_branch._forward_hooks))
+                good = good and max(mods[0].num_features, mods[3].num_features) <= _ops.CX_BN_MAX_C
             else:
                 mods = list(m._modules.values())
                 cls = spconv.SparseConv3d if kind == "down" else spconv.SparseInverseConv3d
                 good = (len(mods) == 3 and _plain_bn(mods[0]) and type(mods[1]) is nn.ReLU and _plain_conv(mods[2], cls, [2, 2, 2])
-                        and (kind == "up" or mods[2].stride == [2, 2, 2]) and not (m._forward_hooks or m._forward_pre_hooks))
+                        and (kind == "up" or mods[2].stride == [2, 2, 2]) and not (m._forward_hooks or m._forward_pre_hooks)
+                        and mods[0].num_features <= _ops.CX_BN_MAX_C)
             ok[0] = ok[0] and good
         plan = self.__dict__["_doda_coarse"] = steps if ok[0] else False
         return plan
@@ -707,14 +710,14 @@ class SparseConvNet(nn.Module):
             scores = _PointLinear.apply(feats, self.linear.weight, self.linear.bias, input_map, v2p_t)
             if labels is not None:
                 self.voxel_pred = None
-                self.point_scores = scores
+                self.point_scores = scores.detach()   # (for point_predictions: no reference to the score matrix's graph)
                 return cross_entropy(scores, labels, ignore_index)
             return scores
         point_feats = feats[input_map.long()]  # voxel -> point
         scores = self.linear(point_feats.to(self.linear.weight.dtype))
         if labels is not None and not return_mid_feat:
             self.voxel_pred = None
-            self.point_scores = scores
+            self.point_scores = scores.detach()
             return cross_entropy(scores, labels, ignore_index)
         return (point_feats, scores) if return_mid_feat else scores
 
@@ -930,7 +933,11 @@ def voxelize_and_run(cfg, model, batch, device, feature_dtype=torch.float32, fus
                          labels=labels, ignore_index=ignore_index)
         return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None)
     if labels is not None:
-        return cross_entropy(model(inp, p2v), labels, ignore_index)
+        scores = model(inp, p2v)
+        net = model.module if hasattr(model, "module") else model
+        net.voxel_pred = None                 # (point_predictions: this batch's scores, not an earlier call's voxel argmax)
+        net.point_scores = scores.detach()
+        return cross_entropy(scores, labels, ignore_index)
     return model(inp, p2v)
 
 

@@ -593,7 +593,7 @@ def test_generic_conv_fwd_bwd_and_inverse(native_lib, oracle, k, s, p, d):
     assert rel_err(up.weight.grad.cpu(), ref_dwi) < RTOL
 
 
-@pytest.mark.parametrize("c", [20, 13, 64])
+@pytest.mark.parametrize("c", [20, 13, 64, 8, 11])
 def test_fused_cross_entropy(native_lib, c):
     """doda_cross_entropy_fwd/_bwd == nn.CrossEntropyLoss(ignore_index=255): value, gradient, all-ignored case."""
     from doda_amd.model import cross_entropy

@@ -1,4 +1,4 @@
-"""ctypes binding of libdoda_hip.so (include/doda_hip.h and its companion include/doda_selftrain.h).
+"""ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -116,6 +116,21 @@ SELFTRAIN_SIGNATURES = {
 SELFTRAIN_SYMBOLS = tuple(SELFTRAIN_SIGNATURES)
 ST_ABI_VERSION = 1  # include/doda_selftrain.h DODA_ST_ABI_VERSION
 ST_RADIX_BITS, ST_RADIX_LEVELS, ST_MAX_CLASSES = 8, 4, 32
+
+# name -> (restype, argtypes); mirrors include/doda_mix.h (the cuboid-mixing companion ABI, same library)
+c_i64p = C.POINTER(c_i64)
+MIX_SIGNATURES = {
+    "doda_mix_abi_version": (c_i32, []),
+    "doda_mix_blocks": (c_i64, [c_i64p, c_i32]),
+    "doda_mix_bounds": (c_i32, [c_vp, c_i32, c_i64p, c_i32, c_vp, c_vp, c_vp]),
+    "doda_mix_classify": (c_i32, [c_vp, c_vp, c_i64p, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "doda_mix_emit": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64p, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                              c_vp]),
+    "doda_mix_extract": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64p, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+}
+MIX_SYMBOLS = tuple(MIX_SIGNATURES)
+MIX_ABI_VERSION = 1  # include/doda_mix.h DODA_MIX_ABI_VERSION
+MIX_MAX_SEGMENTS, MIX_MAX_CUBOIDS, MIX_MAX_CLASSES, MIX_CHUNK, MIX_FIXED_BITS = 128, 32, 32, 1024, 28
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -136,7 +151,7 @@ def lib():
                 "libdoda_hip.so is not built (%s). Run `python -m doda_amd.build` "
                 "(hipcc, gfx950). doda_amd has no CPU fallback for its native ops." % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(SELFTRAIN_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(SELFTRAIN_SIGNATURES.items()) + list(MIX_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
@@ -147,6 +162,8 @@ def lib():
             raise DodaNativeError("libdoda_hip.so ABI version mismatch")
         if handle.doda_st_abi_version() != ST_ABI_VERSION:
             raise DodaNativeError("libdoda_hip.so self-training ABI version mismatch")
+        if handle.doda_mix_abi_version() != MIX_ABI_VERSION:
+            raise DodaNativeError("libdoda_hip.so cuboid-mixing ABI version mismatch")
         _lib = handle
     return _lib
 

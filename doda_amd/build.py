@@ -31,7 +31,8 @@ def _stamp(src):
     h = hashlib.sha1()
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))   # every shared header
     include = os.path.join(HERE, "..", "include")
-    for p in [src] + headers + [os.path.join(include, "doda_hip.h"), os.path.join(include, "doda_selftrain.h")]:
+    for p in [src] + headers + [os.path.join(include, "doda_hip.h"), os.path.join(include, "doda_selftrain.h"),
+                                      os.path.join(include, "doda_mix.h")]:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())

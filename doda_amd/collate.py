@@ -87,7 +87,9 @@ def collate_device_concat(hb, device, voxel_mode=4):
             "v2p_map_t": v2p_map[:, 1:].t().contiguous(),
             "locs_float": locs_float, "feats": locs_float.clone(), "labels": labels,
             "offsets": hb["offsets"], "spatial_shape": hb["spatial_shape"], "id": hb["id"],
-            "mix_idx": [], "tar_tail_splits": [], "selected_idx": [], "mask1": [], "mask2": [], "tar_splits_class_ratio": []}
+            # (filled by the cuboid-mixing loader, doda_amd.loader.MixedDeviceScenes; empty otherwise)
+            "mix_idx": [], "tar_tail_splits": hb.get("tar_tail_splits", []), "selected_idx": [], "mask1": hb.get("mask1", []),
+            "mask2": hb.get("mask2", []), "tar_splits_class_ratio": hb.get("tar_splits_class_ratio", [])}
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -345,6 +345,11 @@ class DeviceScenes:
 
     @torch.no_grad()
     def _batch(self, ids):
+        m, labels, offsets, bidx = self._rigid(ids)
+        return self._finish(m, labels, offsets, bidx, ids)
+
+    def _rigid(self, ids):
+        """The scenes of a batch concatenated, under their rigid augmentation: (xyz_mid [N, 3], labels, offsets, batch index)."""
         dev, bs = self.device, len(ids)
         base = [(i % self.length) % len(self.xyz) for i in ids]
         sizes = [self.xyz[k].shape[0] for k in base]
@@ -368,6 +373,11 @@ class DeviceScenes:
             m += (torch.rand(m.shape, device=dev, generator=self.gen) - 0.5) * 0.01
         else:
             m = x.clone()
+        return m, labels, offsets, bidx
+
+    def _finish(self, m, labels, offsets, bidx, ids):
+        """Integer voxel coordinates of the (augmented) scenes and the batch dictionary."""
+        dev, bs = self.device, len(ids)
         q = m * self.voxel_scale
         # (per-scene minimum as one reduction per scene: a scatter_reduce of 1.8 M values onto 12 addresses is 50 ms of atomics)
         lo = torch.stack([q[offsets[b]:offsets[b + 1]].amin(0) for b in range(bs)])
@@ -376,6 +386,42 @@ class DeviceScenes:
         locs32 = torch.cat((bidx.to(torch.int32)[:, None], q), 1)
         return {"locs32": locs32, "locs_float": m, "labels32": labels, "offsets": torch.tensor(offsets, dtype=torch.int32),
                 "spatial_shape": np.clip(top, self.full_scale0, None), "id": [int(i) for i in ids]}
+
+
+class MixedDeviceScenes(DeviceScenes):
+    """The target loader of the self-training stage with tail-aware cuboid mixing (reference dataset/mix_dataset.py:59-82 with
+    dataset/augmentor/augmentor_utils.py:255-365): target AND source base scenes resident in HBM; per item the target scene of
+    the sampler and a random source scene, each under the rigid augmentation, mixed on the device (doda_amd.tacm.mix_batch), then
+    the integer voxel coordinates.  Yields what DeviceScenes yields plus mask1 / mask2 (which points came from the target scene),
+    tar_tail_splits and tar_splits_class_ratio (for the split sampler's update after the target pass).  set_labels replaces the
+    TARGET side's labels (pseudo labels); the source side keeps its ground truth.  The mixing's read-backs happen here, on the
+    loader thread and stream."""
+
+    def __init__(self, paths, source_paths, length, voxel_scale, seed, batch_size, rank, world, device, tacm_cfg, split_sampler,
+                 augment=True, shuffle=True, full_scale0=128, source_seed=None):
+        super().__init__(paths, length, voxel_scale, seed, batch_size, rank, world, device, augment=augment, shuffle=shuffle,
+                         full_scale0=full_scale0)
+        self.source = DeviceScenes(source_paths, len(source_paths), voxel_scale, seed + 1 if source_seed is None else source_seed,
+                                   batch_size, rank, world, device, augment=augment, shuffle=False, full_scale0=full_scale0)
+        self.tacm_cfg, self.split_sampler = tacm_cfg, split_sampler
+
+    @torch.no_grad()
+    def _batch(self, ids):
+        from . import tacm
+        rng = np.random.default_rng((self.seed * 1000003 + 7 * ids[0] + 3) & 0x7fffffff)
+        src_ids = [int(v) for v in rng.integers(0, len(self.source.xyz), len(ids))]          # mix_dataset.py:67
+        tm, tl, toff, _ = self._rigid(ids)
+        sm, sl, soff, _ = self.source._rigid(src_ids)
+        draws = [tacm.SeededDraws((self.seed * 1000003 + 11 * i + 5) & 0x7fffffff) for i in ids]
+        mixed = tacm.mix_batch(tm, tl, toff, sm, sl, soff, self.tacm_cfg, self.split_sampler, draws)
+        offsets = mixed["offsets"]
+        sizes = [offsets[b + 1] - offsets[b] for b in range(len(ids))]
+        bidx = torch.repeat_interleave(torch.arange(len(ids), device=self.device), torch.tensor(sizes, device=self.device),
+                                       output_size=offsets[-1])
+        out = self._finish(mixed["xyz_mid"], mixed["labels"], offsets, bidx, ids)
+        for k in ("mask1", "mask2", "tar_tail_splits", "tar_splits_class_ratio"):
+            out[k] = mixed[k]
+        return out
 
 
 _OWN_CACHES = []      # cache directories this PROCESS created privately (DODA_PRIVATE_SCENES=1): the only ones it may delete

@@ -54,6 +54,23 @@ def resolve_weight(weight, pretrain_dir):
     raise FileNotFoundError("--weight %s: neither a file nor %s" % (weight, cand))
 
 
+SAMPLER_FILE = "split_sampler.pth"
+
+
+def init_split_sampler(trainer, pseudo_dir, ckpt_dir, resumed, log=print):
+    """tool/st.py:362-369: the split sampler's class ratio from the pseudo labels' class_ratio.txt, its thresholds into the mixing
+    configuration; a resumed run takes the saved queues and ratios of ckpt/split_sampler.pth instead."""
+    import numpy as np
+    sampler = trainer.split_sampler
+    sampler.init_class_ratio(np.loadtxt(Path(pseudo_dir) / "class_ratio.txt"))
+    saved = Path(ckpt_dir) / SAMPLER_FILE
+    if resumed and saved.exists():
+        sampler.load_sampler(saved, device=trainer.device)
+        log("split sampler: loaded %s" % saved)
+    sampler.update_cfg(trainer.tacm)
+    log("split sampler: tail classes %s, ratio %s" % (list(sampler.tail_class_idx), list(sampler.tail_class_ratio)))
+
+
 def main(argv=None):
     from . import dist as ddist
     from . import pseudo_labels as pl
@@ -62,6 +79,10 @@ def main(argv=None):
         raise NotImplementedError("--weight_ema: the EMA teacher of tool/st.py is not part of doda_amd.st")
     if "SELF_TRAIN" not in cfg:
         raise ValueError("doda_amd.st needs a SELF_TRAIN section (cfgs/synthetic/spconv_st.yaml)")
+    from .tacm import TacmConfig
+    if TacmConfig.from_cfg(cfg).enabled and (args.host_loader or args.inline_loader):
+        raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
+                         "(drop --host_loader / --inline_loader, or disable tacm)")
     world, rank, device = tr.setup(args, cfg)
     pretrain_dir, output_dir, ckpt_dir, pseudo_dir = run_dirs(args, cfg)
     if rank == 0:
@@ -82,7 +103,11 @@ def main(argv=None):
         log("pseudo labels: %s" % ("generated" if out is not None else "reused from %s" % pseudo_dir))
         labels = pl.read_scene_labels(pseudo_dir, paths)
         trainer.set_split_labels("target", [torch.from_numpy(a) for a in labels])
-    tr.run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch)
+        if trainer.tacm.enabled:
+            init_split_sampler(trainer, pseudo_dir, ckpt_dir, args.start_epoch > 0, log)
+    tr.run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch,
+                  after_epoch=(lambda _e: trainer.split_sampler.save_sampler(ckpt_dir / SAMPLER_FILE))
+                  if (trainer.tacm.enabled and rank == 0) else None)      # (tool/st.py:396-398)
     tr.finish(trainer, args, rank, world)
     if not args.preserve_pseudo_labels and rank == 0:
         shutil.rmtree(pseudo_dir, ignore_errors=True)

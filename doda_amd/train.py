@@ -325,6 +325,13 @@ class Trainer:
         self.prefetch = PyramidPrefetcher(device, self.n_levels) if device.type == "cuda" else None
         self.iters_done = 0
         self._loaders, self._datasets, self._labels = {}, {}, {}
+        # tail-aware cuboid mixing of the target batches (DATA_CONFIG_TAR.DATA_AUG.tacm; absent = the plain target loader)
+        from .tacm import SplitSampler, TacmConfig
+        self.tacm = TacmConfig.from_cfg(cfg)
+        self.split_sampler = SplitSampler(self.tacm) if self.tacm.enabled else None
+        if self.tacm.enabled and (args.host_loader or args.inline_loader):
+            raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
+                             "(drop --host_loader / --inline_loader, or disable tacm)")
         self.step_times = []      # (iterations, seconds) of the steady part of every epoch (see train_epoch)
 
     # one forward + backward of one batch; `domain`: None | "source" | "target" (DSNorm statistics)
@@ -363,6 +370,15 @@ class Trainer:
             if self.args.host_loader:   # (same sampler seed and the same spatial-shape clip as the HBM-resident loader below)
                 self._loaders[split] = host_loader(ds, self.args.batch_size, self.rank, self.world, self.args.workers,
                                                    shuffle=split != "val", seed=ds.seed + seed, full_scale0=fs0)
+            elif split == "target" and self.tacm.enabled:
+                # the mixed target loader (reference dataset/__init__.py:141-143): target scenes + the source split's base scenes
+                from .loader import MixedDeviceScenes
+                self._loader("train")
+                src = self._datasets["train"]
+                dsc = MixedDeviceScenes(ds.paths, src.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank,
+                                        self.world, self.device, self.tacm, self.split_sampler, augment=ds.augment, shuffle=True,
+                                        full_scale0=fs0, source_seed=src.seed + seed + 1)
+                self._loaders[split] = (dsc, dsc)
             else:
                 dsc = DeviceScenes(ds.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank, self.world,
                                    self.device, augment=ds.augment, shuffle=split != "val",
@@ -398,6 +414,24 @@ class Trainer:
                 self._loader(split)
         else:
             dl.set_labels(labels)
+
+    def update_split_sampler(self, batch):
+        """After the target pass (tool/st.py:82-97): the batch's tail-class cuboids, regrouped per tail class, go into the queues;
+        the class counts of the queue cuboids it used, summed over ranks, move the sampler's class ratio.  Each rank keeps its own
+        queue (the reference all-gathers pickled cuboids)."""
+        num_c = self.tacm.num_class
+        tail = batch.get("tar_tail_splits", [])
+        if len(tail):
+            self.split_sampler.update([[c for lst in tail[i::num_c] for c in lst] for i in range(num_c)])
+        ratio = batch.get("tar_splits_class_ratio", [])
+        if self.tacm.update_class_ratio and len(ratio):
+            ratio = np.asarray(ratio, dtype=np.float64)
+            if self.world > 1:
+                import torch.distributed as dist
+                t = torch.from_numpy(ratio).to(self.device)
+                dist.all_reduce(t)
+                ratio = t.cpu().numpy()
+            self.split_sampler.update_class_ratio(ratio)
 
     def _batches(self, epoch, split):
         """(batch, prebuilt rulebooks): worker processes produce the scenes, a feeder thread collates them on the device and
@@ -456,6 +490,8 @@ class Trainer:
                 if self.reducer is not None:
                     self.reducer.arm()      # (the second backward pass completes the gradients: its hook may start the exchange)
                 self._pass(tb, tp, "target", st.get("TAR", Config()).get("loss_weight", 1.0))
+                if self.tacm.enabled:
+                    self.update_split_sampler(tb)
             else:
                 if self.reducer is not None:
                     self.reducer.arm()
@@ -562,11 +598,14 @@ def restore(trainer, args, ckpt_dir, log):
     return best_miou, best_epoch
 
 
-def run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch):
-    """tool/train.py:235-268: epochs from args.start_epoch, checkpoints, evaluation and the best checkpoint."""
+def run_epochs(trainer, args, cfg, ckpt_dir, rank, log, best_miou, best_epoch, after_epoch=None):
+    """tool/train.py:235-268: epochs from args.start_epoch, checkpoints, evaluation and the best checkpoint.  after_epoch(epoch_log):
+    called after every training epoch (doda_amd.st saves the split sampler there)."""
     for epoch in range(args.start_epoch, args.epochs):
         trainer.train_epoch(epoch, args.epochs)
         epoch_log = epoch + 1
+        if after_epoch is not None:
+            after_epoch(epoch_log)
         if rank == 0 and epoch_log % args.ckpt_save_freq == 0:
             filename = ckpt_dir / ("train_epoch_%d.pth" % epoch_log)
             log("Saving checkpoint to: %s" % filename)

@@ -1,4 +1,5 @@
-"""ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h).
+"""ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
+include/doda_aug.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -131,6 +132,22 @@ MIX_SIGNATURES = {
 MIX_SYMBOLS = tuple(MIX_SIGNATURES)
 MIX_ABI_VERSION = 1  # include/doda_mix.h DODA_MIX_ABI_VERSION
 MIX_MAX_SEGMENTS, MIX_MAX_CUBOIDS, MIX_MAX_CLASSES, MIX_CHUNK, MIX_FIXED_BITS = 128, 32, 32, 1024, 28
+
+# name -> (restype, argtypes); mirrors include/doda_aug.h (the augmentation-pipeline companion ABI, same library)
+c_i32p, c_f64p, c_f64 = C.POINTER(c_i32), C.POINTER(C.c_double), C.c_double
+AUG_SIGNATURES = {
+    "doda_aug_abi_version": (c_i32, []),
+    "doda_aug_blocks": (c_i64, [c_i64p, c_i32]),
+    "doda_aug_affine": (c_i32, [c_vp, c_i64p, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "doda_aug_blur": (c_i32, [c_vp, c_vp, c_i32p, c_i32, c_vp]),
+    "doda_aug_displace": (c_i32, [c_vp, c_i64p, c_i32, c_vp, c_i32p, c_f64p, c_vp, c_vp, c_vp]),
+    "doda_aug_crop": (c_i32, [c_vp, c_i64p, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "doda_aug_emit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64p, c_i32, c_vp, c_f64, c_vp, c_vp, c_vp, c_i32p, c_i64p, c_i32, c_vp,
+                              c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+}
+AUG_SYMBOLS = tuple(AUG_SIGNATURES)
+AUG_ABI_VERSION = 1  # include/doda_aug.h DODA_AUG_ABI_VERSION
+AUG_MAX_SEGMENTS, AUG_CHUNK, AUG_MAX_GRID_CELLS = 64, 1024, 1 << 24
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -151,7 +168,8 @@ def lib():
                 "libdoda_hip.so is not built (%s). Run `python -m doda_amd.build` "
                 "(hipcc, gfx950). doda_amd has no CPU fallback for its native ops." % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(SELFTRAIN_SIGNATURES.items()) + list(MIX_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(SELFTRAIN_SIGNATURES.items()) + list(MIX_SIGNATURES.items()) \
+                + list(AUG_SIGNATURES.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:
@@ -164,6 +182,8 @@ def lib():
             raise DodaNativeError("libdoda_hip.so self-training ABI version mismatch")
         if handle.doda_mix_abi_version() != MIX_ABI_VERSION:
             raise DodaNativeError("libdoda_hip.so cuboid-mixing ABI version mismatch")
+        if handle.doda_aug_abi_version() != AUG_ABI_VERSION:
+            raise DodaNativeError("libdoda_hip.so augmentation ABI version mismatch")
         _lib = handle
     return _lib
 

@@ -32,7 +32,7 @@ def _stamp(src):
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))   # every shared header
     include = os.path.join(HERE, "..", "include")
     for p in [src] + headers + [os.path.join(include, "doda_hip.h"), os.path.join(include, "doda_selftrain.h"),
-                                      os.path.join(include, "doda_mix.h")]:
+                                      os.path.join(include, "doda_mix.h"), os.path.join(include, "doda_aug.h")]:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())

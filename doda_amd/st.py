@@ -80,6 +80,8 @@ def main(argv=None):
     if "SELF_TRAIN" not in cfg:
         raise ValueError("doda_amd.st needs a SELF_TRAIN section (cfgs/synthetic/spconv_st.yaml)")
     from .tacm import TacmConfig
+    from .train import check_aug_loader
+    check_aug_loader(cfg, args)
     if TacmConfig.from_cfg(cfg).enabled and (args.host_loader or args.inline_loader):
         raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
                          "(drop --host_loader / --inline_loader, or disable tacm)")

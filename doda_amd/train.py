@@ -291,6 +291,23 @@ def make_loader(cfg, args, device, rank, world, epoch, split="train"):
 
 
 # ------------------------------------------------------------------------------------------------ training
+
+def aug_config_of(cfg, split):
+    """doda_amd.aug.AugConfig of a split's dataset config: DATA_CONFIG_TAR for the target split (where the experiment has one),
+    DATA_CONFIG otherwise.  No DATA_AUG.aug_list there = disabled = the loaders' own rigid augmentation."""
+    from .aug import AugConfig
+    key = "DATA_CONFIG_TAR" if (split == "target" and "DATA_CONFIG_TAR" in cfg) else "DATA_CONFIG"
+    return AugConfig.from_cfg(cfg[key])
+
+
+def check_aug_loader(cfg, args):
+    """DATA_AUG.aug_list runs on the device-resident loader only, as DATA_AUG.tacm does."""
+    if (getattr(args, "host_loader", False) or getattr(args, "inline_loader", False)) and \
+            any(aug_config_of(cfg, split).enabled for split in ("train", "target")):
+        raise ValueError("DATA_AUG.aug_list is set: scene_aug / elastic / crop run on the device-resident loader only "
+                         "(drop --host_loader / --inline_loader, or remove the aug_list)")
+
+
 class Trainer:
     def __init__(self, args, cfg, device, rank=0, world=1, log=print):
         from . import dist as ddist
@@ -332,6 +349,7 @@ class Trainer:
         if self.tacm.enabled and (args.host_loader or args.inline_loader):
             raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
                              "(drop --host_loader / --inline_loader, or disable tacm)")
+        check_aug_loader(cfg, args)
         self.step_times = []      # (iterations, seconds) of the steady part of every epoch (see train_epoch)
 
     # one forward + backward of one batch; `domain`: None | "source" | "target" (DSNorm statistics)
@@ -377,12 +395,12 @@ class Trainer:
                 src = self._datasets["train"]
                 dsc = MixedDeviceScenes(ds.paths, src.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank,
                                         self.world, self.device, self.tacm, self.split_sampler, augment=ds.augment, shuffle=True,
-                                        full_scale0=fs0, source_seed=src.seed + seed + 1)
+                                        full_scale0=fs0, source_seed=src.seed + seed + 1, aug_cfg=aug_config_of(self.cfg, split))
                 self._loaders[split] = (dsc, dsc)
             else:
                 dsc = DeviceScenes(ds.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank, self.world,
                                    self.device, augment=ds.augment, shuffle=split != "val",
-                                   full_scale0=fs0)
+                                   full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split))
                 self._loaders[split] = (dsc, dsc)
             if split in self._labels:
                 self._apply_labels(split)

@@ -152,6 +152,12 @@ OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_D
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
 
+# the core ABI and its companions: (signature table, version symbol, expected version, name for the error)
+_ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
+         (SELFTRAIN_SIGNATURES, "doda_st_abi_version", ST_ABI_VERSION, "self-training ABI"),
+         (MIX_SIGNATURES, "doda_mix_abi_version", MIX_ABI_VERSION, "cuboid-mixing ABI"),
+         (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"))
+
 _lib = None
 
 
@@ -168,22 +174,16 @@ def lib():
                 "libdoda_hip.so is not built (%s). Run `python -m doda_amd.build` "
                 "(hipcc, gfx950). doda_amd has no CPU fallback for its native ops." % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(SELFTRAIN_SIGNATURES.items()) + list(MIX_SIGNATURES.items()) \
-                + list(AUG_SIGNATURES.items()):
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise DodaNativeError("libdoda_hip.so lacks symbol %s (stale build?)" % name) from e
-            fn.restype = res
-            fn.argtypes = args
-        if handle.doda_abi_version() != ABI_VERSION:
-            raise DodaNativeError("libdoda_hip.so ABI version mismatch")
-        if handle.doda_st_abi_version() != ST_ABI_VERSION:
-            raise DodaNativeError("libdoda_hip.so self-training ABI version mismatch")
-        if handle.doda_mix_abi_version() != MIX_ABI_VERSION:
-            raise DodaNativeError("libdoda_hip.so cuboid-mixing ABI version mismatch")
-        if handle.doda_aug_abi_version() != AUG_ABI_VERSION:
-            raise DodaNativeError("libdoda_hip.so augmentation ABI version mismatch")
+        for table, version_fn, version, what in _ABIS:
+            for name, (res, args) in table.items():
+                try:
+                    fn = getattr(handle, name)
+                except AttributeError as e:
+                    raise DodaNativeError("libdoda_hip.so lacks symbol %s (stale build?)" % name) from e
+                fn.restype = res
+                fn.argtypes = args
+            if getattr(handle, version_fn)() != version:
+                raise DodaNativeError("libdoda_hip.so %s version mismatch" % what)
         _lib = handle
     return _lib
 

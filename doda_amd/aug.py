@@ -12,14 +12,14 @@ The reference augments every sample with numpy / scipy in DataLoader workers.  H
 
 `shuffle` is accepted and does nothing (a row permutation of the points: DESIGN.md §2); `vss` raises NotImplementedError.
 Deviations from the reference are listed in DESIGN.md §13."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, segments
 from ._lib import check, lib
+from .segments import SeededDraws, launch_on, offsets_h, per_sample, stream_handle   # noqa: F401  (SeededDraws: for the callers)
 
 KNOWN = ("scene_aug", "elastic", "crop", "shuffle")
 MAX_REDRAWS = 4          # an emptied sample is drawn again at most this often (reference dataset/scannet.py:72-73 recurses)
@@ -91,19 +91,6 @@ class AugConfig:
 
 
 # ------------------------------------------------------------------------------------------------ randomness
-class SeededDraws:
-    """The production `draws` object: every random number of a sample from one seeded numpy generator."""
-
-    def __init__(self, seed):
-        self.g = np.random.default_rng(seed)
-
-    def rand(self, n=None):
-        return self.g.random() if n is None else self.g.random(n)
-
-    def randn(self, shape):
-        return self.g.standard_normal(tuple(int(v) for v in shape))
-
-
 class RandomStateDraws:
     """Replays numpy's legacy global stream after numpy.random.seed(seed) — the stream the reference draws from — and keeps the
     kinds and sizes of the draws asked for (`log`)."""
@@ -216,24 +203,8 @@ class CropPlan:
 
 
 # ------------------------------------------------------------------------------------------------ device calls
-def _offsets_h(offsets):
-    arr = (C.c_int64 * len(offsets))(*[int(v) for v in offsets])
-    return arr, len(offsets) - 1
-
-
-def _stream(stream):
-    if stream is not None:
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-    from .ops import _stream as cur
-    return cur()
-
-
 def n_blocks(offsets):
-    arr, n_seg = _offsets_h(offsets)
-    nb = lib().doda_aug_blocks(arr, n_seg)
-    if nb < 0:
-        raise _lib.DodaNativeError("doda_aug_blocks: invalid segment offsets")
-    return int(nb)
+    return segments.n_blocks(lib(), "doda_aug_blocks", offsets)
 
 
 def blur_grids(noise, bbs, stream=None):
@@ -243,15 +214,15 @@ def blur_grids(noise, bbs, stream=None):
     bb = np.ascontiguousarray(bbs, dtype=np.int32)
     assert int(3 * bb.astype(np.int64).prod(1).sum()) == noise.numel()
     tmp = torch.empty_like(noise)
-    check(lib().doda_aug_blur(noise.data_ptr(), tmp.data_ptr(), bb.ctypes.data_as(_lib.c_i32p), bb.shape[0], _stream(stream)),
+    check(lib().doda_aug_blur(noise.data_ptr(), tmp.data_ptr(), bb.ctypes.data_as(_lib.c_i32p), bb.shape[0], stream_handle(stream)),
           "doda_aug_blur")
     return noise
 
 
 def _run(xyz, labels, offsets, cfg, draws, masks, stream, return_debug, batch0):
     dev, B, n = xyz.device, len(offsets) - 1, int(offsets[-1])
-    L, st = lib(), _stream(stream)
-    arr, ns = _offsets_h(offsets)
+    L, st = lib(), stream_handle(stream)
+    arr, ns = offsets_h(offsets)
     sizes = [int(offsets[b + 1]) - int(offsets[b]) for b in range(B)]
     nb = max(1, n_blocks(offsets))
     f64 = dict(dtype=torch.float64, device=dev)
@@ -386,18 +357,9 @@ def augment_batch(xyz_mid, labels, offsets, cfg, draws, masks=None, stream=None,
     B = len(offsets) - 1
     if B > _lib.AUG_MAX_SEGMENTS:
         raise ValueError("augment_batch: at most %d scenes per call" % _lib.AUG_MAX_SEGMENTS)
-    if not isinstance(draws, (list, tuple)):
-        draws = [draws]
-    if len(draws) != B:
-        raise ValueError("augment_batch: one draws object per sample")
+    draws = per_sample(draws, B, "augment_batch")
     assert xyz_mid.is_cuda and xyz_mid.dtype == torch.float32 and xyz_mid.dim() == 2 and xyz_mid.shape[1] == 3
     assert int(offsets[-1]) == xyz_mid.shape[0] == labels.shape[0]
     xyz_mid, labels = xyz_mid.contiguous(), labels.to(torch.int32).contiguous()
-    ctx = torch.cuda.stream(stream) if (stream is not None and hasattr(stream, "cuda_stream")) else None
-    if ctx is not None:
-        ctx.__enter__()
-    try:
+    with launch_on(stream):
         return _run(xyz_mid, labels, [int(v) for v in offsets], cfg, draws, masks, stream, return_debug, batch0)
-    finally:
-        if ctx is not None:
-            ctx.__exit__(None, None, None)

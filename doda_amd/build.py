@@ -29,10 +29,10 @@ def _sources():
 
 def _stamp(src):
     h = hashlib.sha1()
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))   # every shared header
     include = os.path.join(HERE, "..", "include")
-    for p in [src] + headers + [os.path.join(include, "doda_hip.h"), os.path.join(include, "doda_selftrain.h"),
-                                      os.path.join(include, "doda_mix.h"), os.path.join(include, "doda_aug.h")]:
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))   # every shared header
+    headers += sorted(os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h"))   # and every ABI header
+    for p in [src] + headers:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())

@@ -2,32 +2,25 @@
 //
 // reference dataset/augmentor/data_augmentor.py:171-230 and augmentor_utils.py:61-104,449-472 run per sample in DataLoader workers:
 // a 3x3 matmul, two elastic passes (scipy.ndimage.convolve x 6 on three random grids, scipy's RegularGridInterpolator per point), the
-// subtraction of the minimum and the crop loop of boolean masks.  Here the scenes of a batch are SEGMENTS of one array (as in
-// mix.hip: chunks of DODA_AUG_CHUNK points, one workgroup each, the offsets as validated launch arguments), the coordinates live
-// in an fp64 [N][3] array `pos` from the affine step to the emit step, and the host decides everything random from a few bytes
-// per segment (doda_amd.aug).
+// subtraction of the minimum and the crop loop of boolean masks.  Here the scenes of a batch are SEGMENTS of one array
+// (segments.hpp: chunks of DODA_AUG_CHUNK points, one workgroup each, the offsets as validated launch arguments), the coordinates
+// live in an fp64 [N][3] array `pos` from the affine step to the emit step, and the host decides everything random from a few
+// bytes per segment (doda_amd.aug).
 //
 // Precision: every coordinate operation is the reference's fp64 operation in the reference's order (the library is compiled with
 // -ffp-contract=off), so a truncated voxel coordinate differs from the reference's only where BLAS's fused dot product or scipy's
 // summation differs in the last bits AND the value sits on an integer.  The blur accumulates three taps in fp64 and rounds to fp32
 // per pass, as scipy.ndimage does for fp32 input.
 //
-// Order and determinism: outputs keep the points' order; a kept point's row = rows kept in earlier chunks of its segment (blk_cnt,
-// stored by the crop pass) + rows kept earlier in its chunk (wave ballot + popcount).  Bounds are min / max (exact in any order);
-// counts and the coordinate maximum are integer atomics.
-#include "common.hpp"
+// Order and determinism: outputs keep the points' order by segments.hpp's stable compaction over blk_cnt, the per-chunk counts the
+// crop pass stored.  Bounds are min / max (exact in any order); counts and the coordinate maximum are integer atomics.
+#include "segments.hpp"
 #include "../../include/doda_aug.h"
 
-namespace {
-constexpr int AG_BLOCK = 256;
-constexpr int AG_WAVES = AG_BLOCK / DODA_WAVE;
-constexpr int AG_ROUNDS = DODA_AUG_CHUNK / AG_BLOCK;
+static_assert(DODA_AUG_CHUNK == SEG_CHUNK, "include/doda_aug.h promises the chunk size of segments.hpp");
 
-struct AugSegs {                                         // launch argument: segment offsets and first chunk of every segment
-    int32_t n;
-    int32_t off[DODA_AUG_MAX_SEGMENTS + 1];
-    int32_t blk[DODA_AUG_MAX_SEGMENTS + 1];
-};
+namespace {
+using AugSegs = Segs<DODA_AUG_MAX_SEGMENTS>;
 
 struct AugGrids {                                        // launch argument: the noise grids of the segments
     int32_t bb[DODA_AUG_MAX_SEGMENTS][3];
@@ -40,22 +33,6 @@ struct AugOut {                                          // launch argument of t
     long long base[DODA_AUG_MAX_SEGMENTS];
     int32_t use_valid[DODA_AUG_MAX_SEGMENTS];
 };
-
-int make_segs(const int64_t *offsets_h, int32_t n_seg, AugSegs *s) {
-    if (!offsets_h || n_seg < 1) return DODA_ERR_INVALID;
-    if (n_seg > DODA_AUG_MAX_SEGMENTS) return DODA_ERR_UNSUPPORTED;
-    if (offsets_h[0] != 0) return DODA_ERR_INVALID;
-    s->n = n_seg;
-    s->off[0] = 0;
-    s->blk[0] = 0;
-    for (int k = 0; k < n_seg; ++k) {
-        const int64_t a = offsets_h[k], b = offsets_h[k + 1];
-        if (b < a || b > 0x7fffffffLL) return DODA_ERR_INVALID;
-        s->off[k + 1] = (int32_t)b;
-        s->blk[k + 1] = s->blk[k] + (int32_t)((b - a + DODA_AUG_CHUNK - 1) / DODA_AUG_CHUNK);
-    }
-    return DODA_OK;
-}
 
 // bb_h [n_seg][3] -> g->bb / g->base; a segment has a grid (all three > 0, at least 2 per axis) or none (0 0 0)
 int make_grids(const int32_t *bb_h, int32_t n_seg, AugGrids *g) {
@@ -80,40 +57,6 @@ int make_grids(const int32_t *bb_h, int32_t n_seg, AugGrids *g) {
     return DODA_OK;
 }
 
-struct Chunk { int seg, base, end; };
-
-// the chunk of this workgroup (blockIdx.x < s.blk[s.n]: the grid is exactly the chunks)
-__device__ __forceinline__ Chunk chunk_of_block(const AugSegs &s) {
-    const int b = blockIdx.x;
-    int seg = 0;
-    for (int k = 0; k < s.n; ++k)
-        if (b >= s.blk[k + 1]) seg = k + 1;              // (empty segments have no chunk: skipped)
-    if (seg >= s.n) seg = s.n - 1;
-    Chunk c;
-    c.seg = seg;
-    c.base = s.off[seg] + (b - s.blk[seg]) * DODA_AUG_CHUNK;
-    const int end = c.base + DODA_AUG_CHUNK;
-    c.end = end < s.off[seg + 1] ? end : s.off[seg + 1];
-    return c;
-}
-
-// min / max of 3 + 3 doubles over the workgroup -> lo / hi of thread 0
-__device__ __forceinline__ void block_minmax(double lo[3], double hi[3], double (*sh)[6]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fmin(lo[k], __shfl_xor(lo[k], d, 64));
-            hi[k] = fmax(hi[k], __shfl_xor(hi[k], d, 64));
-        }
-    if (lane_id() == 0)
-        for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = lo[k]; sh[threadIdx.x >> 6][3 + k] = hi[k]; }
-    doda_sync();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < AG_WAVES; ++w)
-            for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], sh[w][k]); hi[k] = fmax(hi[k], sh[w][3 + k]); }
-}
-
 // xyz[i] @ m (row-major 3x3), the fp32 point widened: (x0 * m0k + x1 * m1k) + x2 * m2k
 __device__ __forceinline__ void point_matmul(const float *__restrict__ xyz, int i, const double *m, double out[3]) {
     const double x0 = (double)xyz[(size_t)i * 3], x1 = (double)xyz[(size_t)i * 3 + 1], x2 = (double)xyz[(size_t)i * 3 + 2];
@@ -121,15 +64,15 @@ __device__ __forceinline__ void point_matmul(const float *__restrict__ xyz, int 
     for (int k = 0; k < 3; ++k) out[k] = (x0 * m[k] + x1 * m[3 + k]) + x2 * m[6 + k];
 }
 
-__global__ __launch_bounds__(AG_BLOCK) void aug_affine(const float *__restrict__ xyz, AugSegs s, const double *__restrict__ mat,
+__global__ __launch_bounds__(SEG_BLOCK) void aug_affine(const float *__restrict__ xyz, AugSegs s, const double *__restrict__ mat,
                                                       double scale, double *__restrict__ pos, double *__restrict__ part) {
-    __shared__ double sh[AG_WAVES][6];
+    __shared__ double sh[SEG_WAVES][6];
     __shared__ double m[9];
     const Chunk ch = chunk_of_block(s);
     if (threadIdx.x < 9) m[threadIdx.x] = mat[ch.seg * 9 + threadIdx.x];
     doda_sync();
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = ch.base + threadIdx.x; i < ch.end; i += AG_BLOCK) {
+    for (int i = ch.base + threadIdx.x; i < ch.end; i += SEG_BLOCK) {
         double p[3];
         point_matmul(xyz, i, m, p);
 #pragma unroll
@@ -141,33 +84,22 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_affine(const float *__restrict__
         }
     }
     doda_sync();
-    block_minmax(lo, hi, sh);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { part[(size_t)blockIdx.x * 6 + k] = lo[k]; part[(size_t)blockIdx.x * 6 + 3 + k] = hi[k]; }
+    block_minmax(lo, hi, sh, part + (size_t)blockIdx.x * 6);
 }
 
-// one workgroup per segment: its chunks' partial bounds -> bounds[seg] (segments with skip[seg] != 0 are left alone)
-__global__ __launch_bounds__(AG_BLOCK) void aug_bounds_final(AugSegs s, AugGrids g, int use_grids, const double *__restrict__ part,
+// one workgroup per segment: its chunks' partial bounds -> bounds[seg] (with use_grids, a segment without a grid is left alone)
+__global__ __launch_bounds__(SEG_BLOCK) void aug_bounds_final(AugSegs s, AugGrids g, int use_grids, const double *__restrict__ part,
                                                             double *__restrict__ bounds) {
-    __shared__ double sh[AG_WAVES][6];
+    __shared__ double sh[SEG_WAVES][6];
     const int seg = blockIdx.x;
     if (use_grids && g.bb[seg][0] == 0) return;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = s.blk[seg] + threadIdx.x; b < s.blk[seg + 1]; b += AG_BLOCK)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fmin(lo[k], part[(size_t)b * 6 + k]);
-            hi[k] = fmax(hi[k], part[(size_t)b * 6 + 3 + k]);
-        }
-    block_minmax(lo, hi, sh);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { bounds[seg * 6 + k] = lo[k]; bounds[seg * 6 + 3 + k] = hi[k]; }
+    segment_minmax(s, seg, part, sh, bounds);
 }
 
 // one box pass along `axis` over every cell of every grid of the batch
-__global__ __launch_bounds__(AG_BLOCK) void aug_blur_pass(const float *__restrict__ in, float *__restrict__ out, AugGrids g, int n_seg,
+__global__ __launch_bounds__(SEG_BLOCK) void aug_blur_pass(const float *__restrict__ in, float *__restrict__ out, AugGrids g, int n_seg,
                                                          int axis) {
-    const int t = blockIdx.x * AG_BLOCK + threadIdx.x;
+    const int t = blockIdx.x * SEG_BLOCK + threadIdx.x;
     if (t >= g.base[n_seg]) return;
     int seg = 0;
     for (int k = 1; k < n_seg; ++k)
@@ -201,9 +133,9 @@ __device__ __forceinline__ bool axis_interval(double x, double a0, double step, 
     return true;
 }
 
-__global__ __launch_bounds__(AG_BLOCK) void aug_displace(double *__restrict__ pos, AugSegs s, const float *__restrict__ noise,
+__global__ __launch_bounds__(SEG_BLOCK) void aug_displace(double *__restrict__ pos, AugSegs s, const float *__restrict__ noise,
                                                         AugGrids g, double *__restrict__ part) {
-    __shared__ double sh[AG_WAVES][6];
+    __shared__ double sh[SEG_WAVES][6];
     const Chunk ch = chunk_of_block(s);
     const int b0 = g.bb[ch.seg][0], b1 = g.bb[ch.seg][1], b2 = g.bb[ch.seg][2];
     if (b0 == 0) return;                                 // (uniform over the workgroup: no elastic pass for this segment)
@@ -212,7 +144,7 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_displace(double *__restrict__ po
     const int cells = b0 * b1 * b2;
     const float *grid = noise + g.base[ch.seg];
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = ch.base + threadIdx.x; i < ch.end; i += AG_BLOCK) {
+    for (int i = ch.base + threadIdx.x; i < ch.end; i += SEG_BLOCK) {
         double x[3], t[3];
         int ix[3];
         bool inside = true;
@@ -241,12 +173,10 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_displace(double *__restrict__ po
             hi[k] = fmax(hi[k], v);
         }
     }
-    block_minmax(lo, hi, sh);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { part[(size_t)blockIdx.x * 6 + k] = lo[k]; part[(size_t)blockIdx.x * 6 + 3 + k] = hi[k]; }
+    block_minmax(lo, hi, sh, part + (size_t)blockIdx.x * 6);
 }
 
-__global__ __launch_bounds__(AG_BLOCK) void aug_crop(const double *__restrict__ pos, AugSegs s, const double *__restrict__ par,
+__global__ __launch_bounds__(SEG_BLOCK) void aug_crop(const double *__restrict__ pos, AugSegs s, const double *__restrict__ par,
                                                     uint8_t *__restrict__ valid, int32_t *__restrict__ count,
                                                     int32_t *__restrict__ blk_cnt) {
     __shared__ double p[10];
@@ -258,7 +188,7 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_crop(const double *__restrict__ 
     if (p[9] == 0.0) return;                             // (uniform over the workgroup: this segment is not tested)
     const bool first = p[9] > 1.0;
     int mine = 0;
-    for (int i = ch.base + threadIdx.x; i < ch.end; i += AG_BLOCK) {
+    for (int i = ch.base + threadIdx.x; i < ch.end; i += SEG_BLOCK) {
         bool t = first || valid[i] != 0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -278,7 +208,7 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_crop(const double *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(AG_BLOCK) void aug_emit(const float *__restrict__ xyz, const double *__restrict__ pos,
+__global__ __launch_bounds__(SEG_BLOCK) void aug_emit(const float *__restrict__ xyz, const double *__restrict__ pos,
                                                     const int32_t *__restrict__ labels, const uint8_t *__restrict__ mask1,
                                                     const uint8_t *__restrict__ mask2, AugSegs s, AugOut o,
                                                     const double *__restrict__ mat, double feat_scale, const double *__restrict__ par,
@@ -288,38 +218,24 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_emit(const float *__restrict__ x
                                                     uint8_t *__restrict__ out_mask2, int32_t *__restrict__ top, long long out_len) {
     __shared__ double p[6];
     __shared__ double m[9];
-    __shared__ int before;
-    __shared__ int wcnt[AG_WAVES];
+    __shared__ Compact cp;
     __shared__ int tmax[3];
     const Chunk ch = chunk_of_block(s);
     const bool use_valid = o.use_valid[ch.seg] != 0;
     if (threadIdx.x < 6) p[threadIdx.x] = par[ch.seg * 10 + threadIdx.x];
     if (threadIdx.x < 9) m[threadIdx.x] = mat[ch.seg * 9 + threadIdx.x];
     if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
-    if (threadIdx.x == 0) before = use_valid ? 0 : (blockIdx.x - s.blk[ch.seg]) * DODA_AUG_CHUNK;
+    compact_init(cp, ch, use_valid);
     doda_sync();
-    if (use_valid) {                                     // rows kept in the earlier chunks of this segment
-        int local = 0;
-        for (int b = s.blk[ch.seg] + threadIdx.x; b < (int)blockIdx.x; b += AG_BLOCK) local += blk_cnt[b];
-        if (local) atomicAdd(&before, local);
-        doda_sync();
-    }
-    int run = before;
+    // rows kept in the earlier chunks of this segment: their counts
+    const size_t first = blockIdx.x - ch.index;
+    int run = compact_before(cp, use_valid, ch.index, [&](int b) { return blk_cnt[first + b]; });
     int mx[3] = {0, 0, 0};
-    for (int r = 0; r < AG_ROUNDS; ++r) {
-        const int i = ch.base + r * AG_BLOCK + threadIdx.x;
-        const bool keep = i < ch.end && (!use_valid || valid[i] != 0);
-        const unsigned long long mk = __ballot(keep);
-        if (lane_id() == 0) wcnt[threadIdx.x >> 6] = __popcll(mk);
-        doda_sync();
-        int off = run, total = 0;
-#pragma unroll
-        for (int w = 0; w < AG_WAVES; ++w) {
-            if (w < (int)(threadIdx.x >> 6)) off += wcnt[w];
-            total += wcnt[w];
-        }
-        const long long row = o.base[ch.seg] + off + mask_rank(mk);
-        if (keep && row >= 0 && row < out_len) {
+    for (int r = 0; r < SEG_ROUNDS; ++r) {
+        const int i = ch.base + r * SEG_BLOCK + threadIdx.x;
+        compact_round(cp, run, i < ch.end && (!use_valid || valid[i] != 0), [&](int rank) {
+            const long long row = o.base[ch.seg] + rank;
+            if (row < 0 || row >= out_len) return;
             double mid[3];
             if (feat_scale == 0.0) point_matmul(xyz, i, m, mid);
             out_locs[(size_t)row * 4] = batch0 + ch.seg;
@@ -333,9 +249,7 @@ __global__ __launch_bounds__(AG_BLOCK) void aug_emit(const float *__restrict__ x
             }
             out_labels[row] = labels[i];
             if (mask1) { out_mask1[row] = mask1[i]; out_mask2[row] = mask2[i]; }
-        }
-        run += total;
-        doda_sync();
+        });
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -365,10 +279,10 @@ extern "C" int doda_aug_affine(const float *xyz, const int64_t *offsets_h, int32
     const int nb = s.blk[n_seg];
     if (nb > 0) {
         if (!xyz || !pos || !part) return DODA_ERR_INVALID;
-        hipLaunchKernelGGL(aug_affine, dim3(nb), dim3(AG_BLOCK), 0, as_stream(stream), xyz, s, mat, scale, pos, part);
+        hipLaunchKernelGGL(aug_affine, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, s, mat, scale, pos, part);
     }
     AugGrids g = {};
-    hipLaunchKernelGGL(aug_bounds_final, dim3(n_seg), dim3(AG_BLOCK), 0, as_stream(stream), s, g, 0, (const double *)part, bounds);
+    hipLaunchKernelGGL(aug_bounds_final, dim3(n_seg), dim3(SEG_BLOCK), 0, as_stream(stream), s, g, 0, (const double *)part, bounds);
     return doda_check_launch();
 }
 
@@ -381,7 +295,7 @@ extern "C" int doda_aug_blur(float *noise, float *tmp, const int32_t *bb_h, int3
     if (!noise || !tmp) return DODA_ERR_INVALID;
     float *a = noise, *b = tmp;
     for (int pass = 0; pass < 6; ++pass) {
-        hipLaunchKernelGGL(aug_blur_pass, dim3(div_up(total, AG_BLOCK)), dim3(AG_BLOCK), 0, as_stream(stream), (const float *)a, b, g,
+        hipLaunchKernelGGL(aug_blur_pass, dim3(div_up(total, SEG_BLOCK)), dim3(SEG_BLOCK), 0, as_stream(stream), (const float *)a, b, g,
                            (int)n_seg, pass % 3);
         float *t = a; a = b; b = t;
     }
@@ -406,9 +320,9 @@ extern "C" int doda_aug_displace(double *pos, const int64_t *offsets_h, int32_t 
     if (g.base[n_seg] == 0) return DODA_OK;
     if (nb > 0) {
         if (!pos || !noise || !part) return DODA_ERR_INVALID;
-        hipLaunchKernelGGL(aug_displace, dim3(nb), dim3(AG_BLOCK), 0, as_stream(stream), pos, s, noise, g, part);
+        hipLaunchKernelGGL(aug_displace, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), pos, s, noise, g, part);
     }
-    hipLaunchKernelGGL(aug_bounds_final, dim3(n_seg), dim3(AG_BLOCK), 0, as_stream(stream), s, g, 1, (const double *)part, bounds);
+    hipLaunchKernelGGL(aug_bounds_final, dim3(n_seg), dim3(SEG_BLOCK), 0, as_stream(stream), s, g, 1, (const double *)part, bounds);
     return doda_check_launch();
 }
 
@@ -420,7 +334,7 @@ extern "C" int doda_aug_crop(const double *pos, const int64_t *offsets_h, int32_
     const int nb = s.blk[n_seg];
     if (nb == 0) return DODA_OK;
     if (!pos || !par || !valid || !count || !blk_cnt) return DODA_ERR_INVALID;
-    hipLaunchKernelGGL(aug_crop, dim3(nb), dim3(AG_BLOCK), 0, as_stream(stream), pos, s, par, valid, count, blk_cnt);
+    hipLaunchKernelGGL(aug_crop, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), pos, s, par, valid, count, blk_cnt);
     return doda_check_launch();
 }
 
@@ -446,7 +360,7 @@ extern "C" int doda_aug_emit(const float *xyz, const double *pos, const int32_t 
     const int nb = s.blk[n_seg];
     if (nb == 0) return DODA_OK;
     if (!xyz || !pos || !labels || !mat || !par || !out_locs || !out_float || !out_labels || !top) return DODA_ERR_INVALID;
-    hipLaunchKernelGGL(aug_emit, dim3(nb), dim3(AG_BLOCK), 0, as_stream(stream), xyz, pos, labels, mask1, mask2, s, o, mat, feat_scale,
+    hipLaunchKernelGGL(aug_emit, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, pos, labels, mask1, mask2, s, o, mat, feat_scale,
                        par, valid, blk_cnt, (int)batch0, out_locs, out_float, out_labels, out_mask1, out_mask2, top,
                        (long long)out_len);
     return doda_check_launch();

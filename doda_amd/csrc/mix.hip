@@ -3,116 +3,46 @@
 //
 // reference dataset/augmentor/augmentor_utils.py:255-445 cuts a target and a source scene into cuboids with numpy boolean masks (one
 // pass over every point per cuboid and step), moves / shrinks the kept cuboids in place and concatenates them.  Here a batch of
-// scenes is a batch of SEGMENTS of one array; a segment is cut into chunks of DODA_MIX_CHUNK points, one workgroup each, and the
-// segment offsets travel as launch arguments (validated on the host: no kernel trusts a device table for its bounds).
+// scenes is a batch of SEGMENTS of one array, cut into chunks of DODA_MIX_CHUNK points, one workgroup each (segments.hpp).
 //
-// Order and determinism: the outputs keep the points' order (the reference's boolean-mask order).  A kept point's row is
-//   rows kept in earlier chunks of its segment   (from blk_cnt, the per-(chunk, cuboid) counts the classify pass stored)
-// + rows kept earlier in its chunk                (wave ballot + popcount prefix, four rounds of 256 points),
-// so there is no scan launch and no atomic decides a position.  The statistics are integer sums (label counts, and coordinates as
-// round(x * 2^28) in int64): exact, so the order in which workgroups add them does not show in any bit.
-#include "common.hpp"
+// Order and determinism: the outputs keep the points' order (the reference's boolean-mask order) by segments.hpp's stable
+// compaction over blk_cnt, the per-(chunk, cuboid) counts the classify pass stored; mix_extract ranks per cuboid with the same
+// arithmetic and counters of its own.  The statistics are integer sums (label counts, and coordinates as round(x * 2^28) in
+// int64): exact, so the order in which workgroups add them does not show in any bit.
+#include "segments.hpp"
 #include "../../include/doda_mix.h"
 
+static_assert(DODA_MIX_CHUNK == SEG_CHUNK, "include/doda_mix.h promises the chunk size of segments.hpp");
+
 namespace {
-constexpr int MX_BLOCK = 256;
-constexpr int MX_WAVES = MX_BLOCK / DODA_WAVE;
-constexpr int MX_ROUNDS = DODA_MIX_CHUNK / MX_BLOCK;
 constexpr int MX_C1 = DODA_MIX_MAX_CUBOIDS + 1;          // + the row of points that no cuboid holds
 constexpr int MX_K1 = DODA_MIX_MAX_CLASSES + 1;          // + the bin of ignored labels
 constexpr double MX_FIX = (double)(1 << DODA_MIX_FIXED_BITS);
 
-struct MixSegs {                                         // launch argument: segment offsets and first chunk of every segment
-    int32_t n;
-    int32_t off[DODA_MIX_MAX_SEGMENTS + 1];
-    int32_t blk[DODA_MIX_MAX_SEGMENTS + 1];
-};
+using MixSegs = Segs<DODA_MIX_MAX_SEGMENTS>;
 
-// DODA_OK and *s filled, or the status to return
-int make_segs(const int64_t *offsets_h, int32_t n_seg, MixSegs *s) {
-    if (!offsets_h || n_seg < 1) return DODA_ERR_INVALID;
-    if (n_seg > DODA_MIX_MAX_SEGMENTS) return DODA_ERR_UNSUPPORTED;
-    if (offsets_h[0] != 0) return DODA_ERR_INVALID;
-    s->n = n_seg;
-    s->off[0] = 0;
-    s->blk[0] = 0;
-    for (int k = 0; k < n_seg; ++k) {
-        const int64_t a = offsets_h[k], b = offsets_h[k + 1];
-        if (b < a || b > 0x7fffffffLL) return DODA_ERR_INVALID;
-        s->off[k + 1] = (int32_t)b;
-        s->blk[k + 1] = s->blk[k] + (int32_t)((b - a + DODA_MIX_CHUNK - 1) / DODA_MIX_CHUNK);
-    }
-    return DODA_OK;
-}
-
-struct Chunk { int seg, base, end; };
-
-// the chunk of this workgroup (blockIdx.x < s.blk[s.n]: the grid is exactly the chunks)
-__device__ __forceinline__ Chunk chunk_of_block(const MixSegs &s) {
-    const int b = blockIdx.x;
-    int seg = 0;
-    for (int k = 0; k < s.n; ++k)
-        if (b >= s.blk[k + 1]) seg = k + 1;              // (empty segments have no chunk: skipped)
-    if (seg >= s.n) seg = s.n - 1;
-    Chunk c;
-    c.seg = seg;
-    c.base = s.off[seg] + (b - s.blk[seg]) * DODA_MIX_CHUNK;
-    const int end = c.base + DODA_MIX_CHUNK;
-    c.end = end < s.off[seg + 1] ? end : s.off[seg + 1];
-    return c;
-}
-
-// min / max of 3 + 3 floats over the workgroup -> lo / hi of thread 0
-__device__ __forceinline__ void block_minmax(float lo[3], float hi[3], float (*sh)[6]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], d, 64));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d, 64));
-        }
-    if (lane_id() == 0)
-        for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = lo[k]; sh[threadIdx.x >> 6][3 + k] = hi[k]; }
-    doda_sync();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < MX_WAVES; ++w)
-            for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], sh[w][k]); hi[k] = fmaxf(hi[k], sh[w][3 + k]); }
-}
-
-__global__ __launch_bounds__(MX_BLOCK) void mix_bounds_part(const float *__restrict__ xyz, int stride, MixSegs s,
-                                                           float *__restrict__ part) {
-    __shared__ float sh[MX_WAVES][6];
+__global__ __launch_bounds__(SEG_BLOCK) void mix_bounds_part(const float *__restrict__ xyz, int stride, MixSegs s,
+                                                            float *__restrict__ part) {
+    __shared__ float sh[SEG_WAVES][6];
     const Chunk ch = chunk_of_block(s);
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = ch.base + threadIdx.x; i < ch.end; i += MX_BLOCK)
+    for (int i = ch.base + threadIdx.x; i < ch.end; i += SEG_BLOCK)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float v = xyz[(size_t)i * stride + k];
             lo[k] = fminf(lo[k], v);
             hi[k] = fmaxf(hi[k], v);
         }
-    block_minmax(lo, hi, sh);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { part[(size_t)blockIdx.x * 6 + k] = lo[k]; part[(size_t)blockIdx.x * 6 + 3 + k] = hi[k]; }
+    block_minmax(lo, hi, sh, part + (size_t)blockIdx.x * 6);
 }
 
 // one workgroup per segment: its chunks' partial bounds -> bounds[seg]
-__global__ __launch_bounds__(MX_BLOCK) void mix_bounds_final(MixSegs s, const float *__restrict__ part, float *__restrict__ bounds) {
-    __shared__ float sh[MX_WAVES][6];
-    const int seg = blockIdx.x;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = s.blk[seg] + threadIdx.x; b < s.blk[seg + 1]; b += MX_BLOCK)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], part[(size_t)b * 6 + k]);
-            hi[k] = fmaxf(hi[k], part[(size_t)b * 6 + 3 + k]);
-        }
-    block_minmax(lo, hi, sh);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { bounds[seg * 6 + k] = lo[k]; bounds[seg * 6 + 3 + k] = hi[k]; }
+__global__ __launch_bounds__(SEG_BLOCK) void mix_bounds_final(MixSegs s, const float *__restrict__ part, float *__restrict__ bounds) {
+    __shared__ float sh[SEG_WAVES][6];
+    segment_minmax(s, (int)blockIdx.x, part, sh, bounds);
 }
 
-__global__ __launch_bounds__(MX_BLOCK) void mix_classify(const float *__restrict__ xyz, const int32_t *__restrict__ labels, MixSegs s,
+__global__ __launch_bounds__(SEG_BLOCK) void mix_classify(const float *__restrict__ xyz, const int32_t *__restrict__ labels, MixSegs s,
                                                         const float *__restrict__ centre, const double *__restrict__ planes, int n_cub,
                                                         int n_classes, uint8_t *__restrict__ cub, int64_t *__restrict__ stats,
                                                         int32_t *__restrict__ blk_cnt) {
@@ -122,13 +52,13 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_classify(const float *__restrict
     __shared__ float ctr[3];
     const Chunk ch = chunk_of_block(s);
     const int c1 = n_cub + 1, k1 = n_classes + 1;
-    for (int e = threadIdx.x; e < n_cub * 6; e += MX_BLOCK) pl[e / 6][e % 6] = planes[(size_t)ch.seg * n_cub * 6 + e];
-    for (int e = threadIdx.x; e < c1 * k1; e += MX_BLOCK) hist[e] = 0u;
-    for (int e = threadIdx.x; e < c1 * 3; e += MX_BLOCK) sums[e] = 0ull;
+    for (int e = threadIdx.x; e < n_cub * 6; e += SEG_BLOCK) pl[e / 6][e % 6] = planes[(size_t)ch.seg * n_cub * 6 + e];
+    for (int e = threadIdx.x; e < c1 * k1; e += SEG_BLOCK) hist[e] = 0u;
+    for (int e = threadIdx.x; e < c1 * 3; e += SEG_BLOCK) sums[e] = 0ull;
     if (threadIdx.x < 3) ctr[threadIdx.x] = centre[ch.seg * 3 + threadIdx.x];
     doda_sync();
-    for (int r = 0; r < MX_ROUNDS; ++r) {
-        const int i = ch.base + r * MX_BLOCK + threadIdx.x;
+    for (int r = 0; r < SEG_ROUNDS; ++r) {
+        const int i = ch.base + r * SEG_BLOCK + threadIdx.x;
         const bool valid = i < ch.end;
         int c = n_cub;
         long long fx[3] = {0, 0, 0};
@@ -170,11 +100,11 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_classify(const float *__restrict
     }
     doda_sync();
     int64_t *out = stats + (size_t)ch.seg * c1 * (3 + k1);
-    for (int e = threadIdx.x; e < c1 * k1; e += MX_BLOCK) {
+    for (int e = threadIdx.x; e < c1 * k1; e += SEG_BLOCK) {
         const unsigned v = hist[e];
         if (v) atomicAdd(reinterpret_cast<unsigned long long *>(out + (e / k1) * (3 + k1) + 3 + e % k1), (unsigned long long)v);
     }
-    for (int e = threadIdx.x; e < c1 * 3; e += MX_BLOCK) {
+    for (int e = threadIdx.x; e < c1 * 3; e += SEG_BLOCK) {
         const unsigned long long v = sums[e];
         if (v) atomicAdd(reinterpret_cast<unsigned long long *>(out + (e / 3) * (3 + k1) + e % 3), v);
     }
@@ -185,7 +115,7 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_classify(const float *__restrict
     }
 }
 
-__global__ __launch_bounds__(MX_BLOCK) void mix_emit(const float *__restrict__ xyz, int stride, const int32_t *__restrict__ labels,
+__global__ __launch_bounds__(SEG_BLOCK) void mix_emit(const float *__restrict__ xyz, int stride, const int32_t *__restrict__ labels,
                                                     const uint8_t *__restrict__ cub, const int32_t *__restrict__ blk_cnt, MixSegs s,
                                                     int n_cub, const float *__restrict__ centre, const double *__restrict__ tab,
                                                     const double *__restrict__ seg_tab, float *__restrict__ out_xyz,
@@ -194,43 +124,27 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_emit(const float *__restrict__ x
     __shared__ double t[MX_C1][7];
     __shared__ double st[5];
     __shared__ float ctr[3];
-    __shared__ int before;
-    __shared__ int wcnt[MX_WAVES];
+    __shared__ Compact cp;
     const Chunk ch = chunk_of_block(s);
     const int c1 = n_cub + 1;
-    for (int e = threadIdx.x; e < c1 * 7; e += MX_BLOCK) t[e / 7][e % 7] = tab[(size_t)ch.seg * c1 * 7 + e];
+    for (int e = threadIdx.x; e < c1 * 7; e += SEG_BLOCK) t[e / 7][e % 7] = tab[(size_t)ch.seg * c1 * 7 + e];
     if (threadIdx.x < 5) st[threadIdx.x] = seg_tab[ch.seg * 5 + threadIdx.x];
     if (threadIdx.x < 3) ctr[threadIdx.x] = centre ? centre[ch.seg * 3 + threadIdx.x] : 0.f;
-    if (threadIdx.x == 0) before = cub ? 0 : (blockIdx.x - s.blk[ch.seg]) * DODA_MIX_CHUNK;
+    compact_init(cp, ch, cub != nullptr);
     doda_sync();
-    if (cub) {                                               // rows kept in the earlier chunks of this segment
-        const int first = s.blk[ch.seg], pairs = (blockIdx.x - first) * c1;
-        int local = 0;
-        for (int p = threadIdx.x; p < pairs; p += MX_BLOCK)
-            if (t[p % c1][0] != 0.0) local += blk_cnt[(size_t)first * c1 + p];
-        if (local) atomicAdd(&before, local);
-        doda_sync();
-    }
-    int run = before;
+    // rows kept in the earlier chunks of this segment: their (chunk, cuboid) counts of the kept cuboids
+    const size_t first = (size_t)(blockIdx.x - ch.index) * c1;
+    int run = compact_before(cp, cub != nullptr, ch.index * c1, [&](int p) { return t[p % c1][0] != 0.0 ? blk_cnt[first + p] : 0; });
     const long long out_base = (long long)st[3];
     const uint8_t m1 = st[4] != 0.0 ? 1 : 0;
-    for (int r = 0; r < MX_ROUNDS; ++r) {
-        const int i = ch.base + r * MX_BLOCK + threadIdx.x;
+    for (int r = 0; r < SEG_ROUNDS; ++r) {
+        const int i = ch.base + r * SEG_BLOCK + threadIdx.x;
         const bool valid = i < ch.end;
         int c = 0;
         if (valid && cub) { c = cub[i]; if (c > n_cub) c = n_cub; }
-        const bool keep = valid && t[c][0] != 0.0;
-        const unsigned long long m = __ballot(keep);
-        if (lane_id() == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-        doda_sync();
-        int off = run, total = 0;
-#pragma unroll
-        for (int w = 0; w < MX_WAVES; ++w) {
-            if (w < (int)(threadIdx.x >> 6)) off += wcnt[w];
-            total += wcnt[w];
-        }
-        const long long o = out_base + off + mask_rank(m);
-        if (keep && o >= 0 && o < out_len) {
+        compact_round(cp, run, valid && t[c][0] != 0.0, [&](int row) {
+            const long long o = out_base + row;
+            if (o < 0 || o >= out_len) return;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 float x = xyz[(size_t)i * stride + k];
@@ -243,37 +157,35 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_emit(const float *__restrict__ x
             out_labels[o] = labels ? labels[i] : (int32_t)xyz[(size_t)i * stride + 3];
             mask1[o] = m1;
             mask2[o] = (uint8_t)(1 - m1);
-        }
-        run += total;
-        doda_sync();
+        });
     }
 }
 
-__global__ __launch_bounds__(MX_BLOCK) void mix_extract(const float *__restrict__ xyz, const int32_t *__restrict__ labels,
+__global__ __launch_bounds__(SEG_BLOCK) void mix_extract(const float *__restrict__ xyz, const int32_t *__restrict__ labels,
                                                        const uint8_t *__restrict__ cub, const int32_t *__restrict__ blk_cnt, MixSegs s,
                                                        int n_cub, const float *__restrict__ centre, const int64_t *__restrict__ ex_base,
                                                        float *__restrict__ out_rows, long long out_len) {
     __shared__ long long base[MX_C1];
     __shared__ int run[MX_C1];
-    __shared__ int wcnt[MX_WAVES][MX_C1];
+    __shared__ int wcnt[SEG_WAVES][MX_C1];
     __shared__ float ctr[3];
     const Chunk ch = chunk_of_block(s);
     const int c1 = n_cub + 1;
     if (threadIdx.x < c1) { base[threadIdx.x] = ex_base[(size_t)ch.seg * c1 + threadIdx.x]; run[threadIdx.x] = 0; }
-    for (int e = threadIdx.x; e < MX_WAVES * MX_C1; e += MX_BLOCK) wcnt[e / MX_C1][e % MX_C1] = 0;
+    for (int e = threadIdx.x; e < SEG_WAVES * MX_C1; e += SEG_BLOCK) wcnt[e / MX_C1][e % MX_C1] = 0;
     if (threadIdx.x < 3) ctr[threadIdx.x] = centre[ch.seg * 3 + threadIdx.x];
     doda_sync();
     {
         const int first = s.blk[ch.seg], pairs = (blockIdx.x - first) * c1;
-        for (int p = threadIdx.x; p < pairs; p += MX_BLOCK) {
+        for (int p = threadIdx.x; p < pairs; p += SEG_BLOCK) {
             const int c = p % c1;
             if (base[c] >= 0) { const int v = blk_cnt[(size_t)first * c1 + p]; if (v) atomicAdd(&run[c], v); }
         }
         doda_sync();
     }
     const int w = threadIdx.x >> 6;
-    for (int r = 0; r < MX_ROUNDS; ++r) {
-        const int i = ch.base + r * MX_BLOCK + threadIdx.x;
+    for (int r = 0; r < SEG_ROUNDS; ++r) {
+        const int i = ch.base + r * SEG_BLOCK + threadIdx.x;
         const bool valid = i < ch.end;
         const int c = valid ? (int)cub[i] : 255;
         const bool want = valid && c < n_cub && base[c] >= 0;
@@ -302,7 +214,7 @@ __global__ __launch_bounds__(MX_BLOCK) void mix_extract(const float *__restrict_
         doda_sync();
         if (threadIdx.x < c1) {
             int tsum = 0;
-            for (int v = 0; v < MX_WAVES; ++v) { tsum += wcnt[v][threadIdx.x]; wcnt[v][threadIdx.x] = 0; }
+            for (int v = 0; v < SEG_WAVES; ++v) { tsum += wcnt[v][threadIdx.x]; wcnt[v][threadIdx.x] = 0; }
             run[threadIdx.x] += tsum;
         }
         doda_sync();
@@ -328,9 +240,9 @@ extern "C" int doda_mix_bounds(const float *xyz, int32_t stride, const int64_t *
     const int nb = s.blk[n_seg];
     if (nb > 0) {
         if (!xyz || !part) return DODA_ERR_INVALID;
-        hipLaunchKernelGGL(mix_bounds_part, dim3(nb), dim3(MX_BLOCK), 0, as_stream(stream), xyz, (int)stride, s, part);
+        hipLaunchKernelGGL(mix_bounds_part, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, (int)stride, s, part);
     }
-    hipLaunchKernelGGL(mix_bounds_final, dim3(n_seg), dim3(MX_BLOCK), 0, as_stream(stream), s, (const float *)part, bounds);
+    hipLaunchKernelGGL(mix_bounds_final, dim3(n_seg), dim3(SEG_BLOCK), 0, as_stream(stream), s, (const float *)part, bounds);
     return doda_check_launch();
 }
 
@@ -344,7 +256,7 @@ extern "C" int doda_mix_classify(const float *xyz, const int32_t *labels, const 
     const int nb = s.blk[n_seg];
     if (nb == 0) return DODA_OK;
     if (!xyz || !labels || !centre || !planes || !cub || !stats || !blk_cnt) return DODA_ERR_INVALID;
-    hipLaunchKernelGGL(mix_classify, dim3(nb), dim3(MX_BLOCK), 0, as_stream(stream), xyz, labels, s, centre, planes, (int)n_cub,
+    hipLaunchKernelGGL(mix_classify, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, labels, s, centre, planes, (int)n_cub,
                        (int)n_classes, cub, stats, blk_cnt);
     return doda_check_launch();
 }
@@ -364,7 +276,7 @@ extern "C" int doda_mix_emit(const float *xyz, int32_t stride, const int32_t *la
     const int nb = s.blk[n_seg];
     if (nb == 0) return DODA_OK;
     if (!xyz || !tab || !seg_tab || !out_xyz || !out_labels || !mask1 || !mask2) return DODA_ERR_INVALID;
-    hipLaunchKernelGGL(mix_emit, dim3(nb), dim3(MX_BLOCK), 0, as_stream(stream), xyz, (int)stride, labels, cub, blk_cnt, s, (int)n_cub,
+    hipLaunchKernelGGL(mix_emit, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, (int)stride, labels, cub, blk_cnt, s, (int)n_cub,
                        centre, tab, seg_tab, out_xyz, out_labels, mask1, mask2, (long long)out_len);
     return doda_check_launch();
 }
@@ -380,7 +292,7 @@ extern "C" int doda_mix_extract(const float *xyz, const int32_t *labels, const u
     const int nb = s.blk[n_seg];
     if (nb == 0) return DODA_OK;
     if (!xyz || !labels || !cub || !blk_cnt || !centre || !ex_base || !out_rows) return DODA_ERR_INVALID;
-    hipLaunchKernelGGL(mix_extract, dim3(nb), dim3(MX_BLOCK), 0, as_stream(stream), xyz, labels, cub, blk_cnt, s, (int)n_cub, centre,
+    hipLaunchKernelGGL(mix_extract, dim3(nb), dim3(SEG_BLOCK), 0, as_stream(stream), xyz, labels, cub, blk_cnt, s, (int)n_cub, centre,
                        ex_base, out_rows, (long long)out_len);
     return doda_check_launch();
 }

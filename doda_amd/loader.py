@@ -371,28 +371,31 @@ class DeviceScenes:
     def _augmented(self, ids):
         """The scenes of a batch under DATA_AUG.aug_list (doda_amd.aug.augment_batch instead of _rigid's transform and _finish)."""
         from . import aug
-        base = [(i % self.length) % len(self.xyz) for i in ids]
-        offsets = [0]
-        for k in base:
-            offsets.append(offsets[-1] + self.xyz[k].shape[0])
-        x = torch.cat([self.xyz[k] for k in base], 0)
-        labels = torch.cat([self.lab[k] for k in base], 0)
+        x, labels, offsets = self._concat(ids)
         draws = [aug.SeededDraws((self.seed * 1000003 + 13 * i + 7) & 0x7fffffff) for i in ids]
         out = aug.augment_batch(x, labels, offsets, self.aug_cfg, draws)
         out["id"] = [int(i) for i in ids]
         return out
 
+    def _concat(self, ids):
+        """The base scenes of the items `ids` concatenated: (xyz_mid [N, 3] float32, labels, offsets)."""
+        base = [(i % self.length) % len(self.xyz) for i in ids]
+        offsets = [0]
+        for k in base:
+            offsets.append(offsets[-1] + self.xyz[k].shape[0])
+        return torch.cat([self.xyz[k] for k in base], 0), torch.cat([self.lab[k] for k in base], 0), offsets
+
+    def _batch_index(self, offsets):
+        """[N]: the sample b of every point of a batch with these offsets."""
+        sizes = [offsets[b + 1] - offsets[b] for b in range(len(offsets) - 1)]
+        return torch.repeat_interleave(torch.arange(len(sizes), device=self.device), torch.tensor(sizes, device=self.device),
+                                       output_size=offsets[-1])
+
     def _rigid(self, ids):
         """The scenes of a batch concatenated, under their rigid augmentation: (xyz_mid [N, 3], labels, offsets, batch index)."""
         dev, bs = self.device, len(ids)
-        base = [(i % self.length) % len(self.xyz) for i in ids]
-        sizes = [self.xyz[k].shape[0] for k in base]
-        offsets = [0]
-        for n in sizes:
-            offsets.append(offsets[-1] + n)
-        x = torch.cat([self.xyz[k] for k in base], 0)                       # [N, 3] float32
-        labels = torch.cat([self.lab[k] for k in base], 0)
-        bidx = torch.repeat_interleave(torch.arange(bs, device=dev), torch.tensor(sizes, device=dev), output_size=offsets[-1])
+        x, labels, offsets = self._concat(ids)
+        bidx = self._batch_index(offsets)
         if self.augment:
             # per-scene rigid transform from host-side seeded draws (tiny), jitter from the device generator
             rng = np.random.default_rng((self.seed * 1000003 + ids[0]) & 0x7fffffff)
@@ -465,10 +468,7 @@ class MixedDeviceScenes(DeviceScenes):
             for k in ("tar_tail_splits", "tar_splits_class_ratio"):
                 out[k] = mixed[k]
             return out
-        sizes = [offsets[b + 1] - offsets[b] for b in range(len(ids))]
-        bidx = torch.repeat_interleave(torch.arange(len(ids), device=self.device), torch.tensor(sizes, device=self.device),
-                                       output_size=offsets[-1])
-        out = self._finish(mixed["xyz_mid"], mixed["labels"], offsets, bidx, ids)
+        out = self._finish(mixed["xyz_mid"], mixed["labels"], offsets, self._batch_index(offsets), ids)
         for k in ("mask1", "mask2", "tar_tail_splits", "tar_splits_class_ratio"):
             out[k] = mixed[k]
         return out

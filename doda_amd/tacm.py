@@ -13,14 +13,14 @@ workers; here the scenes stay on the device:
 Two deliberate deviations: queue cuboids are immutable (the reference moves and shrinks a stored cuboid in place every
 time it is drawn, so it shrinks by 10 % per use; here the transform is applied in the emit kernel: the first use is identical), and
 every rank keeps its own queue (the reference all-gathers pickled cuboids)."""
-import ctypes as C
 import threading
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, segments
 from ._lib import check, lib
+from .segments import SeededDraws, launch_on, offsets_h, per_sample, stream_handle   # noqa: F401  (SeededDraws: for the callers)
 
 FIX = float(1 << _lib.MIX_FIXED_BITS)
 MAX_EXTENT = 2048.0          # metres: |centred coordinate| * 2^28 * points of a cuboid stays inside int64
@@ -70,25 +70,6 @@ class TacmConfig:
 
 
 # ------------------------------------------------------------------------------------------------ randomness
-class SeededDraws:
-    """The production `draws` object: every random number of a sample from one seeded numpy generator."""
-
-    def __init__(self, seed):
-        self.g = np.random.default_rng(seed)
-
-    def rand(self, n=None):
-        return self.g.random() if n is None else self.g.random(n)
-
-    def permutation(self, n):
-        return self.g.permutation(n)
-
-    def choice(self, n, k, p):
-        return self.g.choice(n, k, p=np.asarray(p, dtype=np.float64) / np.sum(p))
-
-    def sample(self, k, n):
-        return [int(v) for v in self.g.choice(n, k, replace=False)]
-
-
 class ReplayDraws:
     """Replays a recorded draw sequence [(kind, value), ...] and checks that the draws are asked for in the recorded order."""
 
@@ -425,24 +406,8 @@ def plan(bounds, stats, cfg, sampler, draws):
 
 
 # ------------------------------------------------------------------------------------------------ device calls
-def _offsets_h(offsets):
-    arr = (C.c_int64 * len(offsets))(*[int(v) for v in offsets])
-    return arr, len(offsets) - 1
-
-
-def _stream(stream):
-    if stream is not None:
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-    from .ops import _stream as cur
-    return cur()
-
-
 def n_blocks(offsets):
-    arr, n_seg = _offsets_h(offsets)
-    nb = lib().doda_mix_blocks(arr, n_seg)
-    if nb < 0:
-        raise _lib.DodaNativeError("doda_mix_blocks: invalid segment offsets")
-    return int(nb)
+    return segments.n_blocks(lib(), "doda_mix_blocks", offsets)
 
 
 def segment_bounds(xyz, offsets, stream=None):
@@ -454,10 +419,10 @@ def segment_bounds(xyz, offsets, stream=None):
     for s0 in range(0, n_seg, _lib.MIX_MAX_SEGMENTS):
         s1 = min(n_seg, s0 + _lib.MIX_MAX_SEGMENTS)
         sub = [int(v) - int(offsets[s0]) for v in offsets[s0:s1 + 1]]
-        arr, ns = _offsets_h(sub)
+        arr, ns = offsets_h(sub)
         part = torch.empty((max(1, n_blocks(sub)), 6), dtype=torch.float32, device=xyz.device)
         check(lib().doda_mix_bounds(xyz[int(offsets[s0]):].data_ptr(), xyz.shape[1], arr, ns, part.data_ptr(), out[s0:].data_ptr(),
-                                    _stream(stream)), "doda_mix_bounds")
+                                    stream_handle(stream)), "doda_mix_bounds")
     return out
 
 
@@ -472,14 +437,14 @@ def classify(xyz, labels, offsets, centre, planes, n_classes, stream=None):
     cub = torch.empty(xyz.shape[0], dtype=torch.uint8, device=dev)
     stats = torch.zeros((n_seg, n_cub + 1, 3 + n_classes + 1), dtype=torch.int64, device=dev)
     blk_cnt = torch.empty((max(1, n_blocks(offsets)), n_cub + 1), dtype=torch.int32, device=dev)
-    arr, ns = _offsets_h(offsets)
+    arr, ns = offsets_h(offsets)
     check(lib().doda_mix_classify(xyz.data_ptr(), labels.data_ptr(), arr, ns, centre.data_ptr(), planes.data_ptr(), n_cub, n_classes,
-                                  cub.data_ptr(), stats.data_ptr(), blk_cnt.data_ptr(), _stream(stream)), "doda_mix_classify")
+                                  cub.data_ptr(), stats.data_ptr(), blk_cnt.data_ptr(), stream_handle(stream)), "doda_mix_classify")
     return cub, stats, blk_cnt
 
 
 def _emit(xyz, labels, cub, blk_cnt, offsets, n_cub, centre, tab, seg_tab, out, stream):
-    arr, ns = _offsets_h(offsets)
+    arr, ns = offsets_h(offsets)
     dev = xyz.device
     tab_d = torch.from_numpy(np.ascontiguousarray(tab, dtype=np.float64)).to(dev)
     seg_d = torch.from_numpy(np.ascontiguousarray(seg_tab, dtype=np.float64)).to(dev)
@@ -487,17 +452,17 @@ def _emit(xyz, labels, cub, blk_cnt, offsets, n_cub, centre, tab, seg_tab, out, 
                               cub.data_ptr() if cub is not None else None, blk_cnt.data_ptr() if blk_cnt is not None else None,
                               arr, ns, n_cub, centre.data_ptr() if centre is not None else None, tab_d.data_ptr(), seg_d.data_ptr(),
                               out["xyz_mid"].data_ptr(), out["labels"].data_ptr(), out["mask1"].data_ptr(), out["mask2"].data_ptr(),
-                              out["xyz_mid"].shape[0], _stream(stream)), "doda_mix_emit")
+                              out["xyz_mid"].shape[0], stream_handle(stream)), "doda_mix_emit")
 
 
 def extract(xyz, labels, cub, blk_cnt, offsets, n_cub, centre, ex_base, n_rows, stream=None):
     """fp32 [n_rows, 4]: the centred points (x, y, z, label) of the wanted cuboids, cuboid (s, c) from row ex_base[s][c]
     (doda_mix_extract).  ex_base: int64 numpy [n_seg, n_cub + 1], negative = not wanted."""
-    arr, ns = _offsets_h(offsets)
+    arr, ns = offsets_h(offsets)
     rows = torch.empty((n_rows, 4), dtype=torch.float32, device=xyz.device)
     ex_d = torch.from_numpy(np.ascontiguousarray(ex_base, dtype=np.int64)).to(xyz.device)
     check(lib().doda_mix_extract(xyz.data_ptr(), labels.data_ptr(), cub.data_ptr(), blk_cnt.data_ptr(), arr, ns, n_cub,
-                                 centre.data_ptr(), ex_d.data_ptr(), rows.data_ptr(), n_rows, _stream(stream)), "doda_mix_extract")
+                                 centre.data_ptr(), ex_d.data_ptr(), rows.data_ptr(), n_rows, stream_handle(stream)), "doda_mix_extract")
     return rows
 
 
@@ -521,14 +486,8 @@ def mix_batch(target_xyz, target_labels, target_offsets, source_xyz, source_labe
     B = len(target_offsets) - 1
     if len(source_offsets) - 1 != B:
         raise ValueError("mix_batch: one source scene per target scene")
-    if not isinstance(draws, (list, tuple)):
-        draws = [draws]
-    if len(draws) != B:
-        raise ValueError("mix_batch: one draws object per sample")
-    ctx = torch.cuda.stream(stream) if (stream is not None and hasattr(stream, "cuda_stream")) else None
-    if ctx is not None:
-        ctx.__enter__()
-    try:
+    draws = per_sample(draws, B, "mix_batch")
+    with launch_on(stream):
         total, K = cfg.total_splits, cfg.n_classes
         nt = int(target_offsets[-1])
         xyz = torch.cat((target_xyz, source_xyz), 0).contiguous()
@@ -594,6 +553,3 @@ def mix_batch(target_xyz, target_labels, target_offsets, source_xyz, source_labe
         if return_debug:
             out["debug"] = {"cub": cub, "stats": stats, "bounds": bounds, "plans": plans, "planes": planes, "centre": centre}
         return out
-    finally:
-        if ctx is not None:
-            ctx.__exit__(None, None, None)

@@ -1,5 +1,5 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h).
+include/doda_aug.h, include/doda_loss.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -148,6 +148,19 @@ AUG_SIGNATURES = {
 AUG_SYMBOLS = tuple(AUG_SIGNATURES)
 AUG_ABI_VERSION = 1  # include/doda_aug.h DODA_AUG_ABI_VERSION
 AUG_MAX_SEGMENTS, AUG_CHUNK, AUG_MAX_GRID_CELLS = 64, 1024, 1 << 24
+
+# name -> (restype, argtypes); mirrors include/doda_loss.h (the Lovasz-softmax companion ABI, same library)
+LOSS_SIGNATURES = {
+    "doda_loss_abi_version": (c_i32, []),
+    "doda_lovasz_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "doda_lovasz_blocks": (c_i32, [c_i32]),
+    "doda_lovasz_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                c_vp]),
+    "doda_lovasz_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+}
+LOSS_SYMBOLS = tuple(LOSS_SIGNATURES)
+LOSS_ABI_VERSION = 1  # include/doda_loss.h DODA_LOSS_ABI_VERSION
+LOVASZ_MAX_CLASSES, LOVASZ_MAX_POINTS_PER_VOXEL = 32, 65535
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -156,7 +169,8 @@ ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
 _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (SELFTRAIN_SIGNATURES, "doda_st_abi_version", ST_ABI_VERSION, "self-training ABI"),
          (MIX_SIGNATURES, "doda_mix_abi_version", MIX_ABI_VERSION, "cuboid-mixing ABI"),
-         (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"))
+         (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"),
+         (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"))
 
 _lib = None
 

@@ -641,9 +641,36 @@ def cross_entropy(scores, labels, ignore_index=255):
     return -(picked * valid).sum() / valid.sum().clamp(min=1)
 
 
+LOSS_KINDS = ("cross_entropy", "lovasz")
+
+
+def loss_kind_of(cfg):
+    """OPTIMIZATION.loss of an experiment config (reference model/unet.py:107-113): cross_entropy (also when the key or the whole
+    section is absent, as in default_cfg) or lovasz; anything else is NotImplementedError, as in the reference."""
+    opt = getattr(cfg, "OPTIMIZATION", None)
+    kind = "cross_entropy" if opt is None else (opt.get("loss", "cross_entropy") if hasattr(opt, "get")
+                                                else getattr(opt, "loss", "cross_entropy"))
+    if kind not in LOSS_KINDS:
+        raise NotImplementedError("OPTIMIZATION.loss: %r (cross_entropy | lovasz)" % (kind,))
+    return kind
+
+
+def criterion_of(model):
+    """The point-level criterion(scores, labels, ignore_index) of a (possibly wrapped) network; cross_entropy for one without a choice."""
+    net = model.module if hasattr(model, "module") else model
+    return getattr(net, "criterion", cross_entropy)
+
+
 class SparseConvNet(nn.Module):
     def __init__(self, cfg):
         super().__init__()
+        # the configured loss: the point-level criterion of the matrix path and the voxel-level autograd function of head_loss
+        self.loss_kind = loss_kind_of(cfg)
+        if self.loss_kind == "lovasz":
+            from .lovasz import _VoxelHeadLovasz, lovasz_softmax
+            self.criterion, self.voxel_head = lovasz_softmax, _VoxelHeadLovasz
+        else:
+            self.criterion, self.voxel_head = cross_entropy, _VoxelHeadCE
         bb = cfg.MODEL.BACKBONE
         try:
             n_classes = cfg.COMMON_CLASSES.n_classes
@@ -662,8 +689,9 @@ class SparseConvNet(nn.Module):
                 mod.bias.data.fill_(0.0)
 
     def head_loss(self, feats, v2p_map, labels, ignore_index=255):
-        """Linear head + CrossEntropyLoss on the voxel features without the point-level score matrix (_VoxelHeadCE), or None
-        when that form does not apply (then: scores = forward(...), cross_entropy(scores, labels)).  Sets self.voxel_pred."""
+        """Linear head + the configured loss on the voxel features without the point-level score matrix (_VoxelHeadCE, or
+        lovasz._VoxelHeadLovasz under OPTIMIZATION.loss: lovasz), or None when that form does not apply (then: scores =
+        forward(...), self.criterion(scores, labels)).  Sets self.voxel_pred."""
         if not (FUSED_HEAD_LOSS and feats.is_cuda and feats.dim() == 2 and feats.shape[1] == 16 and feats.shape[0] > 0
                 and feats.dtype in (torch.float32, torch.bfloat16) and self.linear.out_features <= 32
                 and self.linear.weight.dtype == torch.float32 and v2p_map is not None and v2p_map.is_cuda
@@ -671,7 +699,10 @@ class SparseConvNet(nn.Module):
                 and labels.is_cuda and labels.dtype == torch.int64
                 and not (self.linear._forward_hooks or self.linear._forward_pre_hooks or self.linear._backward_hooks)):
             return None
-        loss, pred = _VoxelHeadCE.apply(feats, self.linear.weight, self.linear.bias, v2p_map, labels, int(ignore_index))
+        if self.loss_kind == "lovasz" and not (self.linear.out_features >= 2 and v2p_map.shape[1] - 1 <= _ops.LOVASZ_MAX_POINTS_PER_VOXEL
+                                                and 2 * feats.shape[0] * self.linear.out_features < 2 ** 31):
+            return None
+        loss, pred = self.voxel_head.apply(feats, self.linear.weight, self.linear.bias, v2p_map, labels, int(ignore_index))
         self.voxel_pred = pred
         return loss
 
@@ -711,14 +742,14 @@ class SparseConvNet(nn.Module):
             if labels is not None:
                 self.voxel_pred = None
                 self.point_scores = scores.detach()   # (for point_predictions: no reference to the score matrix's graph)
-                return cross_entropy(scores, labels, ignore_index)
+                return self.criterion(scores, labels, ignore_index)
             return scores
         point_feats = feats[input_map.long()]  # voxel -> point
         scores = self.linear(point_feats.to(self.linear.weight.dtype))
         if labels is not None and not return_mid_feat:
             self.voxel_pred = None
             self.point_scores = scores.detach()
-            return cross_entropy(scores, labels, ignore_index)
+            return self.criterion(scores, labels, ignore_index)
         return (point_feats, scores) if return_mid_feat else scores
 
 
@@ -937,7 +968,7 @@ def voxelize_and_run(cfg, model, batch, device, feature_dtype=torch.float32, fus
         net = model.module if hasattr(model, "module") else model
         net.voxel_pred = None                 # (point_predictions: this batch's scores, not an earlier call's voxel argmax)
         net.point_scores = scores.detach()
-        return cross_entropy(scores, labels, ignore_index)
+        return criterion_of(model)(scores, labels, ignore_index)
     return model(inp, p2v)
 
 

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import DodaNativeError, check, lib  # noqa: F401
+from ._lib import LOVASZ_MAX_POINTS_PER_VOXEL, DodaNativeError, check, lib  # noqa: F401
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -906,6 +906,49 @@ def head_dw(feats, dz):
         return part.sum(0)[:n_cls]
     ident = torch.arange(m, dtype=torch.int32, device=feats.device).view(1, m)
     return spconv_wgrad(feats.contiguous(), dz, ident, m)[0].t()
+
+
+# ---- Lovasz-softmax head at voxel level (include/doda_loss.h, csrc/lovasz.hip) -------------------------------------
+def lovasz_fwd(feats, weight, bias, v2p, labels, ignore_index, want_grad=True):
+    """Linear head + Lovasz-softmax (classes present) over the voxel -> point lists without the [points, classes] matrix
+    (doda_lovasz_fwd).  -> (out float32 [2] = {loss, present classes}, pred int32 [m], gitem float32 [m, n_cls, 2] or None: the
+    per-item Lovasz gradients doda_lovasz_bwd reads)."""
+    _feat_ok(feats, "feats")
+    for t in (weight, v2p, labels):
+        _need_cuda(t)
+    if weight.dtype != torch.float32 or v2p.dtype != torch.int32 or labels.dtype != torch.int64 or v2p.dim() != 2:
+        raise RuntimeError("lovasz: weight float32 [n_cls, c], v2p int32 [m, 1 + max_active], labels int64 [points]")
+    feats, weight, v2p, labels = feats.contiguous(), weight.contiguous(), v2p.contiguous(), labels.contiguous()
+    m, c = feats.shape
+    n_cls = weight.shape[0]
+    out = torch.empty(2, dtype=torch.float32, device=feats.device)
+    pred = torch.empty(m, dtype=torch.int32, device=feats.device)
+    gitem = torch.empty((m, n_cls, 2), dtype=torch.float32, device=feats.device) if want_grad else None
+    nbytes = int(lib().doda_lovasz_workspace_bytes(m, n_cls))
+    if nbytes == 0:
+        raise DodaNativeError("doda_lovasz_fwd: %d voxels x %d classes is outside the compiled range" % (m, n_cls))
+    ws = _ws(nbytes, feats.device)
+    check(lib().doda_lovasz_fwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
+                                n_cls, _p(v2p), v2p.shape[1], _p(labels), int(ignore_index), _p(out), _p(pred), _p(gitem), _p(ws),
+                                ws.numel(), _stream()), "doda_lovasz_fwd")
+    return out, pred, gitem
+
+
+def lovasz_bwd(feats, weight, bias, gitem, out, grad):
+    """-> (d_feats [m, c], dz [m, n_cls] — both in the features' dtype —, dz_lo [m, n_cls] bf16 = what rounding dz to bf16 dropped
+    (None for fp32 features), d_bias float32 [n_cls])."""
+    feats, weight = feats.contiguous(), weight.contiguous()
+    m, c = feats.shape
+    n_cls = weight.shape[0]
+    nb = int(lib().doda_lovasz_blocks(m))
+    d_feats = torch.empty_like(feats)
+    dz = torch.empty((m, n_cls), dtype=feats.dtype, device=feats.device)
+    dz_lo = torch.empty_like(dz) if feats.dtype == torch.bfloat16 else None
+    dbp = torch.empty((nb, n_cls), dtype=torch.float32, device=feats.device)
+    check(lib().doda_lovasz_bwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
+                                n_cls, _p(gitem), _p(out), _p(grad.contiguous()), _p(d_feats), _p(dz), _p(dz_lo), _p(dbp), nb,
+                                _stream()), "doda_lovasz_bwd")
+    return d_feats, dz, dz_lo, dbp.sum(0)
 
 
 # ---- self-training pseudo labels (include/doda_selftrain.h) --------------------------------------------

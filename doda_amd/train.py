@@ -543,8 +543,9 @@ class Trainer:
     @torch.no_grad()
     def validate_epoch(self, epoch):
         from .dsnorm import set_ds_target
-        from .model import cross_entropy, voxelize_and_run
+        from .model import criterion_of, voxelize_and_run
         cfg = self.cfg
+        criterion = criterion_of(self.model)      # OPTIMIZATION.loss: cross_entropy (default) | lovasz
         self.model.eval()
         if self.reducer is not None:
             self.reducer.sync_buffers()   # evaluation with rank 0's running statistics on every rank
@@ -554,7 +555,7 @@ class Trainer:
         for batch, pyramid in self._batches(epoch, "val"):
             scores = voxelize_and_run(cfg, self.model, batch, self.device, feature_dtype=self.fdt,
                                       inputs_ready=True, pyramid=pyramid)
-            loss = cross_entropy(scores, batch["labels"], ignore_index=cfg.DATA_CONFIG.DATA_CLASS.ignore_label)
+            loss = criterion(scores, batch["labels"], ignore_index=cfg.DATA_CONFIG.DATA_CLASS.ignore_label)
             meters.update(loss, scores.argmax(1), batch["labels"])
         meters.all_reduce()
         l, miou, macc, allacc, iou = meters.read()

@@ -111,10 +111,8 @@ __global__ __launch_bounds__(1024) void head_ce_final(const float *__restrict__ 
 }
 
 // backward: d_feats [m, C], dz [m, n_cls] (storage type of the features), db partial rows [blocks][n_cls].
-// The per-class values of a thread's voxel (exp(z - max), then dz) and its running column sums live in LDS COLUMNS
-// (sz[k][thread], sdb[k][thread]: conflict-free) instead of register arrays: the class loops stay rolled, a point's label indexes
-// its class directly (dz[label] -= scale), and the kernel needs ~50 VGPRs — the register form (three 20-element arrays per thread,
-// loops fully unrolled) compiled to 256 VGPRs + spills and ran at 120 us.
+// The per-class values of a thread's voxel (exp(z - max), then dz) live in its LDS column (head_common.hpp): a point's label indexes
+// its class directly (dz[label] -= scale).
 template <int ESZ, int C, int NK>
 __global__ __launch_bounds__(HD_BLOCK) void head_ce_bwd(const void *__restrict__ feats, int m, const float *__restrict__ weight,
                                                         const float *__restrict__ bias, int n_cls, const int32_t *__restrict__ v2p,
@@ -129,19 +127,13 @@ __global__ __launch_bounds__(HD_BLOCK) void head_ce_bwd(const void *__restrict__
     const int tid = threadIdx.x;
     const long long v = (long long)blockIdx.x * HD_BLOCK + tid;
 #pragma unroll 1
-    for (int k = 0; k < NK; ++k) sz[k][tid] = 0.f;      // (a thread past the last voxel contributes zeros to the column sums)
+    for (int k = 0; k < NK; ++k) sz[k][tid] = 0.f;      // (a thread past the last voxel contributes zeros to hd_db_colsums)
     if (v < m) {
         float f[C];
         hd_load_row<ESZ, C>(feats, v, f);
         const int32_t *row = v2p + v * v2p_ld;
         const int np = row[0];
-        float mx = -INFINITY;
-#pragma unroll 2
-        for (int k = 0; k < n_cls; ++k) {
-            const float z = hd_logit<C>(w, b, k, f);
-            sz[k][tid] = z;
-            mx = fmaxf(mx, z);
-        }
+        const float mx = hd_logits_lds<C>(w, b, n_cls, f, sz, tid);
         float s = 0.f;
 #pragma unroll 2
         for (int k = 0; k < n_cls; ++k) {
@@ -185,33 +177,9 @@ __global__ __launch_bounds__(HD_BLOCK) void head_ce_bwd(const void *__restrict__
                     *reinterpret_cast<f32x2 *>(dzr + (size_t)k * 4) = (f32x2){g0, g1};
             } else HdRow<ESZ>::store(dzr + (size_t)k * ESZ, g0);
         }
-        char *dfr = (char *)d_feats + (size_t)v * C * ESZ;
-        if constexpr (ESZ == 2) {
-#pragma unroll
-            for (int q = 0; q < C; q += 8) {
-                u32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (unsigned)f2bf(df[q + 2 * j]) | ((unsigned)f2bf(df[q + 2 * j + 1]) << 16);
-                *reinterpret_cast<u32x4 *>(dfr + (size_t)q * 2) = o;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < C; q += 4) *reinterpret_cast<f32x4 *>(dfr + (size_t)q * 4) = (f32x4){df[q], df[q + 1], df[q + 2], df[q + 3]};
-        }
+        hd_store_dfeats<ESZ, C>(d_feats, v, df);
     }
-    // column sums of the workgroup's 256 voxels: 8 threads per class over 32 columns each, then the eight in order (fixed order)
-    doda_sync();
-    {
-        const int k = tid >> 3, part = tid & 7;
-        float t = 0.f;
-        if (k < n_cls) {
-            for (int q = 0; q < 32; ++q) t += sz[k][part * 32 + q];
-        }
-        t += __shfl_xor(t, 1, 64);
-        t += __shfl_xor(t, 2, 64);
-        t += __shfl_xor(t, 4, 64);
-        if (k < n_cls && part == 0) db_partial[(size_t)blockIdx.x * n_cls + k] = t;
-    }
+    hd_db_colsums(sz, n_cls, db_partial);
 }
 
 // dW of the head from the voxel-level score gradient, bf16: partial[wg][32 classes][16 channels] = sum over the workgroup's voxels of
@@ -278,46 +246,6 @@ __global__ __launch_bounds__(HD_BLOCK) void head_dw_bf16(const unsigned short *_
     }
 }
 
-inline int hd_blocks(int m) {
-    const int nb = div_up(m, HD_BLOCK);    // one voxel per thread: three dependent global reads per voxel (point list -> point ids ->
-    return nb < 1 ? 1 : nb;                // labels) want every wave slot of the chip filled (1024 fatter workgroups: 24 / 53 us)
-}
-// class counts as compile-time multiples of four (DODA: 20 ScanNet / 13 S3DIS / 11 common classes); others: DODA_ERR_UNSUPPORTED
-#define HD_DISPATCH(KERNEL, ...)                                                                                   \
-    do {                                                                                                           \
-        const int nk = (n_cls + 3) / 4 * 4;                                                                        \
-        if (elem_bytes == 2) {                                                                                     \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<2, 16, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<2, 16, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<2, 16, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<2, 16, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
-        } else {                                                                                                   \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<4, 16, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<4, 16, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<4, 16, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<4, 16, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
-        }                                                                                                          \
-    } while (0)
-// the same class-count buckets with 32 feature channels (the reference configs' `mid_channel: 16 # or 32`): self-training confidence only
-#define ST_DISPATCH32(KERNEL, ...)                                                                                 \
-    do {                                                                                                           \
-        const int nk = (n_cls + 3) / 4 * 4;                                                                        \
-        if (elem_bytes == 2) {                                                                                     \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<2, 32, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<2, 32, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<2, 32, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<2, 32, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
-        } else {                                                                                                   \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<4, 32, 12>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<4, 32, 16>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<4, 32, 20>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<4, 32, 32>), dim3(n_blocks), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                \
-        }                                                                                                          \
-    } while (0)
-inline bool hd_bad(const void *feats, int m, int c, int esz, const float *weight, int n_cls, const int32_t *v2p, int v2p_ld,
-                   const int64_t *labels) {
-    return m < 0 || (esz != 2 && esz != 4) || n_cls <= 0 || v2p_ld < 1 || !feats || !weight || !v2p || !labels;
-}
 }  // namespace
 
 extern "C" int32_t doda_head_ce_blocks(int32_t m) { return hd_blocks(m > 0 ? m : 1); }
@@ -328,10 +256,11 @@ extern "C" int doda_head_ce_fwd(const void *feats, int32_t m, int32_t c, int32_t
     if (!out) return DODA_ERR_INVALID;
     hipStream_t s = as_stream(stream);
     if (m == 0) { (void)hipMemsetAsync(out, 0, 8, s); return DODA_OK; }
-    if (hd_bad(feats, m, c, elem_bytes, weight, n_cls, v2p, v2p_ld, labels) || !partial_ws) return DODA_ERR_INVALID;
+    if (hd_args_bad(m, elem_bytes, v2p_ld, {feats, weight, v2p, labels, partial_ws}) || n_cls <= 0) return DODA_ERR_INVALID;
     if (c != 16 || n_cls > 32) return DODA_ERR_UNSUPPORTED;     // (DODA's head: 16 channels, <= 20 classes; others take the matrix path)
     if (n_blocks != hd_blocks(m)) return DODA_ERR_WORKSPACE;
-    HD_DISPATCH(head_ce_fwd, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index, partial_ws, pred);
+    HD_DISPATCH(head_ce_fwd, 16, n_blocks, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index,
+                partial_ws, pred);
     hipLaunchKernelGGL(head_ce_final, dim3(1), dim3(1024), 0, s, (const float *)partial_ws, n_blocks, out);
     return doda_check_launch();
 }
@@ -341,25 +270,25 @@ extern "C" int doda_head_ce_bwd(const void *feats, int32_t m, int32_t c, int32_t
                                 const float *out, const float *grad, void *d_feats, void *dz, float *db_partial, int32_t n_blocks,
                                 doda_stream_t stream) {
     if (m == 0) return DODA_OK;
-    if (hd_bad(feats, m, c, elem_bytes, weight, n_cls, v2p, v2p_ld, labels) || !out || !grad || !d_feats || !dz || !db_partial)
+    if (hd_args_bad(m, elem_bytes, v2p_ld, {feats, weight, v2p, labels, out, grad, d_feats, dz, db_partial}) || n_cls <= 0)
         return DODA_ERR_INVALID;
     if (c != 16 || n_cls > 32) return DODA_ERR_UNSUPPORTED;
     if (n_blocks != hd_blocks(m)) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
-    HD_DISPATCH(head_ce_bwd, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index, out, grad,
-                d_feats, dz, db_partial);
+    HD_DISPATCH(head_ce_bwd, 16, n_blocks, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index,
+                out, grad, d_feats, dz, db_partial);
     return doda_check_launch();
 }
 
 extern "C" int doda_st_voxel_confidence(const void *feats, int32_t m, int32_t c, int32_t elem_bytes, const float *weight,
                                         const float *bias, int32_t n_cls, int32_t *pred, float *conf, doda_stream_t stream) {
-    if (m < 0 || (elem_bytes != 2 && elem_bytes != 4) || !weight || !pred || !conf || (m > 0 && !feats)) return DODA_ERR_INVALID;
+    if (hd_args_bad(m, elem_bytes, 1, {weight, pred, conf}) || (m > 0 && !feats)) return DODA_ERR_INVALID;
     if ((c != 16 && c != 32) || n_cls < 2 || n_cls > DODA_ST_MAX_CLASSES) return DODA_ERR_UNSUPPORTED;
     if (m == 0) return DODA_OK;
     hipStream_t s = as_stream(stream);
-    const int n_blocks = hd_blocks(m);
-    if (c == 16) HD_DISPATCH(st_voxel_conf, feats, m, weight, bias, n_cls, pred, conf);
-    else ST_DISPATCH32(st_voxel_conf, feats, m, weight, bias, n_cls, pred, conf);
+    // (32 channels, the reference configs' `mid_channel: 16 # or 32`: this entry point only)
+    if (c == 16) HD_DISPATCH(st_voxel_conf, 16, hd_blocks(m), feats, m, weight, bias, n_cls, pred, conf);
+    else HD_DISPATCH(st_voxel_conf, 32, hd_blocks(m), feats, m, weight, bias, n_cls, pred, conf);
     return doda_check_launch();
 }
 

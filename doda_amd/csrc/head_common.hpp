@@ -1,7 +1,10 @@
 // The Linear head on a voxel row, shared by the kernels that must agree on its bits: head_ce_fwd / _bwd and the self-training
 // confidence (head.hip), the Lovasz-softmax items and backward sweeps (lovasz.hip).  Row loads for bf16 / fp32 features, the
-// weights staged in LDS (rounded to bf16 for bf16 features), the logits of one voxel in registers with their argmax.
+// weights staged in LDS (rounded to bf16 for bf16 features), the logits of one voxel in registers with their argmax; what the two
+// backward sweeps have in common (the LDS columns, the d_feats row store, the column sums for db); and the host side of every
+// entry point: block count, argument check, the dispatch over element size and class-count bucket.
 #pragma once
+#include <initializer_list>
 #include "common.hpp"
 #include "spconv_common.hpp"
 
@@ -73,4 +76,80 @@ __device__ __forceinline__ void hd_logits(const float (*w)[HD_MAX_C], const floa
         if ((k & 3) == 3) asm volatile("" ::: "memory");
     }
 }
+
+// ---- the backward sweeps (head_ce_bwd, lovasz_bwd): one voxel per thread, a workgroup's 256 voxels -----------------------------
+// The per-class values of a thread's voxel live in LDS COLUMNS (sz[k][thread]: conflict-free) instead of register arrays: the class
+// loops stay rolled and the kernels need ~50-60 VGPRs — the register form (three 20-element arrays per thread, loops fully unrolled)
+// compiled to 256 VGPRs + spills and ran at 120 us.
+// the voxel's logits into its column, -> their max: the same chain of fused multiply-adds as hd_logits (the forward's bits)
+template <int C>
+__device__ __forceinline__ float hd_logits_lds(const float (*w)[HD_MAX_C], const float *b, int n_cls, const float (&f)[C],
+                                               float (*sz)[HD_BLOCK], int tid) {
+    float mx = -INFINITY;
+#pragma unroll 2
+    for (int k = 0; k < n_cls; ++k) {
+        const float z = hd_logit<C>(w, b, k, f);
+        sz[k][tid] = z;
+        mx = fmaxf(mx, z);
+    }
+    return mx;
+}
+template <int ESZ, int C>
+__device__ __forceinline__ void hd_store_dfeats(void *d_feats, long long v, const float (&df)[C]) {
+    char *dfr = (char *)d_feats + (size_t)v * C * ESZ;
+    if constexpr (ESZ == 2) {
+#pragma unroll
+        for (int q = 0; q < C; q += 8) {
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (unsigned)f2bf(df[q + 2 * j]) | ((unsigned)f2bf(df[q + 2 * j + 1]) << 16);
+            *reinterpret_cast<u32x4 *>(dfr + (size_t)q * 2) = o;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < C; q += 4) *reinterpret_cast<f32x4 *>(dfr + (size_t)q * 4) = (f32x4){df[q], df[q + 1], df[q + 2], df[q + 3]};
+    }
+}
+// db_partial[workgroup][k] = the column sums of the workgroup's 256 voxels: 8 threads per class over 32 columns each, then the eight
+// in order (fixed order)
+__device__ __forceinline__ void hd_db_colsums(const float (*sz)[HD_BLOCK], int n_cls, float *__restrict__ db_partial) {
+    doda_sync();
+    const int k = threadIdx.x >> 3, part = threadIdx.x & 7;
+    float t = 0.f;
+    if (k < n_cls) {
+        for (int q = 0; q < 32; ++q) t += sz[k][part * 32 + q];
+    }
+    t += __shfl_xor(t, 1, 64);
+    t += __shfl_xor(t, 2, 64);
+    t += __shfl_xor(t, 4, 64);
+    if (k < n_cls && part == 0) db_partial[(size_t)blockIdx.x * n_cls + k] = t;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+inline int hd_blocks(int m) {
+    const int nb = div_up(m, HD_BLOCK);    // one voxel per thread: three dependent global reads per voxel (point list -> point ids ->
+    return nb < 1 ? 1 : nb;                // labels) want every wave slot of the chip filled (1024 fatter workgroups: 24 / 53 us)
+}
+// what every entry point of the head rejects as DODA_ERR_INVALID: the voxel count, the element size, the row stride of the point lists
+// (1 where the entry point takes none) and its required pointers
+inline bool hd_args_bad(int m, int esz, int v2p_ld, std::initializer_list<const void *> required) {
+    bool bad = m < 0 || (esz != 2 && esz != 4) || v2p_ld < 1;
+    for (const void *p : required) bad = bad || !p;
+    return bad;
+}
+// KERNEL<element bytes, C channels, classes> on GRID workgroups of HD_BLOCK threads (uses the caller's elem_bytes, n_cls and stream
+// s): class counts as compile-time multiples of four (DODA: 20 ScanNet / 13 S3DIS / 11 common classes)
+#define HD_DISPATCH_ESZ(KERNEL, ESZ, C, GRID, ...)                                                                      \
+    do {                                                                                                                \
+        const int nk = (n_cls + 3) / 4 * 4;                                                                             \
+        if (nk <= 12) hipLaunchKernelGGL((KERNEL<ESZ, C, 12>), dim3(GRID), dim3(HD_BLOCK), 0, s, __VA_ARGS__);          \
+        else if (nk <= 16) hipLaunchKernelGGL((KERNEL<ESZ, C, 16>), dim3(GRID), dim3(HD_BLOCK), 0, s, __VA_ARGS__);     \
+        else if (nk <= 20) hipLaunchKernelGGL((KERNEL<ESZ, C, 20>), dim3(GRID), dim3(HD_BLOCK), 0, s, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((KERNEL<ESZ, C, 32>), dim3(GRID), dim3(HD_BLOCK), 0, s, __VA_ARGS__);                   \
+    } while (0)
+#define HD_DISPATCH(KERNEL, C, GRID, ...)                                                                               \
+    do {                                                                                                                \
+        if (elem_bytes == 2) HD_DISPATCH_ESZ(KERNEL, 2, C, GRID, __VA_ARGS__);                                          \
+        else HD_DISPATCH_ESZ(KERNEL, 4, C, GRID, __VA_ARGS__);                                                          \
+    } while (0)
 }  // namespace

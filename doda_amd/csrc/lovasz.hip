@@ -25,7 +25,8 @@
 #include "../../include/doda_loss.h"
 
 namespace {
-constexpr int LV_BLOCK = HD_BLOCK;
+constexpr int LV_BLOCK = 256;
+static_assert(LV_BLOCK == HD_BLOCK, "the items / backward sweeps use the head's workgroup: its dispatch, LDS columns and column sums");
 constexpr int LV_WAVES = LV_BLOCK / 64;
 constexpr int LV_BITS = 10, LV_BINS = 1 << LV_BITS, LV_PASSES = 3;   // 30 key bits
 constexpr int LV_WTILE = 4096;          // sort: items of one class per wave
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(1024) void lovasz_final(const double *__restrict__ 
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------
-// The per-class values of a thread's voxel live in LDS columns (sz[k][thread]), as in head_ce_bwd: rolled class loops, ~50 VGPRs.
+// The per-class values of a thread's voxel live in its LDS column, as in head_ce_bwd (head_common.hpp).
 template <int ESZ, int C, int NK>
 __global__ __launch_bounds__(LV_BLOCK) void lovasz_bwd(const void *__restrict__ feats, int m, const float *__restrict__ weight,
                                                        const float *__restrict__ bias, int n_cls, const float *__restrict__ gitem,
@@ -306,17 +307,11 @@ __global__ __launch_bounds__(LV_BLOCK) void lovasz_bwd(const void *__restrict__ 
     const int tid = threadIdx.x;
     const long long v = (long long)blockIdx.x * LV_BLOCK + tid;
 #pragma unroll 1
-    for (int k = 0; k < NK; ++k) sz[k][tid] = 0.f;      // (a thread past the last voxel contributes zeros to the column sums)
+    for (int k = 0; k < NK; ++k) sz[k][tid] = 0.f;      // (a thread past the last voxel contributes zeros to hd_db_colsums)
     if (v < m) {
         float f[C];
         hd_load_row<ESZ, C>(feats, v, f);
-        float mx = -INFINITY;
-#pragma unroll 2
-        for (int k = 0; k < n_cls; ++k) {
-            const float z = hd_logit<C>(w, b, k, f);      // (the same chain of fused multiply-adds as hd_logits: the forward's bits)
-            sz[k][tid] = z;
-            mx = fmaxf(mx, z);
-        }
+        const float mx = hd_logits_lds<C>(w, b, n_cls, f, sz, tid);
         float s = 0.f;
 #pragma unroll 2
         for (int k = 0; k < n_cls; ++k) {
@@ -350,50 +345,10 @@ __global__ __launch_bounds__(LV_BLOCK) void lovasz_bwd(const void *__restrict__ 
                 }
             }
         }
-        char *dfr = (char *)d_feats + (size_t)v * C * ESZ;
-        if constexpr (ESZ == 2) {
-#pragma unroll
-            for (int q = 0; q < C; q += 8) {
-                u32x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (unsigned)f2bf(df[q + 2 * j]) | ((unsigned)f2bf(df[q + 2 * j + 1]) << 16);
-                *reinterpret_cast<u32x4 *>(dfr + (size_t)q * 2) = o;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < C; q += 4) *reinterpret_cast<f32x4 *>(dfr + (size_t)q * 4) = (f32x4){df[q], df[q + 1], df[q + 2], df[q + 3]};
-        }
+        hd_store_dfeats<ESZ, C>(d_feats, v, df);
     }
-    // column sums of the workgroup's 256 voxels: 8 threads per class over 32 columns each, then the eight in order (fixed order)
-    doda_sync();
-    {
-        const int k = tid >> 3, part = tid & 7;
-        float t = 0.f;
-        if (k < n_cls) {
-            for (int q = 0; q < 32; ++q) t += sz[k][part * 32 + q];
-        }
-        t += __shfl_xor(t, 1, 64);
-        t += __shfl_xor(t, 2, 64);
-        t += __shfl_xor(t, 4, 64);
-        if (k < n_cls && part == 0) db_partial[(size_t)blockIdx.x * n_cls + k] = t;
-    }
+    hd_db_colsums(sz, n_cls, db_partial);
 }
-
-#define LV_DISPATCH(KERNEL, GRID, ...)                                                                             \
-    do {                                                                                                           \
-        const int nk = (n_cls + 3) / 4 * 4;                                                                        \
-        if (elem_bytes == 2) {                                                                                     \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<2, 16, 12>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<2, 16, 16>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<2, 16, 20>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<2, 16, 32>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);                \
-        } else {                                                                                                   \
-            if (nk <= 12) hipLaunchKernelGGL((KERNEL<4, 16, 12>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);       \
-            else if (nk <= 16) hipLaunchKernelGGL((KERNEL<4, 16, 16>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);  \
-            else if (nk <= 20) hipLaunchKernelGGL((KERNEL<4, 16, 20>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<4, 16, 32>), dim3(GRID), dim3(LV_BLOCK), 0, s, __VA_ARGS__);                \
-        }                                                                                                          \
-    } while (0)
 
 // the workspace, cut into 256-byte aligned pieces
 struct LvPlan {
@@ -437,7 +392,7 @@ extern "C" size_t doda_lovasz_workspace_bytes(int32_t m, int32_t n_cls) {
     return lv_plan(m > 0 ? m : 1, n_cls, &p) ? p.bytes : 0;
 }
 
-extern "C" int32_t doda_lovasz_blocks(int32_t m) { return div_up(m > 0 ? m : 1, LV_BLOCK); }
+extern "C" int32_t doda_lovasz_blocks(int32_t m) { return hd_blocks(m > 0 ? m : 1); }
 
 extern "C" int doda_lovasz_fwd(const void *feats, int32_t m, int32_t c, int32_t elem_bytes, const float *weight, const float *bias,
                                int32_t n_cls, const int32_t *v2p, int32_t v2p_ld, const int64_t *labels, int64_t ignore_index,
@@ -445,8 +400,7 @@ extern "C" int doda_lovasz_fwd(const void *feats, int32_t m, int32_t c, int32_t 
     if (!out || m < 0) return DODA_ERR_INVALID;
     hipStream_t s = as_stream(stream);
     if (m == 0) { (void)hipMemsetAsync(out, 0, 8, s); return DODA_OK; }
-    if ((elem_bytes != 2 && elem_bytes != 4) || v2p_ld < 1 || !feats || !weight || !v2p || !labels || !ws || ((uintptr_t)ws & 255) ||
-        ((uintptr_t)feats & 15))
+    if (hd_args_bad(m, elem_bytes, v2p_ld, {feats, weight, v2p, labels, ws}) || ((uintptr_t)ws & 255) || ((uintptr_t)feats & 15))
         return DODA_ERR_INVALID;
     if (c != 16 || n_cls < 2 || n_cls > DODA_LOVASZ_MAX_CLASSES || v2p_ld - 1 > DODA_LOVASZ_MAX_POINTS_PER_VOXEL) return DODA_ERR_UNSUPPORTED;
     LvPlan p;
@@ -460,8 +414,7 @@ extern "C" int doda_lovasz_fwd(const void *feats, int32_t m, int32_t c, int32_t 
     int32_t *tsum = (int32_t *)(base + p.tsum), *tpre = (int32_t *)(base + p.tpre), *tot = (int32_t *)(base + p.tot);
     double *tloss = (double *)(base + p.tloss);
 
-    const int items_grid = div_up(m, LV_BLOCK);
-    LV_DISPATCH(lovasz_items, items_grid, feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index,
+    HD_DISPATCH(lovasz_items, 16, hd_blocks(m), feats, m, weight, bias, n_cls, v2p, v2p_ld, (const long long *)labels, (long long)ignore_index,
                 keys[0], wt, pred);
     const int sort_grid = div_up(p.n_wt, LV_WAVES);
     int cur = 0;
@@ -494,12 +447,13 @@ extern "C" int doda_lovasz_bwd(const void *feats, int32_t m, int32_t c, int32_t 
                                void *dz_lo, float *db_partial, int32_t n_blocks, doda_stream_t stream) {
     if (m < 0) return DODA_ERR_INVALID;
     if (m == 0) return DODA_OK;
-    if ((elem_bytes != 2 && elem_bytes != 4) || !feats || !weight || !gitem || !out || !grad || !d_feats || !dz || !db_partial ||
-        ((uintptr_t)feats & 15) || ((uintptr_t)d_feats & 15))
+    if (hd_args_bad(m, elem_bytes, 1, {feats, weight, gitem, out, grad, d_feats, dz, db_partial}) || ((uintptr_t)feats & 15) ||
+        ((uintptr_t)d_feats & 15))
         return DODA_ERR_INVALID;
     if (c != 16 || n_cls < 2 || n_cls > DODA_LOVASZ_MAX_CLASSES) return DODA_ERR_UNSUPPORTED;
     if (n_blocks != doda_lovasz_blocks(m)) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
-    LV_DISPATCH(lovasz_bwd, n_blocks, feats, m, weight, bias, n_cls, gitem, out, grad, d_feats, dz, elem_bytes == 2 ? dz_lo : nullptr, db_partial);
+    HD_DISPATCH(lovasz_bwd, 16, n_blocks, feats, m, weight, bias, n_cls, gitem, out, grad, d_feats, dz, elem_bytes == 2 ? dz_lo : nullptr,
+                db_partial);
     return doda_check_launch();
 }

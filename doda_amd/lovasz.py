@@ -68,13 +68,5 @@ class _VoxelHeadLovasz(Function):
     @staticmethod
     def backward(ctx, grad, _grad_pred):
         feats, weight, bias, gitem, out = ctx.saved_tensors
-        g = grad.reshape(1).to(torch.float32)
-        d_feats, dz, dz_lo, d_b = _ops.lovasz_bwd(feats, weight, bias, gitem, out, g)
-        d_w = None
-        if ctx.needs_input_grad[1]:   # dW = dz^T feats: the cross-entropy head's kernels, dz in the layout they read
-            d_w = _ops.head_dw(feats, dz)
-            if dz_lo is not None:     # bf16: the part of dz its rounding dropped, through the same kernel
-                d_w = d_w + _ops.head_dw(feats, dz_lo)
-            d_w = d_w.to(weight.dtype)
-        return (d_feats if ctx.needs_input_grad[0] else None), d_w, (d_b if bias is not None and ctx.needs_input_grad[2] else None), \
-            None, None, None
+        bwd = _ops.lovasz_bwd(feats, weight, bias, gitem, out, grad.reshape(1).to(torch.float32))
+        return _ops.head_grads(ctx.needs_input_grad, feats, weight, bias, *bwd)   # (dW: the cross-entropy head's kernels on dz and dz_lo)

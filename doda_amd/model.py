@@ -615,13 +615,8 @@ class _VoxelHeadCE(Function):
     @staticmethod
     def backward(ctx, grad, _grad_pred):
         feats, weight, bias, v2p, labels, out = ctx.saved_tensors
-        g = grad.reshape(1).to(torch.float32)
-        d_feats, dz, d_b = _ops.head_ce_bwd(feats, weight, bias, v2p, labels, ctx.ignore_index, out, g)
-        d_w = None
-        if ctx.needs_input_grad[1]:   # dW = dz^T feats (voxels as the MFMA k dimension: doda_head_dw_bf16; fp32: identity-table wgrad)
-            d_w = _ops.head_dw(feats, dz).to(weight.dtype)
-        return (d_feats if ctx.needs_input_grad[0] else None), d_w, (d_b if bias is not None and ctx.needs_input_grad[2] else None), \
-            None, None, None
+        d_feats, dz, d_b = _ops.head_ce_bwd(feats, weight, bias, v2p, labels, ctx.ignore_index, out, grad.reshape(1).to(torch.float32))
+        return _ops.head_grads(ctx.needs_input_grad, feats, weight, bias, d_feats, dz, None, d_b)
 
 
 FUSED_HEAD_LOSS = _os.environ.get("DODA_FUSED_HEAD_LOSS", "1") == "1"

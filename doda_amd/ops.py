@@ -859,39 +859,54 @@ def cross_entropy_bwd(logits, labels, lse, out, grad, ignore_index):
 
 
 # ---- point head + loss at voxel level (ABI 11, csrc/head.hip) -----------------------------------------------------
+def _head_args(what, feats, weight, bias, v2p=None, labels=None):
+    """The operands of a voxel-level head call, checked and contiguous: (feats, weight, bias, v2p, labels); v2p and labels None for
+    an entry point that takes no point lists (voxel_confidence)."""
+    _feat_ok(feats, "feats")
+    lists = v2p is not None
+    _need_cuda(weight, *((v2p, labels) if lists else ()))
+    if weight.dtype != torch.float32 or (lists and (v2p.dtype != torch.int32 or labels.dtype != torch.int64 or v2p.dim() != 2)):
+        raise RuntimeError("%s: weight float32 [n_cls, c]%s" % (what, ", v2p int32 [m, 1 + max_active], labels int64 [points]" if lists else ""))
+    cont = lambda t: t.contiguous() if t is not None else None
+    return feats.contiguous(), weight.contiguous(), cont(bias), cont(v2p), cont(labels)
+
+
+def _head_bwd(blocks, feats, weight, bias, want_lo, launch):
+    """A backward sweep into outputs allocated here: launch(the native call's leading arguments (feats .. n_cls), d_feats, dz, dz_lo,
+    db_partial, n_blocks).  -> (d_feats, dz, dz_lo or None, d_bias float32 [n_cls] = the workgroups' rows summed)."""
+    feats, weight = feats.contiguous(), weight.contiguous()
+    (m, c), n_cls = feats.shape, weight.shape[0]
+    nb = int(blocks(m))
+    d_feats = torch.empty_like(feats)
+    dz = torch.empty((m, n_cls), dtype=feats.dtype, device=feats.device)
+    dz_lo = torch.empty_like(dz) if want_lo else None
+    dbp = torch.empty((nb, n_cls), dtype=torch.float32, device=feats.device)
+    launch((_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous() if bias is not None else None), n_cls),
+           d_feats, dz, dz_lo, dbp, nb)
+    return d_feats, dz, dz_lo, dbp.sum(0)
+
+
 def head_ce_fwd(feats, weight, bias, v2p, labels, ignore_index, want_pred=True):
     """Linear head + cross-entropy over the voxel -> point lists without the [points, classes] matrix (doda_head_ce_fwd).
     -> (out float32 [2] = {mean loss over the valid points, n_valid}, pred int32 [m] = argmax class per voxel or None)."""
-    _feat_ok(feats, "feats")
-    for t in (weight, v2p, labels):
-        _need_cuda(t)
-    if weight.dtype != torch.float32 or v2p.dtype != torch.int32 or labels.dtype != torch.int64 or v2p.dim() != 2:
-        raise RuntimeError("head_ce: weight float32 [n_cls, c], v2p int32 [m, 1 + max_active], labels int64 [points]")
-    feats, weight, v2p, labels = feats.contiguous(), weight.contiguous(), v2p.contiguous(), labels.contiguous()
+    feats, weight, bias, v2p, labels = _head_args("head_ce", feats, weight, bias, v2p, labels)
     m, c = feats.shape
     nb = int(lib().doda_head_ce_blocks(m))
     out = torch.empty(2, dtype=torch.float32, device=feats.device)
     pred = torch.empty(m, dtype=torch.int32, device=feats.device) if want_pred else None
     ws = torch.empty(2 * nb, dtype=torch.float32, device=feats.device)
-    check(lib().doda_head_ce_fwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
-                                 weight.shape[0], _p(v2p), v2p.shape[1], _p(labels), int(ignore_index), _p(out),
-                                 _p(pred) if pred is not None else None, _p(ws), nb, _stream()), "doda_head_ce_fwd")
+    check(lib().doda_head_ce_fwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias), weight.shape[0], _p(v2p), v2p.shape[1],
+                                 _p(labels), int(ignore_index), _p(out), _p(pred), _p(ws), nb, _stream()), "doda_head_ce_fwd")
     return out, pred
 
 
 def head_ce_bwd(feats, weight, bias, v2p, labels, ignore_index, out, grad):
     """-> (d_feats [m, c], dz [m, n_cls] — both in the features' dtype —, d_bias float32 [n_cls])."""
-    feats, weight, v2p, labels = feats.contiguous(), weight.contiguous(), v2p.contiguous(), labels.contiguous()
-    m, c = feats.shape
-    n_cls = weight.shape[0]
-    nb = int(lib().doda_head_ce_blocks(m))
-    d_feats = torch.empty_like(feats)
-    dz = torch.empty((m, n_cls), dtype=feats.dtype, device=feats.device)
-    dbp = torch.empty((nb, n_cls), dtype=torch.float32, device=feats.device)
-    check(lib().doda_head_ce_bwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
-                                 n_cls, _p(v2p), v2p.shape[1], _p(labels), int(ignore_index), _p(out), _p(grad.contiguous()),
-                                 _p(d_feats), _p(dz), _p(dbp), nb, _stream()), "doda_head_ce_bwd")
-    return d_feats, dz, dbp.sum(0)
+    v2p, labels = v2p.contiguous(), labels.contiguous()
+    d_feats, dz, _, d_b = _head_bwd(lib().doda_head_ce_blocks, feats, weight, bias, False, lambda head, d_feats, dz, dz_lo, dbp, nb: check(
+        lib().doda_head_ce_bwd(*head, _p(v2p), v2p.shape[1], _p(labels), int(ignore_index), _p(out), _p(grad.contiguous()), _p(d_feats),
+                               _p(dz), _p(dbp), nb, _stream()), "doda_head_ce_bwd"))
+    return d_feats, dz, d_b
 
 
 def head_dw(feats, dz):
@@ -908,17 +923,25 @@ def head_dw(feats, dz):
     return spconv_wgrad(feats.contiguous(), dz, ident, m)[0].t()
 
 
+def head_grads(needs, feats, weight, bias, d_feats, dz, dz_lo, d_b):
+    """The gradients a voxel-level head function (model._VoxelHeadCE, lovasz._VoxelHeadLovasz: feats, weight, bias, v2p, labels,
+    ignore_index) returns, from its backward sweep's outputs and needs = ctx.needs_input_grad: dW = dz^T feats through head_dw, plus
+    the same on dz_lo where the sweep wrote one (bf16: what rounding dz dropped)."""
+    d_w = None
+    if needs[1]:
+        d_w = head_dw(feats, dz)
+        if dz_lo is not None:
+            d_w = d_w + head_dw(feats, dz_lo)
+        d_w = d_w.to(weight.dtype)
+    return (d_feats if needs[0] else None), d_w, (d_b if bias is not None and needs[2] else None), None, None, None
+
+
 # ---- Lovasz-softmax head at voxel level (include/doda_loss.h, csrc/lovasz.hip) -------------------------------------
 def lovasz_fwd(feats, weight, bias, v2p, labels, ignore_index, want_grad=True):
     """Linear head + Lovasz-softmax (classes present) over the voxel -> point lists without the [points, classes] matrix
     (doda_lovasz_fwd).  -> (out float32 [2] = {loss, present classes}, pred int32 [m], gitem float32 [m, n_cls, 2] or None: the
     per-item Lovasz gradients doda_lovasz_bwd reads)."""
-    _feat_ok(feats, "feats")
-    for t in (weight, v2p, labels):
-        _need_cuda(t)
-    if weight.dtype != torch.float32 or v2p.dtype != torch.int32 or labels.dtype != torch.int64 or v2p.dim() != 2:
-        raise RuntimeError("lovasz: weight float32 [n_cls, c], v2p int32 [m, 1 + max_active], labels int64 [points]")
-    feats, weight, v2p, labels = feats.contiguous(), weight.contiguous(), v2p.contiguous(), labels.contiguous()
+    feats, weight, bias, v2p, labels = _head_args("lovasz", feats, weight, bias, v2p, labels)
     m, c = feats.shape
     n_cls = weight.shape[0]
     out = torch.empty(2, dtype=torch.float32, device=feats.device)
@@ -928,36 +951,25 @@ def lovasz_fwd(feats, weight, bias, v2p, labels, ignore_index, want_grad=True):
     if nbytes == 0:
         raise DodaNativeError("doda_lovasz_fwd: %d voxels x %d classes is outside the compiled range" % (m, n_cls))
     ws = _ws(nbytes, feats.device)
-    check(lib().doda_lovasz_fwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
-                                n_cls, _p(v2p), v2p.shape[1], _p(labels), int(ignore_index), _p(out), _p(pred), _p(gitem), _p(ws),
-                                ws.numel(), _stream()), "doda_lovasz_fwd")
+    check(lib().doda_lovasz_fwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias), n_cls, _p(v2p), v2p.shape[1], _p(labels),
+                                int(ignore_index), _p(out), _p(pred), _p(gitem), _p(ws), ws.numel(), _stream()), "doda_lovasz_fwd")
     return out, pred, gitem
 
 
 def lovasz_bwd(feats, weight, bias, gitem, out, grad):
     """-> (d_feats [m, c], dz [m, n_cls] — both in the features' dtype —, dz_lo [m, n_cls] bf16 = what rounding dz to bf16 dropped
     (None for fp32 features), d_bias float32 [n_cls])."""
-    feats, weight = feats.contiguous(), weight.contiguous()
-    m, c = feats.shape
-    n_cls = weight.shape[0]
-    nb = int(lib().doda_lovasz_blocks(m))
-    d_feats = torch.empty_like(feats)
-    dz = torch.empty((m, n_cls), dtype=feats.dtype, device=feats.device)
-    dz_lo = torch.empty_like(dz) if feats.dtype == torch.bfloat16 else None
-    dbp = torch.empty((nb, n_cls), dtype=torch.float32, device=feats.device)
-    check(lib().doda_lovasz_bwd(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias.contiguous()) if bias is not None else None,
-                                n_cls, _p(gitem), _p(out), _p(grad.contiguous()), _p(d_feats), _p(dz), _p(dz_lo), _p(dbp), nb,
-                                _stream()), "doda_lovasz_bwd")
-    return d_feats, dz, dz_lo, dbp.sum(0)
+    return _head_bwd(lib().doda_lovasz_blocks, feats, weight, bias, feats.dtype == torch.bfloat16, lambda head, d_feats, dz, dz_lo, dbp, nb: check(
+        lib().doda_lovasz_bwd(*head, _p(gitem), _p(out), _p(grad.contiguous()), _p(d_feats), _p(dz), _p(dz_lo), _p(dbp), nb, _stream()),
+        "doda_lovasz_bwd"))
 
 
 # ---- self-training pseudo labels (include/doda_selftrain.h) --------------------------------------------
 def voxel_confidence(feats, weight, bias):
     """(pred int32 [m], conf float32 [m]) of the Linear head on the voxel rows: the argmax class (bit-identical to head_ce_fwd's
     pred) and its softmax probability 1 / sum_k exp(z_k - z_max) (doda_st_voxel_confidence).  feats bf16 / fp32 [m, 16 | 32]."""
-    _feat_ok(feats, "feats")
-    _need_cuda(weight)
-    if weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] != feats.shape[1]:
+    feats, weight, bias, _, _ = _head_args("voxel_confidence", feats, weight, bias)
+    if weight.dim() != 2 or weight.shape[1] != feats.shape[1]:
         raise RuntimeError("voxel_confidence: weight float32 [n_cls, c]")
     if bias is not None:
         _need_cuda(bias)
@@ -966,9 +978,8 @@ def voxel_confidence(feats, weight, bias):
     m, c = feats.shape
     pred = torch.empty(m, dtype=torch.int32, device=feats.device)
     conf = torch.empty(m, dtype=torch.float32, device=feats.device)
-    check(lib().doda_st_voxel_confidence(_p(feats), m, c, feats.element_size(), _p(weight.contiguous()),
-                                         _p(bias.contiguous()) if bias is not None else None, weight.shape[0], _p(pred), _p(conf),
-                                         _stream()), "doda_st_voxel_confidence")
+    check(lib().doda_st_voxel_confidence(_p(feats), m, c, feats.element_size(), _p(weight), _p(bias), weight.shape[0], _p(pred),
+                                         _p(conf), _stream()), "doda_st_voxel_confidence")
     return pred, conf
 
 

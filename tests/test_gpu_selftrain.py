@@ -134,10 +134,13 @@ def test_labels_and_kept_counts_bit_exact(native_lib, mode):
 
 # ------------------------------------------------------------------------------------------------ odd class counts in the head backward
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("n_cls", [8, 11, 13])
-def test_voxel_head_backward_with_odd_class_counts(native_lib, n_cls, dtype):
+@pytest.mark.parametrize("n_cls,m", [pytest.param(8, None, id="8"), pytest.param(11, None, id="11"), pytest.param(13, None, id="13"),
+                                     pytest.param(11, 257, id="11-m257"), pytest.param(13, 100, id="13-m100")])
+def test_voxel_head_backward_with_odd_class_counts(native_lib, n_cls, m, dtype):
     """_VoxelHeadCE (doda_head_ce_fwd / _bwd, the dz rows of odd class counts stored element by element) against the fp64 score
-    matrix definition, at the tolerances tests/test_gpu_round6.py holds the 20-class head to."""
+    matrix definition, at the tolerances tests/test_gpu_round6.py holds the 20-class head to.  m: the first m voxels of the scene
+    and their points only — one voxel past a workgroup of the backward sweep (its column sums then cover a workgroup with a single
+    voxel) and less than one workgroup; None: the whole scene."""
     import torch.nn.functional as F
     from doda_amd.model import _VoxelHeadCE
     from doda_amd.scene import make_batch
@@ -147,6 +150,10 @@ def test_voxel_head_backward_with_odd_class_counts(native_lib, n_cls, dtype):
     g = torch.Generator().manual_seed(9 + n_cls)
     labels = torch.randint(0, n_cls, b["labels"].shape, generator=g).to(d)
     labels[torch.randperm(labels.numel(), generator=g)[:5000].to(d)] = 255
+    if m is not None:      # (the point lists keep their point numbers: labels of points outside the first m voxels are not read)
+        v2p = v2p[:m].contiguous()
+        labels = torch.where(p2v < m, labels, torch.full_like(labels, 255))
+        p2v = p2v.clamp(max=m - 1)
     m = v2p.shape[0]
     feats = (torch.randn(m, 16, generator=g) * 1.5).to(d).to(dtype).requires_grad_(True)
     W = (torch.randn(n_cls, 16, generator=g) * 0.4).to(d).requires_grad_(True)

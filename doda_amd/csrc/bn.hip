@@ -15,12 +15,22 @@
 // Lanes own 4-channel fragments (8 B bf16 / 16 B fp32); consecutive lanes walk consecutive
 // fragments, so every access is a contiguous wave-wide burst.  All reductions are fixed-order:
 // results are run-to-run deterministic.  Algorithmic bytes: fwd 3 passes, bwd 5 passes of M*C*s.
+//
+// Four forms of the statistics share this file: standalone (bn_stats_partial / bn_stats_final, bn_bwd_partial / bn_bwd_final,
+// then the apply sweeps; bn_small_* in one launch up to BN_SMALL_ROWS rows), statistics ROWS of a conv epilogue
+// (bn_fwd_final_stats / bn_bwd_final_stats + the apply sweeps, or bn_fused_* in one launch) and fp64 TOTALS (bn_apply /
+// bn_bwd_apply<.., TOT>: no reduction launch).  Each piece of arithmetic exists once:
+//   bn_totals.hpp   the element (bn_fwd_elem4, bn_bwd_front4 + bn_bwd_tail4; scalar twins for the conv prologue), the per-channel
+//                   finish (bn_fwd_finish, bn_unbiased + bn_running, bn_bwd_coef) and the totals prologue's channels;
+//   here            partial_park / partial_row (LDS layout, barrier and column sum of the two partial-sum kernels), sum_rows (the statistics
+//                   rows, four in flight; first row and stride by the caller), bwd_coef4, apply_grid / plain_grid /
+//                   fused_grid / tot_grid_cap, launch_apply / launch_bwd_apply<T, TOT>, BN_DISPATCH (element type),
+//                   any_null / add_bad / bn_args_bad and tot_fwd_args / tot_bwd_args for the entry points;
+//   common.hpp      al16 and env_ll (with layers.hip).
+// Which threads finish which channels differs per form on purpose (see fwd_final_body) and stays with the kernels.
 #include "common.hpp"
 #include "bn_totals.hpp"
-#include <stdlib.h>
-#include <utility>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -32,11 +42,14 @@ __device__ __forceinline__ unsigned short f2bf(float f) {
     return __builtin_bit_cast(unsigned short, (__bf16)f);
 }
 
+__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+__device__ __forceinline__ void st4(float *p, const f32x4 &v) { *reinterpret_cast<f32x4 *>(p) = v; }
+
 struct F32 {
     typedef float elem;
     static constexpr int W = 1;   // 4-channel fragments per 16-byte access
-    static __device__ __forceinline__ f32x4 load4(const elem *p) { return *reinterpret_cast<const f32x4 *>(p); }
-    static __device__ __forceinline__ void store4(elem *p, const f32x4 &v) { *reinterpret_cast<f32x4 *>(p) = v; }
+    static __device__ __forceinline__ f32x4 load4(const elem *p) { return ld4(p); }
+    static __device__ __forceinline__ void store4(elem *p, const f32x4 &v) { st4(p, v); }
     static __device__ __forceinline__ void loadw(const elem *p, f32x4 (&v)[1]) { v[0] = load4(p); }
     static __device__ __forceinline__ void storew(elem *p, const f32x4 (&v)[1]) { store4(p, v[0]); }
 };
@@ -78,6 +91,24 @@ struct Geo {
     int rpb;   // row lanes per block
 };
 
+// ---- the partial-sum kernels' common half: this thread's sums into LDS [rpb][2][c] (partial_park, by the threads that own rows),
+// then a fixed-order column sum, one partial row per block (partial_row, all threads)
+__device__ __forceinline__ void partial_park(float *lds, int rl, int f, int c, const f32x4 &s1, const f32x4 &s2) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        lds[(rl * 2 + 0) * c + f * 4 + q] = s1[q];
+        lds[(rl * 2 + 1) * c + f * 4 + q] = s2[q];
+    }
+}
+__device__ __forceinline__ void partial_row(const float *lds, int c, int rpb, float *__restrict__ partial /*[blocks][2][C]*/) {
+    doda_sync();
+    for (int e = threadIdx.x; e < 2 * c; e += BN_BLOCK) {
+        float t = 0.f;
+        for (int r = 0; r < rpb; ++r) t += lds[r * 2 * c + e];
+        partial[(long long)blockIdx.x * 2 * c + e] = t;
+    }
+}
+
 // ---- pass 1: per-block partial sums of (x-k) and (x-k)^2 -------------------------------------
 template <class T>
 __global__ __launch_bounds__(BN_BLOCK) void bn_stats_partial(const typename T::elem *__restrict__ x,
@@ -93,18 +124,9 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_stats_partial(const typename T::e
             s1 += v;
             s2 += v * v;
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            lds[(rl * 2 + 0) * c + f * 4 + q] = s1[q];
-            lds[(rl * 2 + 1) * c + f * 4 + q] = s2[q];
-        }
+        partial_park(lds, rl, f, c, s1, s2);
     }
-    doda_sync();
-    for (int e = threadIdx.x; e < 2 * c; e += BN_BLOCK) {
-        float t = 0.f;
-        for (int r = 0; r < g.rpb; ++r) t += lds[r * 2 * c + e];
-        partial[(long long)blockIdx.x * 2 * c + e] = t;
-    }
+    partial_row(lds, c, g.rpb, partial);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {  // fixed-order butterfly: deterministic
@@ -139,17 +161,13 @@ __global__ __launch_bounds__(64) void bn_stats_final(const typename T::elem *__r
     s2 = wave_sum(s2);
     if (threadIdx.x != 0) return;
     if (ch == 0 && num_batches_tracked) *num_batches_tracked = n_tracked + 1;
-    const double k = (double)k4[ch & 3];
-    const double d = s1 / m;
-    double var = s2 / m - d * d;
-    if (var < 0.0) var = 0.0;
-    const double mu = k + d;
+    const BnMoments mo = bn_fwd_finish(s1, s2, m, eps);
+    const double mu = (double)k4[ch & 3] + mo.mean;
     mean[ch] = (float)mu;
-    invstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
+    invstd[ch] = mo.invstd;
     if (running_mean) {
-        const double unbiased = m > 1 ? var * (double)m / (double)(m - 1) : var;
-        running_mean[ch] = (float)((1.0 - momentum) * (double)rm_old + momentum * mu);
-        running_var[ch] = (float)((1.0 - momentum) * (double)rv_old + momentum * unbiased);
+        running_mean[ch] = bn_running(rm_old, momentum, mu);
+        running_var[ch] = bn_running(rv_old, momentum, bn_unbiased(mo.var, m));
     }
 }
 
@@ -198,7 +216,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_apply(const typename T::elem *__r
                                                      const float *__restrict__ beta, int relu,
                                                      typename T::elem *__restrict__ y, const TotArgs tot = TotArgs()) {
     // (round 6) FIXED: this thread's first rows are REQUESTED before the totals prologue (its fp64 arithmetic and barrier are a
-    // dependent round trip of their own): with the whole grid resident at once (launch_apply_tot caps it) every workgroup used to sit
+    // dependent round trip of their own): with the whole grid resident at once (tot_grid_cap) every workgroup used to sit
     // through the prologue with no row in flight — 12-16 us per level-1 sweep of 38 MB in the step, 7.5 us without the prologue
     f32x4 pre_v[T::W];
     [[maybe_unused]] bool pre_have = false;
@@ -220,10 +238,10 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_apply(const typename T::elem *__r
         f32x4 mu[W], is[W], ga[W], be[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) {
-            mu[w] = *reinterpret_cast<const f32x4 *>(mean + (f + w) * 4);
-            is[w] = *reinterpret_cast<const f32x4 *>(invstd + (f + w) * 4);
-            ga[w] = *reinterpret_cast<const f32x4 *>(gamma + (f + w) * 4);
-            be[w] = *reinterpret_cast<const f32x4 *>(beta + (f + w) * 4);
+            mu[w] = ld4(mean + (f + w) * 4);
+            is[w] = ld4(invstd + (f + w) * 4);
+            ga[w] = ld4(gamma + (f + w) * 4);
+            be[w] = ld4(beta + (f + w) * 4);
         }
         for (long long e = e0; e < n_w; e += (long long)gridDim.x * BN_BLOCK) {
             f32x4 v[W];
@@ -232,14 +250,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_apply(const typename T::elem *__r
                 for (int w = 0; w < W; ++w) v[w] = pre_v[w];
             } else T::loadw(x + e * (4 * W), v);
 #pragma unroll
-            for (int w = 0; w < W; ++w) {
-                f32x4 o = (v[w] - mu[w]) * is[w] * ga[w] + be[w];
-                if (relu) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = o[q] > 0.f ? o[q] : 0.f;
-                }
-                v[w] = o;
-            }
+            for (int w = 0; w < W; ++w) v[w] = bn_fwd_elem4(v[w], mu[w], is[w], ga[w], be[w], relu);
             T::storew(y + e * (4 * W), v);
         }
         return;
@@ -247,38 +258,31 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_apply(const typename T::elem *__r
     for (long long e = (long long)blockIdx.x * BN_BLOCK + threadIdx.x; e < n_frag;
          e += (long long)gridDim.x * BN_BLOCK) {
         const int f = (int)(e % nf);
-        const f32x4 v = T::load4(x + e * 4);
-        const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + f * 4);
-        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
-        const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-        const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
-        f32x4 o = (v - mu) * is * ga + be;
-        if (relu) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = o[q] > 0.f ? o[q] : 0.f;
-        }
-        T::store4(y + e * 4, o);
+        T::store4(y + e * 4, bn_fwd_elem4(T::load4(x + e * 4), ld4(mean + f * 4), ld4(invstd + f * 4), ld4(gamma + f * 4),
+                                          ld4(beta + f * 4), relu));
     }
 }
 
-// grid of an apply sweep: as many workgroups as fragments need (<= 4096), rounded DOWN so that the thread count is a
-// multiple of the 16-byte columns per row (then FIXED applies); *fixed = false when no such grid exists
-inline int apply_grid(long long n_frag, int nf, int W, bool *fixed, int cap = 4096) {
-    const long long n_w = n_frag / W;
+// grid of a sweep without a fixed column per thread: one workgroup per BN_BLOCK fragments, at most `cap`
+inline int plain_grid(long long n_frag, int cap = 4096) {
+    return (int)((n_frag + BN_BLOCK - 1) / BN_BLOCK < cap ? (n_frag + BN_BLOCK - 1) / BN_BLOCK : cap);
+}
+// grid of an apply sweep: as many workgroups as fragments need (<= cap), rounded DOWN so that the thread count is a
+// multiple of the 16-byte columns per row (then FIXED applies); *fixed = false when no such grid exists or an operand is
+// not `aligned` for 16-byte accesses: then the plain grid of the general sweep
+inline int apply_grid(long long n_frag, int nf, int W, bool aligned, int cap, bool *fixed) {
+    *fixed = false;
+    if (!aligned || nf % W != 0 || n_frag % W != 0) return plain_grid(n_frag);
     const int cols = nf / W;
-    long long grid = (n_w + BN_BLOCK - 1) / BN_BLOCK;
+    long long grid = (n_frag / W + BN_BLOCK - 1) / BN_BLOCK;
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    *fixed = false;
-    if (nf % W != 0 || n_frag % W != 0) return (int)((n_frag + BN_BLOCK - 1) / BN_BLOCK < 4096 ? (n_frag + BN_BLOCK - 1) / BN_BLOCK : 4096);
     int a = cols, b = BN_BLOCK;            // q = cols / gcd(cols, BN_BLOCK): grid must be a multiple of q
     while (b) { const int t = a % b; a = b; b = t; }
     const int q = cols / a;
-    if (grid >= q) {
-        *fixed = true;
-        return (int)(grid - grid % q);
-    }
-    return (int)((n_frag + BN_BLOCK - 1) / BN_BLOCK < 4096 ? (n_frag + BN_BLOCK - 1) / BN_BLOCK : 4096);
+    if (grid < q) return plain_grid(n_frag);
+    *fixed = true;
+    return (int)(grid - grid % q);
 }
 
 // ---- backward pass 1: per-block partial sums of dz and dz*xhat --------------------------------
@@ -295,33 +299,16 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_partial(const typename T::ele
     const int f = threadIdx.x % g.nf, rl = threadIdx.x / g.nf;
     f32x4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
     if (rl < g.rpb) {
-        const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + f * 4);
-        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
-        const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-        const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
+        const f32x4 mu = ld4(mean + f * 4), is = ld4(invstd + f * 4), ga = ld4(gamma + f * 4), be = ld4(beta + f * 4);
         for (long long r = (long long)blockIdx.x * g.rpb + rl; r < m; r += (long long)gridDim.x * g.rpb) {
-            const f32x4 xh = (T::load4(x + r * c + f * 4) - mu) * is;
             f32x4 dz = T::load4(dy + r * c + f * 4);
-            if (relu) {
-                const f32x4 yv = xh * ga + be;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) dz[q] = yv[q] > 0.f ? dz[q] : 0.f;
-            }
+            const f32x4 xh = bn_bwd_front4(T::load4(x + r * c + f * 4), dz, mu, is, ga, be, relu);
             s1 += dz;
             s2 += dz * xh;
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            lds[(rl * 2 + 0) * c + f * 4 + q] = s1[q];
-            lds[(rl * 2 + 1) * c + f * 4 + q] = s2[q];
-        }
+        partial_park(lds, rl, f, c, s1, s2);
     }
-    doda_sync();
-    for (int e = threadIdx.x; e < 2 * c; e += BN_BLOCK) {
-        float t = 0.f;
-        for (int r = 0; r < g.rpb; ++r) t += lds[r * 2 * c + e];
-        partial[(long long)blockIdx.x * 2 * c + e] = t;
-    }
+    partial_row(lds, c, g.rpb, partial);
 }
 
 __global__ __launch_bounds__(64) void bn_bwd_final(const float *__restrict__ partial, int nblocks,
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(64) void bn_bwd_final(const float *__restrict__ par
                                                    float *__restrict__ dgamma, float *__restrict__ dbeta,
                                                    float *__restrict__ coef /*[3][C]*/) {
     const int ch = blockIdx.x;
-    const float a_coef = gamma[ch] * invstd[ch];   // requested before the partial sums (see bn_stats_final)
+    const float ga = gamma[ch], is = invstd[ch];   // requested before the partial sums (see bn_stats_final)
     double s1 = 0.0, s2 = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 64) {
         s1 += (double)partial[(long long)b * 2 * c + ch];
@@ -339,12 +326,12 @@ __global__ __launch_bounds__(64) void bn_bwd_final(const float *__restrict__ par
     s1 = wave_sum(s1);
     s2 = wave_sum(s2);
     if (threadIdx.x != 0) return;
-    dbeta[ch] = (float)s1;
-    dgamma[ch] = (float)s2;
-    // dx = a * (dz - b - xhat * d)
-    coef[ch] = a_coef;
-    coef[c + ch] = (float)(s1 / m);
-    coef[2 * c + ch] = (float)(s2 / m);
+    const BnBwdCoef k = bn_bwd_coef(s1, s2, m, ga, is);
+    dbeta[ch] = k.dbeta;
+    dgamma[ch] = k.dgamma;
+    coef[ch] = k.a;
+    coef[c + ch] = k.b;
+    coef[2 * c + ch] = k.d;
 }
 
 template <class T, bool FIXED, bool TOT = false>
@@ -381,13 +368,13 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply(const typename T::elem 
         f32x4 mu[W], is[W], ga[W], be[W], ca[W], cb[W], cd[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) {
-            mu[w] = *reinterpret_cast<const f32x4 *>(mean + (f + w) * 4);
-            is[w] = *reinterpret_cast<const f32x4 *>(invstd + (f + w) * 4);
-            ga[w] = *reinterpret_cast<const f32x4 *>(gamma + (f + w) * 4);
-            be[w] = *reinterpret_cast<const f32x4 *>(beta + (f + w) * 4);
-            ca[w] = *reinterpret_cast<const f32x4 *>(coef + (f + w) * 4);
-            cb[w] = *reinterpret_cast<const f32x4 *>(coef + c + (f + w) * 4);
-            cd[w] = *reinterpret_cast<const f32x4 *>(coef + 2 * c + (f + w) * 4);
+            mu[w] = ld4(mean + (f + w) * 4);
+            is[w] = ld4(invstd + (f + w) * 4);
+            ga[w] = ld4(gamma + (f + w) * 4);
+            be[w] = ld4(beta + (f + w) * 4);
+            ca[w] = ld4(coef + (f + w) * 4);
+            cb[w] = ld4(coef + c + (f + w) * 4);
+            cd[w] = ld4(coef + 2 * c + (f + w) * 4);
         }
         for (long long e = e0; e < n_w; e += (long long)gridDim.x * BN_BLOCK) {
             f32x4 xv[W], dz[W], av[W];
@@ -401,13 +388,8 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply(const typename T::elem 
             }
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-                const f32x4 xh = (xv[w] - mu[w]) * is[w];
-                if (relu) {
-                    const f32x4 yv = xh * ga[w] + be[w];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dz[w][q] = yv[q] > 0.f ? dz[w][q] : 0.f;
-                }
-                f32x4 o = ca[w] * (dz[w] - cb[w] - xh * cd[w]);
+                const f32x4 xh = bn_bwd_front4(xv[w], dz[w], mu[w], is[w], ga[w], be[w], relu);
+                f32x4 o = bn_bwd_tail4(dz[w], xh, ca[w], cb[w], cd[w]);
                 if (add) o += av[w];
                 xv[w] = o;
             }
@@ -418,21 +400,10 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply(const typename T::elem 
     for (long long e = (long long)blockIdx.x * BN_BLOCK + threadIdx.x; e < n_frag;
          e += (long long)gridDim.x * BN_BLOCK) {
         const int f = (int)(e % nf);
-        const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + f * 4);
-        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
-        const f32x4 xh = (T::load4(x + e * 4) - mu) * is;
         f32x4 dz = T::load4(dy + e * 4);
-        if (relu) {
-            const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-            const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
-            const f32x4 yv = xh * ga + be;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dz[q] = yv[q] > 0.f ? dz[q] : 0.f;
-        }
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(coef + f * 4);
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(coef + c + f * 4);
-        const f32x4 d = *reinterpret_cast<const f32x4 *>(coef + 2 * c + f * 4);
-        f32x4 o = a * (dz - b - xh * d);
+        const f32x4 xh = bn_bwd_front4(T::load4(x + e * 4), dz, ld4(mean + f * 4), ld4(invstd + f * 4), ld4(gamma + f * 4),
+                                       ld4(beta + f * 4), relu);
+        f32x4 o = bn_bwd_tail4(dz, xh, ld4(coef + f * 4), ld4(coef + c + f * 4), ld4(coef + 2 * c + f * 4));
         // a second gradient of x (residual / skip path) summed here; add_ld != 0: its rows lie add_ld elements apart
         // (a column slice of a wider matrix: the gradient of torch.cat's input, reference model/unet_block.py:93)
         if (add) o += T::load4(add_ld ? add + (e / nf) * add_ld + f * 4 : add + e * 4);
@@ -440,71 +411,40 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply(const typename T::elem 
     }
 }
 
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline int plain_grid(long long n_frag) {
-    return (int)((n_frag + BN_BLOCK - 1) / BN_BLOCK < 4096 ? (n_frag + BN_BLOCK - 1) / BN_BLOCK : 4096);
+// DODA_BN_TOT_GRID: cap of the totals sweeps' grids.  (round 6) at most 1024 workgroups (4 per CU, all resident at once): every
+// workgroup pays the totals prologue — 16 doubles per channel out of padded 128-byte lines, fp64 division / square root, a barrier —
+// once per ~5 x 16 bytes per thread at level 1 instead of once per 16 bytes.  In-step sums of bn_apply + bn_bwd_apply
+// (tools/layers_prof.sh): 4096 workgroups 613 us, 2048 573, 1024 518, 768 518, 512 531, 256 667
+inline int tot_grid_cap() {
+    static const int cap = [] { const int v = (int)env_ll("DODA_BN_TOT_GRID", 1024); return v < 64 ? 64 : v > 4096 ? 4096 : v; }();
+    return cap;
 }
-template <class T>
-void launch_apply(const typename T::elem *x, long long n_frag, int nf, const float *mean, const float *invstd,
-                  const float *gamma, const float *beta, int relu, typename T::elem *y, hipStream_t s) {
+// TOT: mean / invstd (forward) and coef (backward) are unused — the kernels derive them from `tot`
+template <class T, bool TOT>
+int launch_apply(const void *x_, long long n_frag, int nf, const float *mean, const float *invstd, const float *gamma,
+                 const float *beta, int relu, void *y_, const TotArgs &tot, hipStream_t s) {
+    typedef typename T::elem elem;
+    const elem *x = (const elem *)x_;
+    elem *y = (elem *)y_;
     bool fixed;
-    int grid = apply_grid(n_frag, nf, T::W, &fixed);
-    if (fixed && !(al16(x) && al16(y))) { fixed = false; grid = plain_grid(n_frag); }
-    if (fixed)
-        hipLaunchKernelGGL((bn_apply<T, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, mean, invstd, gamma, beta, relu, y);
-    else
-        hipLaunchKernelGGL((bn_apply<T, false>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, mean, invstd, gamma, beta, relu, y);
+    const int grid = apply_grid(n_frag, nf, T::W, al16(x) && al16(y), TOT ? tot_grid_cap() : 4096, &fixed);
+    hipLaunchKernelGGL((fixed ? bn_apply<T, true, TOT> : bn_apply<T, false, TOT>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, mean,
+                       invstd, gamma, beta, relu, y, tot);
+    return doda_check_launch();
 }
-template <class T>
-void launch_apply_tot(const typename T::elem *x, long long n_frag, int nf, const float *gamma, const float *beta, int relu,
-                      typename T::elem *y, const TotArgs &tot, hipStream_t s) {
-    // (round 6) at most 1024 workgroups (4 per CU, all resident at once): every workgroup pays the totals prologue — 16 doubles per
-    // channel out of padded 128-byte lines, fp64 division / square root, a barrier — once per ~5 x 16 bytes per thread at level 1
-    // instead of once per 16 bytes.  In-step sums of bn_apply + bn_bwd_apply (tools/layers_prof.sh, DODA_BN_TOT_GRID): 4096
-    // workgroups 613 us, 2048 573, 1024 518, 768 518, 512 531, 256 667
-    static const int cap = [] { const char *e = getenv("DODA_BN_TOT_GRID"); const int v = e ? atoi(e) : 1024; return v < 64 ? 64 : v > 4096 ? 4096 : v; }();
+template <class T, bool TOT>
+int launch_bwd_apply(const void *x_, const void *dy_, long long n_frag, int nf, int c, const float *mean, const float *invstd,
+                     const float *gamma, const float *beta, int relu, const float *coef, void *dx_, const void *add_, int add_ld,
+                     const TotArgs &tot, hipStream_t s) {
+    typedef typename T::elem elem;
+    const elem *x = (const elem *)x_, *dy = (const elem *)dy_, *add = (const elem *)add_;
+    elem *dx = (elem *)dx_;
+    const bool aligned = al16(x) && al16(dy) && al16(dx) && (!add || (al16(add) && add_ld % (4 * T::W) == 0));
     bool fixed;
-    int grid = apply_grid(n_frag, nf, T::W, &fixed, cap);
-    if (fixed && !(al16(x) && al16(y))) { fixed = false; grid = plain_grid(n_frag); }
-    if (fixed)
-        hipLaunchKernelGGL((bn_apply<T, true, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, nullptr, nullptr, gamma, beta, relu, y, tot);
-    else
-        hipLaunchKernelGGL((bn_apply<T, false, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, nullptr, nullptr, gamma, beta, relu, y, tot);
-}
-template <class T>
-void launch_bwd_apply_tot(const typename T::elem *x, const typename T::elem *dy, long long n_frag, int nf, int c,
-                          const float *mean, const float *invstd, const float *gamma, const float *beta, int relu,
-                          typename T::elem *dx, const typename T::elem *add, int add_ld, const TotArgs &tot, hipStream_t s) {
-    static const int cap = [] { const char *e = getenv("DODA_BN_TOT_GRID"); const int v = e ? atoi(e) : 1024; return v < 64 ? 64 : v > 4096 ? 4096 : v; }();
-    bool fixed;
-    int grid = apply_grid(n_frag, nf, T::W, &fixed, cap);
-    if (fixed && !(al16(x) && al16(dy) && al16(dx) && (!add || (al16(add) && add_ld % (4 * T::W) == 0)))) {
-        fixed = false;
-        grid = plain_grid(n_frag);
-    }
-    if (fixed)
-        hipLaunchKernelGGL((bn_bwd_apply<T, true, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag, nf, c, mean, invstd, gamma,
-                           beta, relu, nullptr, dx, add, add_ld, tot);
-    else
-        hipLaunchKernelGGL((bn_bwd_apply<T, false, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag, nf, c, mean, invstd, gamma,
-                           beta, relu, nullptr, dx, add, add_ld, tot);
-}
-template <class T>
-void launch_bwd_apply(const typename T::elem *x, const typename T::elem *dy, long long n_frag, int nf, int c,
-                      const float *mean, const float *invstd, const float *gamma, const float *beta, int relu,
-                      const float *coef, typename T::elem *dx, const typename T::elem *add, int add_ld, hipStream_t s) {
-    bool fixed;
-    int grid = apply_grid(n_frag, nf, T::W, &fixed);
-    if (fixed && !(al16(x) && al16(dy) && al16(dx) && (!add || (al16(add) && add_ld % (4 * T::W) == 0)))) {
-        fixed = false;
-        grid = plain_grid(n_frag);
-    }
-    if (fixed)
-        hipLaunchKernelGGL((bn_bwd_apply<T, true>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag, nf, c, mean, invstd, gamma,
-                           beta, relu, coef, dx, add, add_ld);
-    else
-        hipLaunchKernelGGL((bn_bwd_apply<T, false>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag, nf, c, mean, invstd, gamma,
-                           beta, relu, coef, dx, add, add_ld);
+    const int grid = apply_grid(n_frag, nf, T::W, aligned, TOT ? tot_grid_cap() : 4096, &fixed);
+    hipLaunchKernelGGL((fixed ? bn_bwd_apply<T, true, TOT> : bn_bwd_apply<T, false, TOT>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag,
+                       nf, c, mean, invstd, gamma, beta, relu, coef, dx, add, add_ld, tot);
+    return doda_check_launch();
 }
 
 // ---- small-M variants: ONE launch per direction --------------------------------------------------
@@ -512,25 +452,6 @@ void launch_bwd_apply(const typename T::elem *x, const typename T::elem *dy, lon
 // launch-floor time.  Here a block owns one 4-channel fragment column over ALL rows, so the
 // statistics need no cross-block step: sweep 1 reduces, sweep 2 applies (rows stay in L2).
 constexpr int BN_SMALL_ROWS = 4096;   // measured: at ~11k rows the C/4 blocks of this form take up to 80 us
-
-__device__ __forceinline__ f32x4 block_sum4(f32x4 v, float (*lds)[4]) {  // 256 threads, fixed order
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] += __shfl_xor(v[q], d, 64);
-    }
-    const int wid = threadIdx.x >> 6;
-    doda_sync();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lds[wid][q] = v[q];
-    }
-    doda_sync();
-    f32x4 t;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) t[q] = (lds[0][q] + lds[1][q]) + (lds[2][q] + lds[3][q]);
-    return t;
-}
 
 // both sums through ONE LDS exchange (the small kernels are launch-floor kernels: every barrier pair counts)
 __device__ __forceinline__ void block_sum4x2(f32x4 &a, f32x4 &b, float (*lds)[8]) {  // 256 threads, fixed order
@@ -570,15 +491,14 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_small_fwd(const typename T::elem 
     // four of them in series (shift row, stats sweep, affine parameters, apply sweep).
     constexpr int RPT = BN_SMALL_ROWS / BN_BLOCK;
     const f32x4 k = T::load4(x + f * 4);
-    const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-    const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
+    const f32x4 ga = ld4(gamma + f * 4), be = ld4(beta + f * 4);
     // (the running statistics and the batch counter too: updating them element by element at the end
     // cost thread 0 five more dependent round trips)
     f32x4 rm = {0, 0, 0, 0}, rv = {0, 0, 0, 0};
     long long n_tracked = 0;
     if (threadIdx.x == 0 && running_mean) {
-        rm = *reinterpret_cast<const f32x4 *>(running_mean + f * 4);
-        rv = *reinterpret_cast<const f32x4 *>(running_var + f * 4);
+        rm = ld4(running_mean + f * 4);
+        rv = ld4(running_var + f * 4);
     }
     if (threadIdx.x == 0 && f == 0 && nbt) n_tracked = *nbt;
     f32x4 xv[RPT];
@@ -599,35 +519,26 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_small_fwd(const typename T::elem 
     f32x4 mu, is;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const double d = (double)s1[q] / m;
-        double var = (double)s2[q] / m - d * d;
-        if (var < 0.0) var = 0.0;
-        mu[q] = (float)((double)k[q] + d);
-        is[q] = (float)(1.0 / sqrt(var + (double)eps));
-        const double unbiased = m > 1 ? var * (double)m / (double)(m - 1) : var;
-        rm[q] = (float)((1.0 - momentum) * (double)rm[q] + momentum * ((double)k[q] + d));
-        rv[q] = (float)((1.0 - momentum) * (double)rv[q] + momentum * unbiased);
+        const BnMoments mo = bn_fwd_finish((double)s1[q], (double)s2[q], m, eps);
+        const double muq = (double)k[q] + mo.mean;
+        mu[q] = (float)muq;
+        is[q] = mo.invstd;
+        rm[q] = bn_running(rm[q], momentum, muq);
+        rv[q] = bn_running(rv[q], momentum, bn_unbiased(mo.var, m));
     }
     if (threadIdx.x == 0) {
-        *reinterpret_cast<f32x4 *>(mean + f * 4) = mu;
-        *reinterpret_cast<f32x4 *>(invstd + f * 4) = is;
+        st4(mean + f * 4, mu);
+        st4(invstd + f * 4, is);
         if (running_mean) {
-            *reinterpret_cast<f32x4 *>(running_mean + f * 4) = rm;
-            *reinterpret_cast<f32x4 *>(running_var + f * 4) = rv;
+            st4(running_mean + f * 4, rm);
+            st4(running_var + f * 4, rv);
         }
         if (f == 0 && nbt) *nbt = n_tracked + 1;
     }
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
         const int r = threadIdx.x + i * BN_BLOCK;
-        if (r < m) {
-            f32x4 o = (xv[i] - mu) * is * ga + be;
-            if (relu) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = o[q] > 0.f ? o[q] : 0.f;
-            }
-            T::store4(y + (long long)r * c + f * 4, o);
-        }
+        if (r < m) T::store4(y + (long long)r * c + f * 4, bn_fwd_elem4(xv[i], mu, is, ga, be, relu));
     }
 }
 
@@ -644,10 +555,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_small_bwd(const typename T::elem 
                                                          const typename T::elem *__restrict__ add, int add_ld = 0) {
     __shared__ float lds[4][8];
     const int f = blockIdx.x;
-    const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + f * 4);
-    const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
-    const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-    const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
+    const f32x4 mu = ld4(mean + f * 4), is = ld4(invstd + f * 4), ga = ld4(gamma + f * 4), be = ld4(beta + f * 4);
     constexpr int RPT = BN_SMALL_ROWS / BN_BLOCK;
     f32x4 xh[RPT], dz[RPT], ad[RPT];   // all reads up front, kept for the apply pass (see bn_small_fwd)
 #pragma unroll
@@ -661,12 +569,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_small_bwd(const typename T::elem 
     f32x4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
-        xh[i] = (xh[i] - mu) * is;
-        if (relu) {
-            const f32x4 yv = xh[i] * ga + be;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dz[i][q] = yv[q] > 0.f ? dz[i][q] : 0.f;
-        }
+        xh[i] = bn_bwd_front4(xh[i], dz[i], mu, is, ga, be, relu);
         const float w = threadIdx.x + i * BN_BLOCK < m ? 1.f : 0.f;
         s1 += dz[i] * w;
         s2 += dz[i] * xh[i] * w;
@@ -681,27 +584,13 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_small_bwd(const typename T::elem 
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
         const int r = threadIdx.x + i * BN_BLOCK;
-        if (r < m) T::store4(dx + (long long)r * c + f * 4, a * (dz[i] - b - xh[i] * d) + ad[i]);
+        if (r < m) T::store4(dx + (long long)r * c + f * 4, bn_bwd_tail4(dz[i], xh[i], a, b, d) + ad[i]);
     }
 }
 
 // ---- statistics delivered by a conv epilogue (doda_spconv_gather_ex) ---------------------------------
 // `stats` = [rows][2][c] partial sums, one row per workgroup tile of the conv.  One block per 4-channel
 // fragment: 256 threads walk the rows with 16-byte loads, fp64 sums, fixed-order tree in LDS.
-__device__ __forceinline__ void block_sum_d4(double (&v)[4], double (*lds)[4]) {   // 256 threads, fixed order
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = wave_sum(v[q]);
-    const int wid = threadIdx.x >> 6;
-    doda_sync();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lds[wid][q] = v[q];
-    }
-    doda_sync();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = (lds[0][q] + lds[1][q]) + (lds[2][q] + lds[3][q]);
-}
-
 // both sums at once: one pair of barriers instead of two (the `final` kernels are launch-floor kernels: 75 per step)
 __device__ __forceinline__ void block_sum_d8(double (&a)[4], double (&b)[4], double (*lds)[8]) {   // 256 threads, fixed order
 #pragma unroll
@@ -719,28 +608,28 @@ __device__ __forceinline__ void block_sum_d8(double (&a)[4], double (&b)[4], dou
     }
 }
 
-// this thread's share of the partial rows of channel quad f.  Four rows per trip with all eight loads
+// this thread's share of the partial rows of channel quad f: rows r0, r0 + step, ...  Four rows per trip with all eight loads
 // issued before the first add: a level-1 layer has ~4700 partial rows and four blocks to reduce them, so
 // the kernel is a chain of L2 round trips (13.4 us with one row per trip)
-__device__ __forceinline__ void sum_partials(const float *__restrict__ stats, int rows, int c, int f,
-                                             double (&s1)[4], double (&s2)[4]) {
-    int r = threadIdx.x;
-    for (; r + 3 * BN_BLOCK < rows; r += 4 * BN_BLOCK) {
+__device__ __forceinline__ void sum_rows(const float *__restrict__ stats, int rows, int c, int f, int r0, int step,
+                                         double (&s1)[4], double (&s2)[4]) {
+    int r = r0;
+    for (; r + 3 * step < rows; r += 4 * step) {
         f32x4 a[4], b[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float *p = stats + (long long)(r + k * BN_BLOCK) * 2 * c + f * 4;
-            a[k] = *reinterpret_cast<const f32x4 *>(p);
-            b[k] = *reinterpret_cast<const f32x4 *>(p + c);
+            const float *p = stats + (long long)(r + k * step) * 2 * c + f * 4;
+            a[k] = ld4(p);
+            b[k] = ld4(p + c);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int q = 0; q < 4; ++q) { s1[q] += (double)a[k][q]; s2[q] += (double)b[k][q]; }
     }
-    for (; r < rows; r += BN_BLOCK) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(stats + (long long)r * 2 * c + f * 4);
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(stats + (long long)r * 2 * c + c + f * 4);
+    for (; r < rows; r += step) {
+        const f32x4 a = ld4(stats + (long long)r * 2 * c + f * 4);
+        const f32x4 b = ld4(stats + (long long)r * 2 * c + c + f * 4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) { s1[q] += (double)a[q]; s2[q] += (double)b[q]; }
     }
@@ -763,21 +652,18 @@ __device__ __forceinline__ void fwd_final_body(int f, const float *__restrict__ 
     }
     if (threadIdx.x == 0 && f == 0 && nbt) n_tracked = *nbt;
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    sum_partials(stats, rows, c, f, s1, s2);
+    sum_rows(stats, rows, c, f, threadIdx.x, BN_BLOCK, s1, s2);
     block_sum_d8(s1, s2, lds);
     if (threadIdx.x >= 4) return;
     double a1 = s1[0], a2 = s2[0];
 #pragma unroll
     for (int k = 1; k < 4; ++k) { if (q == k) { a1 = s1[k]; a2 = s2[k]; } }
-    const double d = a1 / m;
-    double var = a2 / m - d * d;
-    if (var < 0.0) var = 0.0;
-    mean[f * 4 + q] = (float)d;
-    invstd[f * 4 + q] = (float)(1.0 / sqrt(var + (double)eps));
+    const BnMoments mo = bn_fwd_finish(a1, a2, m, eps);
+    mean[f * 4 + q] = (float)mo.mean;
+    invstd[f * 4 + q] = mo.invstd;
     if (running_mean) {
-        const double unbiased = m > 1 ? var * (double)m / (double)(m - 1) : var;
-        running_mean[f * 4 + q] = (float)((1.0 - momentum) * (double)rm + momentum * d);
-        running_var[f * 4 + q] = (float)((1.0 - momentum) * (double)rv + momentum * unbiased);
+        running_mean[f * 4 + q] = bn_running(rm, momentum, mo.mean);
+        running_var[f * 4 + q] = bn_running(rv, momentum, bn_unbiased(mo.var, m));
     }
     if (threadIdx.x == 0 && f == 0 && nbt) *nbt = n_tracked + 1;
 }
@@ -791,31 +677,33 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_fwd_final_stats(const float *__re
     fwd_final_body(blockIdx.x, stats, rows, m, c, eps, momentum, mean, invstd, running_mean, running_var, nbt);
 }
 
+// bn_bwd_coef for the four channels of a fragment
+__device__ __forceinline__ void bwd_coef4(const double (&s1)[4], const double (&s2)[4], int m, const f32x4 &ga, const f32x4 &is,
+                                          f32x4 &a, f32x4 &b, f32x4 &d, f32x4 &dg, f32x4 &db) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const BnBwdCoef k = bn_bwd_coef(s1[q], s2[q], m, ga[q], is[q]);
+        a[q] = k.a; b[q] = k.b; d[q] = k.d; dg[q] = k.dgamma; db[q] = k.dbeta;
+    }
+}
+
 __device__ __forceinline__ void bwd_final_body(int f, const float *__restrict__ stats, int rows, int m, int c,
                                                const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                float *__restrict__ dgamma, float *__restrict__ dbeta,
                                                float *__restrict__ coef /*[3][C]*/) {
     __shared__ double lds[4][8];
-    const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-    const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
+    const f32x4 ga = ld4(gamma + f * 4), is = ld4(invstd + f * 4);
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    sum_partials(stats, rows, c, f, s1, s2);
+    sum_rows(stats, rows, c, f, threadIdx.x, BN_BLOCK, s1, s2);
     block_sum_d8(s1, s2, lds);
     if (threadIdx.x != 0) return;
     f32x4 db, dg, a, bb, dd;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        db[q] = (float)s1[q];
-        dg[q] = (float)s2[q];
-        a[q] = ga[q] * is[q];
-        bb[q] = (float)(s1[q] / m);
-        dd[q] = (float)(s2[q] / m);
-    }
-    *reinterpret_cast<f32x4 *>(dbeta + f * 4) = db;
-    *reinterpret_cast<f32x4 *>(dgamma + f * 4) = dg;
-    *reinterpret_cast<f32x4 *>(coef + f * 4) = a;           // dx = a * (dz - b - xhat * d)
-    *reinterpret_cast<f32x4 *>(coef + c + f * 4) = bb;
-    *reinterpret_cast<f32x4 *>(coef + 2 * c + f * 4) = dd;
+    bwd_coef4(s1, s2, m, ga, is, a, bb, dd, dg, db);
+    st4(dbeta + f * 4, db);
+    st4(dgamma + f * 4, dg);
+    st4(coef + f * 4, a);           // dx = a * (dz - b - xhat * d)
+    st4(coef + c + f * 4, bb);
+    st4(coef + 2 * c + f * 4, dd);
 }
 
 __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_final_stats(const float *__restrict__ stats, int rows, int m, int c,
@@ -845,28 +733,7 @@ __device__ __forceinline__ void fused_reduce(const float *__restrict__ stats, in
     const int f = threadIdx.x % nf, rl = threadIdx.x / nf;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { s1[q] = 0.0; s2[q] = 0.0; }
-    if (rl < rpb) {
-        int r = rl;
-        for (; r + 3 * rpb < rows; r += 4 * rpb) {      // four rows in flight
-            f32x4 a[4], b[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float *p = stats + (long long)(r + k * rpb) * 2 * c + f * 4;
-                a[k] = *reinterpret_cast<const f32x4 *>(p);
-                b[k] = *reinterpret_cast<const f32x4 *>(p + c);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { s1[q] += (double)a[k][q]; s2[q] += (double)b[k][q]; }
-        }
-        for (; r < rows; r += rpb) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(stats + (long long)r * 2 * c + f * 4);
-            const f32x4 b = *reinterpret_cast<const f32x4 *>(stats + (long long)r * 2 * c + c + f * 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { s1[q] += (double)a[q]; s2[q] += (double)b[q]; }
-        }
-    }
+    if (rl < rpb) sum_rows(stats, rows, c, f, rl, rpb, s1, s2);
 #pragma unroll
     for (int q = 0; q < 4; ++q) { red[threadIdx.x][q] = s1[q]; red[threadIdx.x][4 + q] = s2[q]; }
     doda_sync();
@@ -896,33 +763,27 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_fused_fwd(const typename T::elem 
     if (threadIdx.x < nf) {
         const int f = threadIdx.x;
         f32x4 mu, is;
-        double dmu[4], dvar[4];
+        BnMoments mo[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const double d = s1[q] / m;
-            double var = s2[q] / m - d * d;
-            if (var < 0.0) var = 0.0;
-            dmu[q] = d;
-            dvar[q] = var;
-            mu[q] = (float)d;
-            is[q] = (float)(1.0 / sqrt(var + (double)eps));
+            mo[q] = bn_fwd_finish(s1[q], s2[q], m, eps);
+            mu[q] = (float)mo[q].mean;
+            is[q] = mo[q].invstd;
         }
         v_mu[f] = mu;      // (the apply sweep evaluates (x - mean) * invstd * gamma + beta exactly as bn_apply does)
         v_is[f] = is;
         if (blockIdx.x == 0) {
-            *reinterpret_cast<f32x4 *>(mean + f * 4) = mu;
-            *reinterpret_cast<f32x4 *>(invstd + f * 4) = is;
+            st4(mean + f * 4, mu);
+            st4(invstd + f * 4, is);
             if (running_mean) {
-                f32x4 rm = *reinterpret_cast<const f32x4 *>(running_mean + f * 4);
-                f32x4 rv = *reinterpret_cast<const f32x4 *>(running_var + f * 4);
+                f32x4 rm = ld4(running_mean + f * 4), rv = ld4(running_var + f * 4);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const double unbiased = m > 1 ? dvar[q] * (double)m / (double)(m - 1) : dvar[q];
-                    rm[q] = (float)((1.0 - momentum) * (double)rm[q] + momentum * dmu[q]);
-                    rv[q] = (float)((1.0 - momentum) * (double)rv[q] + momentum * unbiased);
+                    rm[q] = bn_running(rm[q], momentum, mo[q].mean);
+                    rv[q] = bn_running(rv[q], momentum, bn_unbiased(mo[q].var, m));
                 }
-                *reinterpret_cast<f32x4 *>(running_mean + f * 4) = rm;
-                *reinterpret_cast<f32x4 *>(running_var + f * 4) = rv;
+                st4(running_mean + f * 4, rm);
+                st4(running_var + f * 4, rv);
             }
             if (f == 0 && nbt) *nbt = *nbt + 1;
         }
@@ -930,15 +791,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_fused_fwd(const typename T::elem 
     doda_sync();
     for (long long e = (long long)blockIdx.x * BN_BLOCK + threadIdx.x; e < n_frag; e += (long long)gridDim.x * BN_BLOCK) {
         const int f = (int)(e % nf);
-        const f32x4 v = T::load4(x + e * 4);
-        const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-        const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
-        f32x4 o = (v - v_mu[f]) * v_is[f] * ga + be;
-        if (relu) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = o[q] > 0.f ? o[q] : 0.f;
-        }
-        T::store4(y + e * 4, o);
+        T::store4(y + e * 4, bn_fwd_elem4(T::load4(x + e * 4), v_mu[f], v_is[f], ld4(gamma + f * 4), ld4(beta + f * 4), relu));
     }
 }
 
@@ -959,38 +812,21 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_fused_bwd(const typename T::elem 
     fused_reduce(stats, rows, c, nf, rpb, red, s1, s2);
     if (threadIdx.x < nf) {
         const int f = threadIdx.x;
-        const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
         f32x4 db, dg, a, bb, dd;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            db[q] = (float)s1[q];
-            dg[q] = (float)s2[q];
-            a[q] = ga[q] * is[q];
-            bb[q] = (float)(s1[q] / m);
-            dd[q] = (float)(s2[q] / m);
-        }
+        bwd_coef4(s1, s2, m, ld4(gamma + f * 4), ld4(invstd + f * 4), a, bb, dd, dg, db);
         v_a[f] = a; v_b[f] = bb; v_d[f] = dd;
         if (blockIdx.x == 0) {
-            *reinterpret_cast<f32x4 *>(dbeta + f * 4) = db;
-            *reinterpret_cast<f32x4 *>(dgamma + f * 4) = dg;
+            st4(dbeta + f * 4, db);
+            st4(dgamma + f * 4, dg);
         }
     }
     doda_sync();
     for (long long e = (long long)blockIdx.x * BN_BLOCK + threadIdx.x; e < n_frag; e += (long long)gridDim.x * BN_BLOCK) {
         const int f = (int)(e % nf);
-        const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + f * 4);
-        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + f * 4);
-        const f32x4 xh = (T::load4(x + e * 4) - mu) * is;
         f32x4 dz = T::load4(dy + e * 4);
-        if (relu) {
-            const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + f * 4);
-            const f32x4 be = *reinterpret_cast<const f32x4 *>(beta + f * 4);
-            const f32x4 yv = xh * ga + be;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dz[q] = yv[q] > 0.f ? dz[q] : 0.f;
-        }
-        f32x4 o = v_a[f] * (dz - v_b[f] - xh * v_d[f]);
+        const f32x4 xh = bn_bwd_front4(T::load4(x + e * 4), dz, ld4(mean + f * 4), ld4(invstd + f * 4), ld4(gamma + f * 4),
+                                       ld4(beta + f * 4), relu);
+        f32x4 o = bn_bwd_tail4(dz, xh, v_a[f], v_b[f], v_d[f]);
         if (add) o += T::load4(add + e * 4);
         T::store4(dx + e * 4, o);
     }
@@ -1006,15 +842,11 @@ inline bool fused_ok(int rows, int c, int m) {
     // DODA_BN_FUSED_SMALL=0 switches that off).
     static const bool on = getenv("DODA_BN_FUSED_FINAL") && getenv("DODA_BN_FUSED_FINAL")[0] == '1';
     // DODA_BN_FUSED_SMALL: 0 = off, 1 / unset = the default threshold, larger values = that many elements
-    static const long long small_elems = [] {
-        const char *e = getenv("DODA_BN_FUSED_SMALL");
-        if (!e) return BN_FUSED_SMALL_ELEMS;
-        const long long v = atoll(e);
-        return v == 1 ? BN_FUSED_SMALL_ELEMS : v;
-    }();
+    static const long long small_elems = [] { const long long v = env_ll("DODA_BN_FUSED_SMALL", 1); return v == 1 ? BN_FUSED_SMALL_ELEMS : v; }();
     const bool want = on || (long long)m * c <= small_elems;
     return want && c <= BN_FUSED_MAX_C && c / 4 <= BN_BLOCK && (long long)rows * 2 * c * 4 <= BN_FUSED_MAX_PARTIAL_BYTES;
 }
+inline int fused_grid(long long n_frag) { return plain_grid(n_frag, BN_FUSED_BLOCKS); }
 
 Geo make_geo(int c) {
     Geo g;
@@ -1037,11 +869,10 @@ int run_fwd(const void *x_, int m, int c, float eps, float momentum, const float
             int relu, void *y_, float *mean, float *invstd, void *ws, size_t ws_bytes, hipStream_t s) {
     typedef typename T::elem elem;
     const elem *x = (const elem *)x_;
-    elem *y = (elem *)y_;
     const Geo g = make_geo(c);
     if (training && m <= BN_SMALL_ROWS) {
         hipLaunchKernelGGL((bn_small_fwd<T>), dim3(c / 4), dim3(BN_BLOCK), 0, s, x, m, c, eps, momentum,
-                           gamma, beta, running_mean, running_var, nbt, relu, y, mean, invstd);
+                           gamma, beta, running_mean, running_var, nbt, relu, (elem *)y_, mean, invstd);
         return doda_check_launch();
     }
     if (training) {
@@ -1053,23 +884,20 @@ int run_fwd(const void *x_, int m, int c, float eps, float momentum, const float
         hipLaunchKernelGGL((bn_stats_final<T>), dim3(c), dim3(64), 0, s, x, partial, nb, m,
                            c, eps, momentum, mean, invstd, running_mean, running_var, nbt);
     }
-    const long long n_frag = (long long)m * g.nf;
-    launch_apply<T>(x, n_frag, g.nf, mean, invstd, gamma, beta, relu, y, s);
-    return doda_check_launch();
+    return launch_apply<T, false>(x, (long long)m * g.nf, g.nf, mean, invstd, gamma, beta, relu, y_, TotArgs(), s);
 }
 
 template <class T>
 int run_bwd(const void *x_, const void *dy_, int m, int c, const float *mean, const float *invstd,
             const float *gamma, const float *beta, int relu, void *dx_, float *dgamma, float *dbeta,
-            void *ws, size_t ws_bytes, const void *add_, hipStream_t s, int add_ld = 0) {
+            void *ws, size_t ws_bytes, const void *add_, int add_ld, hipStream_t s) {
     typedef typename T::elem elem;
-    const elem *x = (const elem *)x_, *dy = (const elem *)dy_, *add = (const elem *)add_;
-    elem *dx = (elem *)dx_;
+    const elem *x = (const elem *)x_, *dy = (const elem *)dy_;
     const Geo g = make_geo(c);
     if (add_ld == c) add_ld = 0;   // dense
     if (m <= BN_SMALL_ROWS) {
         hipLaunchKernelGGL((bn_small_bwd<T>), dim3(c / 4), dim3(BN_BLOCK), 0, s, x, dy, m, c, mean, invstd,
-                           gamma, beta, relu, dx, dgamma, dbeta, add, add_ld);
+                           gamma, beta, relu, (elem *)dx_, dgamma, dbeta, (const elem *)add_, add_ld);
         return doda_check_launch();
     }
     const int nb = n_blocks_for(m, g);
@@ -1080,15 +908,77 @@ int run_bwd(const void *x_, const void *dy_, int m, int c, const float *mean, co
                        m, c, g, mean, invstd, gamma, beta, relu, partial);
     hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(64), 0, s, partial, nb, m, c, invstd,
                        gamma, dgamma, dbeta, coef);
-    const long long n_frag = (long long)m * g.nf;
-    launch_bwd_apply<T>(x, dy, n_frag, g.nf, c, mean, invstd, gamma, beta, relu, coef, dx, add, add_ld, s);
-    return doda_check_launch();
+    return launch_bwd_apply<T, false>(x, dy, (long long)m * g.nf, g.nf, c, mean, invstd, gamma, beta, relu, coef, dx_, add_, add_ld,
+                                      TotArgs(), s);
 }
 
+// ---- BatchNorm(+ReLU) over statistics that a conv epilogue accumulated ------------------------------
+template <class T>
+int run_fwd_stats(const void *x_, int m, int c, const float *stats, int rows, float eps, float momentum,
+                  const float *gamma, const float *beta, float *rm, float *rv, long long *nbt, int relu,
+                  void *y_, float *mean, float *invstd, hipStream_t s) {
+    typedef typename T::elem elem;
+    const Geo g = make_geo(c);
+    const long long n_frag = (long long)m * g.nf;
+    if (fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows
+        hipLaunchKernelGGL((bn_fused_fwd<T>), dim3(fused_grid(n_frag)), dim3(BN_BLOCK), 0, s, (const elem *)x_, n_frag, g.nf, g.rpb,
+                           stats, rows, m, eps, momentum, gamma, beta, mean, invstd, rm, rv, nbt, relu, (elem *)y_);
+        return doda_check_launch();
+    }
+    hipLaunchKernelGGL(bn_fwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, eps, momentum, mean,
+                       invstd, rm, rv, nbt);
+    return launch_apply<T, false>(x_, n_frag, g.nf, mean, invstd, gamma, beta, relu, y_, TotArgs(), s);
+}
+
+template <class T>
+int run_bwd_stats(const void *x_, const void *dy_, int m, int c, const float *stats, int rows,
+                  const float *mean, const float *invstd, const float *gamma, const float *beta, int relu,
+                  const void *add_, int add_ld, void *dx_, float *dgamma, float *dbeta, float *coef, hipStream_t s) {
+    typedef typename T::elem elem;
+    const Geo g = make_geo(c);
+    const long long n_frag = (long long)m * g.nf;
+    if (add_ld == c || !add_) add_ld = 0;   // dense
+    if (!add_ld && fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows (opt-in; dense `add` only)
+        hipLaunchKernelGGL((bn_fused_bwd<T>), dim3(fused_grid(n_frag)), dim3(BN_BLOCK), 0, s, (const elem *)x_, (const elem *)dy_,
+                           n_frag, g.nf, g.rpb, stats, rows, m, mean, invstd, gamma, beta, relu, dgamma, dbeta, (elem *)dx_,
+                           (const elem *)add_);
+        return doda_check_launch();
+    }
+    hipLaunchKernelGGL(bn_bwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, invstd, gamma, dgamma,
+                       dbeta, coef);
+    return launch_bwd_apply<T, false>(x_, dy_, n_frag, g.nf, c, mean, invstd, gamma, beta, relu, coef, dx_, add_, add_ld, TotArgs(), s);
+}
+
+// ---- argument checks of the entry points ---------------------------------------------------------------------------
 bool bn_args_bad(int m, int c, int elem_bytes) {
     return m <= 0 || c <= 0 || (c % 4) != 0 || c > 1024 || (elem_bytes != 2 && elem_bytes != 4);
 }
+template <class... P>
+bool any_null(const P *...p) { return (... || !p); }
+// the second-gradient operand: rows at least c elements apart, a multiple of one fragment, fragment-aligned
+bool add_bad(const void *add, int add_ld, int c, int elem_bytes) {
+    return add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes));
+}
+// TotArgs of the forward / backward totals sweeps (backward: no running statistics; `accum` is the op list's alone, layers.hip)
+TotArgs tot_fwd_args(const double *ta, const double *tb, int ca, int m, float eps, float momentum, float *rm, float *rv,
+                     long long *nbt, float *save_mean, float *save_invstd) {
+    TotArgs t;
+    t.ta = ta; t.tb = tb; t.ca = ca; t.m = m; t.eps = eps; t.momentum = momentum;
+    t.rm = rm; t.rv = rv; t.nbt = nbt;
+    t.out_a = save_mean; t.out_b = save_invstd;
+    return t;
+}
+TotArgs tot_bwd_args(const double *totals, int c, int m, float *dgamma, float *dbeta) {
+    TotArgs t;
+    t.ta = totals; t.ca = c; t.m = m;
+    t.out_a = dgamma; t.out_b = dbeta;
+    return t;
+}
 }  // namespace
+
+// the value of an expression in T, with T = F32 or BF16 by the element size (which has passed bn_args_bad)
+#define BN_DISPATCH(elem_bytes, ...) \
+    ((elem_bytes) == 4 ? [&] { typedef F32 T; return __VA_ARGS__; }() : [&] { typedef BF16 T; return __VA_ARGS__; }())
 
 extern "C" size_t doda_bn_workspace_bytes(int32_t m, int32_t c) {
     if (m <= 0 || c <= 0 || c % 4) return 256;
@@ -1104,14 +994,9 @@ extern "C" int doda_bn_relu_fwd(const void *x, int32_t m, int32_t c, int32_t ele
                                 size_t ws_bytes, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !y || !gamma || !beta || !save_mean || !save_invstd || !ws) return DODA_ERR_INVALID;
-    if (elem_bytes == 4)
-        return run_fwd<F32>(x, m, c, eps, momentum, gamma, beta, running_mean, running_var,
-                            (long long *)num_batches_tracked, training, relu, y, save_mean, save_invstd,
-                            ws, ws_bytes, as_stream(stream));
-    return run_fwd<BF16>(x, m, c, eps, momentum, gamma, beta, running_mean, running_var,
-                         (long long *)num_batches_tracked, training, relu, y, save_mean, save_invstd, ws,
-                         ws_bytes, as_stream(stream));
+    if (any_null(x, y, gamma, beta, save_mean, save_invstd, ws)) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, run_fwd<T>(x, m, c, eps, momentum, gamma, beta, running_mean, running_var, (long long *)num_batches_tracked,
+                                              training, relu, y, save_mean, save_invstd, ws, ws_bytes, as_stream(stream)));
 }
 
 extern "C" int doda_bn_relu_bwd(const void *x, const void *dy, int32_t m, int32_t c,
@@ -1121,13 +1006,9 @@ extern "C" int doda_bn_relu_bwd(const void *x, const void *dy, int32_t m, int32_
                                 size_t ws_bytes, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !dy || !dx || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta || !ws)
-        return DODA_ERR_INVALID;
-    if (elem_bytes == 4)
-        return run_bwd<F32>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws,
-                            ws_bytes, nullptr, as_stream(stream));
-    return run_bwd<BF16>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws,
-                         ws_bytes, nullptr, as_stream(stream));
+    if (any_null(x, dy, dx, gamma, beta, save_mean, save_invstd, dgamma, dbeta, ws)) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, run_bwd<T>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws, ws_bytes,
+                                              nullptr, 0, as_stream(stream)));
 }
 
 // dx = BN backward + add: `add` ([m, c], dtype of x) is a second gradient of the same x — in a
@@ -1140,57 +1021,10 @@ extern "C" int doda_bn_relu_bwd_add(const void *x, const void *dy, int32_t m, in
                                        float *dbeta, void *ws, size_t ws_bytes, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !dy || !dx || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta || !ws || !add)
-        return DODA_ERR_INVALID;
-    if (add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes))) return DODA_ERR_INVALID;
-    if (elem_bytes == 4)
-        return run_bwd<F32>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws,
-                            ws_bytes, add, as_stream(stream), add_ld);
-    return run_bwd<BF16>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws,
-                         ws_bytes, add, as_stream(stream), add_ld);
-}
-// ---- BatchNorm(+ReLU) over statistics that a conv epilogue accumulated ------------------------------
-template <class T>
-static int run_fwd_stats(const void *x_, int m, int c, const float *stats, int rows, float eps, float momentum,
-                         const float *gamma, const float *beta, float *rm, float *rv, long long *nbt, int relu,
-                         void *y_, float *mean, float *invstd, hipStream_t s) {
-    typedef typename T::elem elem;
-    const Geo g = make_geo(c);
-    if (fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows
-        const long long nfr = (long long)m * g.nf;
-        const int grid = (int)((nfr + BN_BLOCK - 1) / BN_BLOCK < BN_FUSED_BLOCKS ? (nfr + BN_BLOCK - 1) / BN_BLOCK : BN_FUSED_BLOCKS);
-        hipLaunchKernelGGL((bn_fused_fwd<T>), dim3(grid), dim3(BN_BLOCK), 0, s, (const elem *)x_, nfr, g.nf, g.rpb, stats, rows,
-                           m, eps, momentum, gamma, beta, mean, invstd, rm, rv, nbt, relu, (elem *)y_);
-        return doda_check_launch();
-    }
-    const long long n_frag = (long long)m * g.nf;
-    hipLaunchKernelGGL(bn_fwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, eps, momentum, mean,
-                       invstd, rm, rv, nbt);
-    launch_apply<T>((const elem *)x_, n_frag, g.nf, mean, invstd, gamma, beta, relu, (elem *)y_, s);
-    return doda_check_launch();
-}
-
-template <class T>
-static int run_bwd_stats(const void *x_, const void *dy_, int m, int c, const float *stats, int rows,
-                         const float *mean, const float *invstd, const float *gamma, const float *beta, int relu,
-                         const void *add_, void *dx_, float *dgamma, float *dbeta, float *coef, hipStream_t s,
-                         int add_ld = 0) {
-    typedef typename T::elem elem;
-    const Geo g = make_geo(c);
-    if (add_ld == c || !add_) add_ld = 0;   // dense
-    if (!add_ld && fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows (opt-in; dense `add` only)
-        const long long nfr = (long long)m * g.nf;
-        const int grid = (int)((nfr + BN_BLOCK - 1) / BN_BLOCK < BN_FUSED_BLOCKS ? (nfr + BN_BLOCK - 1) / BN_BLOCK : BN_FUSED_BLOCKS);
-        hipLaunchKernelGGL((bn_fused_bwd<T>), dim3(grid), dim3(BN_BLOCK), 0, s, (const elem *)x_, (const elem *)dy_, nfr, g.nf,
-                           g.rpb, stats, rows, m, mean, invstd, gamma, beta, relu, dgamma, dbeta, (elem *)dx_, (const elem *)add_);
-        return doda_check_launch();
-    }
-    const long long n_frag = (long long)m * g.nf;
-    hipLaunchKernelGGL(bn_bwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, invstd, gamma, dgamma,
-                       dbeta, coef);
-    launch_bwd_apply<T>((const elem *)x_, (const elem *)dy_, n_frag, g.nf, c, mean, invstd, gamma, beta, relu, coef,
-                        (elem *)dx_, (const elem *)add_, add_ld, s);
-    return doda_check_launch();
+    if (any_null(x, dy, dx, gamma, beta, save_mean, save_invstd, dgamma, dbeta, ws, add)) return DODA_ERR_INVALID;
+    if (add_bad(add, add_ld, c, elem_bytes)) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, run_bwd<T>(x, dy, m, c, save_mean, save_invstd, gamma, beta, relu, dx, dgamma, dbeta, ws, ws_bytes,
+                                              add, add_ld, as_stream(stream)));
 }
 
 extern "C" int doda_bn_relu_fwd_stats(const void *x, int32_t m, int32_t c, int32_t elem_bytes, const float *stats,
@@ -1200,12 +1034,9 @@ extern "C" int doda_bn_relu_fwd_stats(const void *x, int32_t m, int32_t c, int32
                                       float *save_invstd, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !y || !stats || stats_rows <= 0 || !gamma || !beta || !save_mean || !save_invstd) return DODA_ERR_INVALID;
-    if (elem_bytes == 4)
-        return run_fwd_stats<F32>(x, m, c, stats, stats_rows, eps, momentum, gamma, beta, running_mean, running_var,
-                                  (long long *)num_batches_tracked, relu, y, save_mean, save_invstd, as_stream(stream));
-    return run_fwd_stats<BF16>(x, m, c, stats, stats_rows, eps, momentum, gamma, beta, running_mean, running_var,
-                               (long long *)num_batches_tracked, relu, y, save_mean, save_invstd, as_stream(stream));
+    if (any_null(x, y, stats, gamma, beta, save_mean, save_invstd) || stats_rows <= 0) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, run_fwd_stats<T>(x, m, c, stats, stats_rows, eps, momentum, gamma, beta, running_mean, running_var,
+                                                    (long long *)num_batches_tracked, relu, y, save_mean, save_invstd, as_stream(stream)));
 }
 
 extern "C" int doda_bn_relu_apply(const void *x, int32_t m, int32_t c, int32_t elem_bytes, const float *mean,
@@ -1213,15 +1044,9 @@ extern "C" int doda_bn_relu_apply(const void *x, int32_t m, int32_t c, int32_t e
                                   doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !y || !mean || !invstd || !gamma || !beta) return DODA_ERR_INVALID;
-    const Geo g = make_geo(c);
-    const long long n_frag = (long long)m * g.nf;
-    if (elem_bytes == 4)
-        launch_apply<F32>((const float *)x, n_frag, g.nf, mean, invstd, gamma, beta, relu, (float *)y, as_stream(stream));
-    else
-        launch_apply<BF16>((const unsigned short *)x, n_frag, g.nf, mean, invstd, gamma, beta, relu, (unsigned short *)y,
-                           as_stream(stream));
-    return doda_check_launch();
+    if (any_null(x, y, mean, invstd, gamma, beta)) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, launch_apply<T, false>(x, (long long)m * (c / 4), c / 4, mean, invstd, gamma, beta, relu, y, TotArgs(),
+                                                          as_stream(stream)));
 }
 
 // ABI 6: the reduction alone — the apply pass rides in the consuming convolution's prologue (spconv_tile.hip, PRE)
@@ -1230,7 +1055,7 @@ extern "C" int doda_bn_fwd_final(const float *stats, int32_t stats_rows, int32_t
                                  float *save_invstd, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, 2)) return DODA_ERR_UNSUPPORTED;
-    if (!stats || stats_rows <= 0 || !save_mean || !save_invstd || (!running_mean != !running_var)) return DODA_ERR_INVALID;
+    if (any_null(stats, save_mean, save_invstd) || stats_rows <= 0 || (!running_mean != !running_var)) return DODA_ERR_INVALID;
     hipLaunchKernelGGL(bn_fwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, as_stream(stream), stats, stats_rows, m, c, eps,
                        momentum, save_mean, save_invstd, running_mean, running_var, (long long *)num_batches_tracked);
     return doda_check_launch();
@@ -1245,44 +1070,27 @@ extern "C" int doda_bn_relu_fwd_totals(const void *x, int32_t m, int32_t c, int3
                                        float *save_invstd, doda_stream_t stream) {
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
-    if (!x || !y || !totals || !gamma || !beta || !save_mean || !save_invstd || (!running_mean != !running_var))
-        return DODA_ERR_INVALID;
+    if (any_null(x, y, totals, gamma, beta, save_mean, save_invstd) || (!running_mean != !running_var)) return DODA_ERR_INVALID;
     if (totals_b && (c_a <= 0 || c_a >= c)) return DODA_ERR_INVALID;
-    TotArgs t;
-    t.ta = totals; t.tb = totals_b; t.ca = totals_b ? c_a : c; t.m = m; t.eps = eps; t.momentum = momentum;
-    t.rm = running_mean; t.rv = running_var; t.nbt = (long long *)num_batches_tracked;
-    t.out_a = save_mean; t.out_b = save_invstd;
-    const Geo g = make_geo(c);
-    const long long n_frag = (long long)m * g.nf;
-    if (elem_bytes == 4)
-        launch_apply_tot<F32>((const float *)x, n_frag, g.nf, gamma, beta, relu, (float *)y, t, as_stream(stream));
-    else
-        launch_apply_tot<BF16>((const unsigned short *)x, n_frag, g.nf, gamma, beta, relu, (unsigned short *)y, t, as_stream(stream));
-    return doda_check_launch();
+    const TotArgs t = tot_fwd_args(totals, totals_b, totals_b ? c_a : c, m, eps, momentum, running_mean, running_var,
+                                   (long long *)num_batches_tracked, save_mean, save_invstd);
+    return BN_DISPATCH(elem_bytes, launch_apply<T, true>(x, (long long)m * (c / 4), c / 4, nullptr, nullptr, gamma, beta, relu, y, t,
+                                                         as_stream(stream)));
 }
 
+// (the two entry points over a data-grad epilogue's statistics test `add` before m == 0)
 extern "C" int doda_bn_relu_bwd_totals(const void *x, const void *dy, int32_t m, int32_t c, int32_t elem_bytes,
                                        const double *totals, const float *save_mean, const float *save_invstd,
                                        const float *gamma, const float *beta, int32_t relu, const void *add, int32_t add_ld,
                                        void *dx, float *dgamma, float *dbeta, doda_stream_t stream) {
-    if (add && (add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes)))) return DODA_ERR_INVALID;
+    if (add && add_bad(add, add_ld, c, elem_bytes)) return DODA_ERR_INVALID;
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
-    if (!x || !dy || !dx || !totals || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta) return DODA_ERR_INVALID;
-    TotArgs t;
-    t.ta = totals; t.tb = nullptr; t.ca = c; t.m = m; t.eps = 0.f; t.momentum = 0.f;
-    t.rm = nullptr; t.rv = nullptr; t.nbt = nullptr;
-    t.out_a = dgamma; t.out_b = dbeta;
-    const Geo g = make_geo(c);
-    const long long n_frag = (long long)m * g.nf;
+    if (any_null(x, dy, dx, totals, gamma, beta, save_mean, save_invstd, dgamma, dbeta)) return DODA_ERR_INVALID;
     if (add_ld == c || !add) add_ld = 0;   // dense
-    if (elem_bytes == 4)
-        launch_bwd_apply_tot<F32>((const float *)x, (const float *)dy, n_frag, g.nf, c, save_mean, save_invstd, gamma, beta, relu,
-                                  (float *)dx, (const float *)add, add_ld, t, as_stream(stream));
-    else
-        launch_bwd_apply_tot<BF16>((const unsigned short *)x, (const unsigned short *)dy, n_frag, g.nf, c, save_mean, save_invstd,
-                                   gamma, beta, relu, (unsigned short *)dx, (const unsigned short *)add, add_ld, t, as_stream(stream));
-    return doda_check_launch();
+    return BN_DISPATCH(elem_bytes, launch_bwd_apply<T, true>(x, dy, (long long)m * (c / 4), c / 4, c, save_mean, save_invstd, gamma, beta,
+                                                             relu, nullptr, dx, add, add_ld, tot_bwd_args(totals, c, m, dgamma, dbeta),
+                                                             as_stream(stream)));
 }
 
 extern "C" int doda_bn_relu_bwd_stats(const void *x, const void *dy, int32_t m, int32_t c, int32_t elem_bytes,
@@ -1290,15 +1098,10 @@ extern "C" int doda_bn_relu_bwd_stats(const void *x, const void *dy, int32_t m, 
                                          const float *save_invstd, const float *gamma, const float *beta, int32_t relu,
                                          const void *add, int32_t add_ld, void *dx, float *dgamma, float *dbeta,
                                          float *coef_ws, doda_stream_t stream) {
-    if (add && (add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes)))) return DODA_ERR_INVALID;
+    if (add && add_bad(add, add_ld, c, elem_bytes)) return DODA_ERR_INVALID;
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes)) return DODA_ERR_UNSUPPORTED;
-    if (!x || !dy || !dx || !stats || stats_rows <= 0 || !gamma || !beta || !save_mean || !save_invstd || !dgamma ||
-        !dbeta || !coef_ws)
-        return DODA_ERR_INVALID;
-    if (elem_bytes == 4)
-        return run_bwd_stats<F32>(x, dy, m, c, stats, stats_rows, save_mean, save_invstd, gamma, beta, relu, add, dx,
-                                  dgamma, dbeta, coef_ws, as_stream(stream), add_ld);
-    return run_bwd_stats<BF16>(x, dy, m, c, stats, stats_rows, save_mean, save_invstd, gamma, beta, relu, add, dx,
-                               dgamma, dbeta, coef_ws, as_stream(stream), add_ld);
+    if (any_null(x, dy, dx, stats, gamma, beta, save_mean, save_invstd, dgamma, dbeta, coef_ws) || stats_rows <= 0) return DODA_ERR_INVALID;
+    return BN_DISPATCH(elem_bytes, run_bwd_stats<T>(x, dy, m, c, stats, stats_rows, save_mean, save_invstd, gamma, beta, relu, add, add_ld,
+                                                    dx, dgamma, dbeta, coef_ws, as_stream(stream)));
 }

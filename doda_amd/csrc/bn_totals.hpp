@@ -5,6 +5,8 @@
 #pragma once
 #include "common.hpp"
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 constexpr int BN_TOT_MAX_C = 256;
 constexpr int BN_TOT_SLOTS = 8;      // = DODA_STATS_SLOTS (spconv_common.hpp)
 
@@ -32,23 +34,49 @@ __device__ __forceinline__ void tot_sums(const TotArgs &t, int c, int ch, double
     }
 }
 
+// ---- the per-channel arithmetic: ONE copy for every form of the statistics (standalone partials, statistics rows, fused, totals) ----
+// Forward finish: batch mean, biased variance (clamped at 0) and 1 / sqrt(variance + eps) from (sum, sum of squares) over m rows.
+// `mean` is the mean of what was summed: the standalone kernels sum x - k (k = the first row) and add k themselves.
+struct BnMoments { double mean, var; float invstd; };
+__device__ __forceinline__ BnMoments bn_fwd_finish(double s1, double s2, int m, float eps) {
+    BnMoments r;
+    r.mean = s1 / m;
+    r.var = s2 / m - r.mean * r.mean;
+    if (r.var < 0.0) r.var = 0.0;
+    r.invstd = (float)(1.0 / sqrt(r.var + (double)eps));
+    return r;
+}
+// Running statistics: running_mean takes the batch mean (shift included), running_var the UNBIASED variance.
+__device__ __forceinline__ double bn_unbiased(double var, int m) { return m > 1 ? var * (double)m / (double)(m - 1) : var; }
+__device__ __forceinline__ float bn_running(float old, float momentum, double v) {
+    return (float)((1.0 - momentum) * (double)old + momentum * v);
+}
+// Backward coefficients, dx = a * (dz - b - xhat * d), and the parameter gradients, from s1 = sum dz, s2 = sum dz * xhat.
+struct BnBwdCoef { float a, b, d, dgamma, dbeta; };
+__device__ __forceinline__ BnBwdCoef bn_bwd_coef(double s1, double s2, int m, float gamma, float invstd) {
+    BnBwdCoef r;
+    r.dbeta = (float)s1;
+    r.dgamma = (float)s2;
+    r.a = gamma * invstd;
+    r.b = (float)(s1 / m);
+    r.d = (float)(s2 / m);
+    return r;
+}
+
 // Forward, channel `ch`: batch mean / 1 / sqrt(biased variance + eps) from the totals; `publish` (one workgroup of the launch):
 // save_mean / save_invstd, the running statistics (momentum, unbiased variance) and num_batches_tracked.
 __device__ __forceinline__ void tot_fwd_channel(const TotArgs &t, int c, int ch, bool publish, float &mu, float &is) {
     double s1, s2;
     tot_sums(t, c, ch, s1, s2);
-    const double d = s1 / t.m;
-    double var = s2 / t.m - d * d;
-    if (var < 0.0) var = 0.0;
-    mu = (float)d;
-    is = (float)(1.0 / sqrt(var + (double)t.eps));
+    const BnMoments mo = bn_fwd_finish(s1, s2, t.m, t.eps);
+    mu = (float)mo.mean;
+    is = mo.invstd;
     if (publish) {
         t.out_a[ch] = mu;
         t.out_b[ch] = is;
         if (t.rm) {
-            const double unbiased = t.m > 1 ? var * (double)t.m / (double)(t.m - 1) : var;
-            t.rm[ch] = (float)((1.0 - t.momentum) * (double)t.rm[ch] + t.momentum * d);
-            t.rv[ch] = (float)((1.0 - t.momentum) * (double)t.rv[ch] + t.momentum * unbiased);
+            t.rm[ch] = bn_running(t.rm[ch], t.momentum, mo.mean);
+            t.rv[ch] = bn_running(t.rv[ch], t.momentum, bn_unbiased(mo.var, t.m));
         }
         if (ch == 0 && t.nbt) *t.nbt = *t.nbt + 1;
     }
@@ -59,16 +87,17 @@ __device__ __forceinline__ void tot_bwd_channel(const TotArgs &t, int c, int ch,
                                                 float &ca, float &cb, float &cd) {
     double s1, s2;
     tot_sums(t, c, ch, s1, s2);
-    ca = gamma * invstd;
-    cb = (float)(s1 / t.m);
-    cd = (float)(s2 / t.m);
+    const BnBwdCoef k = bn_bwd_coef(s1, s2, t.m, gamma, invstd);
+    ca = k.a;
+    cb = k.b;
+    cd = k.d;
     if (publish) {
         if (t.accum) {
-            t.out_b[ch] += (float)s1;
-            t.out_a[ch] += (float)s2;
+            t.out_b[ch] += k.dbeta;
+            t.out_a[ch] += k.dgamma;
         } else {
-            t.out_b[ch] = (float)s1;                // dbeta
-            t.out_a[ch] = (float)s2;                // dgamma
+            t.out_b[ch] = k.dbeta;
+            t.out_a[ch] = k.dgamma;
         }
     }
 }
@@ -76,6 +105,8 @@ __device__ __forceinline__ void tot_bwd_channel(const TotArgs &t, int c, int ch,
 // One element of the sweeps, in the order the standalone kernels always used (-ffp-contract=off: every operation rounds):
 //   forward  y  = [relu]((x - mu) * is * ga + be)
 //   backward dx = ca * ([yv > 0] dz - cb - xh * cd),  xh = (x - mu) * is, yv = xh * ga + be
+// The scalar pair serves the conv prologue (spconv_common.hpp pre_piece, which clamps y itself), the 4-channel forms below every
+// sweep of bn.hip: the same formulas, operation for operation.
 __device__ __forceinline__ float bn_fwd_elem(float x, float mu, float is, float ga, float be) { return (x - mu) * is * ga + be; }
 __device__ __forceinline__ float bn_bwd_elem(float x, float dz, float mu, float is, float ga, float be, float ca, float cb, float cd,
                                              int relu) {
@@ -85,5 +116,28 @@ __device__ __forceinline__ float bn_bwd_elem(float x, float dz, float mu, float 
         dz = yv > 0.f ? dz : 0.f;
     }
     return ca * (dz - cb - xh * cd);
+}
+__device__ __forceinline__ f32x4 bn_fwd_elem4(const f32x4 &x, const f32x4 &mu, const f32x4 &is, const f32x4 &ga, const f32x4 &be,
+                                              int relu) {
+    f32x4 o = (x - mu) * is * ga + be;
+    if (relu) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = o[q] > 0.f ? o[q] : 0.f;
+    }
+    return o;
+}
+// backward, front half: returns xh and masks dz in place (the partial-sum kernels need both)
+__device__ __forceinline__ f32x4 bn_bwd_front4(const f32x4 &x, f32x4 &dz, const f32x4 &mu, const f32x4 &is, const f32x4 &ga,
+                                               const f32x4 &be, int relu) {
+    const f32x4 xh = (x - mu) * is;
+    if (relu) {
+        const f32x4 yv = xh * ga + be;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dz[q] = yv[q] > 0.f ? dz[q] : 0.f;
+    }
+    return xh;
+}
+__device__ __forceinline__ f32x4 bn_bwd_tail4(const f32x4 &dz, const f32x4 &xh, const f32x4 &a, const f32x4 &b, const f32x4 &d) {
+    return a * (dz - b - xh * d);
 }
 #endif

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "../../include/doda_hip.h"
 
 #define DODA_WAVE 64
@@ -16,6 +17,14 @@ static inline hipStream_t as_stream(doda_stream_t s) { return reinterpret_cast<h
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+static inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// integer tuning knob from the environment; unset or empty: the default
+static inline long long env_ll(const char *name, long long dflt) {
+    const char *e = getenv(name);
+    return e && *e ? atoll(e) : dflt;
+}
 
 static inline uint32_t next_pow2(uint32_t x) {
     uint32_t p = 1;

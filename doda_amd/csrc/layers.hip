@@ -21,11 +21,6 @@
 
 namespace {
 
-inline long long env_ll(const char *name, long long dflt) {
-    const char *e = getenv(name);
-    return e && *e ? atoll(e) : dflt;
-}
-
 // ---- standalone BatchNorm ops in the general (strided, split-output) form -------------------------------------------------
 // y[:, 0:c_split) -> y, y[:, c_split:c) -> y2: the two halves of a concatenation's gradient as two dense tensors.
 template <int ESZ, int KIND>
@@ -107,7 +102,6 @@ __global__ __launch_bounds__(256) void lay_stats(const void *__restrict__ x_, un
 }
 
 inline bool chan_ok(int c, int esz) { return c > 0 && c <= PRE_MAX_C && c % (16 / esz) == 0; }
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // PreArgs of a BatchNorm op of the list (BNFWD: kind 1; BNBWD: kind 2 / 3)
 bool pre_of(const doda_cx_op &o, int esz, PreArgs *p) {

@@ -644,41 +644,12 @@ def _esz(t):
     raise RuntimeError("unsupported feature dtype %s" % t.dtype)
 
 
-def bn_relu_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu,
-                num_batches_tracked=None):
-    """-> (y, save_mean, save_invstd).  x: contiguous [m, c] fp32|bf16 on device, c % 4 == 0."""
-    _feat_ok(x, "x")
-    m, c = x.shape
-    y = torch.empty_like(x)
-    if training:
-        save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-    else:
-        save_mean = running_mean.float().contiguous()
-        save_invstd = torch.rsqrt(running_var.float() + eps).contiguous()
-    ws = _ws(lib().doda_bn_workspace_bytes(m, c), x.device)
-    rm = _p(running_mean) if (training and running_mean is not None) else None
-    rv = _p(running_var) if (training and running_var is not None) else None
-    nbt = _p(num_batches_tracked) if (training and num_batches_tracked is not None) else None
-    check(lib().doda_bn_relu_fwd(_p(x), m, c, _esz(x), float(eps), float(momentum), _p(gamma), _p(beta),
-                                 rm, rv, nbt, int(bool(training)), int(bool(relu)), _p(y), _p(save_mean),
-                                 _p(save_invstd), _p(ws), ws.numel(), _stream()), "doda_bn_relu_fwd")
-    return y, save_mean, save_invstd
-
-
-def bn_relu_bwd(x, dy, save_mean, save_invstd, gamma, beta, relu):
-    """-> (dx, dgamma, dbeta) for the training-mode forward above."""
-    _feat_ok(x, "x")
-    _feat_ok(dy, "dy")
-    m, c = x.shape
-    dx = torch.empty_like(x)
-    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
-    ws = _ws(lib().doda_bn_workspace_bytes(m, c), x.device)
-    check(lib().doda_bn_relu_bwd(_p(x), _p(dy), m, c, _esz(x), _p(save_mean), _p(save_invstd),
-                                 _p(gamma), _p(beta), int(bool(relu)), _p(dx), _p(dgamma), _p(dbeta),
-                                 _p(ws), ws.numel(), _stream()), "doda_bn_relu_bwd")
-    return dx, dgamma, dbeta
+def _bn_bwd_out(x):
+    """An [m, c] tensor like x and two fp32 [c] vectors: (dx, dgamma, dbeta) of a backward, (y, save_mean, save_invstd) of a
+    training-mode forward."""
+    c = x.shape[1]
+    return (torch.empty_like(x), torch.empty(c, dtype=torch.float32, device=x.device),
+            torch.empty(c, dtype=torch.float32, device=x.device))
 
 
 def _add_ld(add, m, c, what):
@@ -689,16 +660,52 @@ def _add_ld(add, m, c, what):
     return _p(add), int(add.stride(0))
 
 
+def _bn_bwd_args(what, x, dy, add=None, also=()):
+    """Operand checks of a BatchNorm backward -> (m, c, add's pointer or None, add's row stride in elements)."""
+    _feat_ok(x, "x")
+    _feat_ok(dy, "dy")
+    _need_cuda(*also)
+    m, c = x.shape
+    ap, ld = _add_ld(add, m, c, what) if add is not None else (None, c)
+    return m, c, ap, ld
+
+
+def bn_relu_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu,
+                num_batches_tracked=None):
+    """-> (y, save_mean, save_invstd).  x: contiguous [m, c] fp32|bf16 on device, c % 4 == 0."""
+    _feat_ok(x, "x")
+    m, c = x.shape
+    if training:
+        y, save_mean, save_invstd = _bn_bwd_out(x)
+    else:
+        y = torch.empty_like(x)
+        save_mean = running_mean.float().contiguous()
+        save_invstd = torch.rsqrt(running_var.float() + eps).contiguous()
+    ws = _ws(lib().doda_bn_workspace_bytes(m, c), x.device)
+    rm, rv, nbt = (running_mean, running_var, num_batches_tracked) if training else (None, None, None)
+    check(lib().doda_bn_relu_fwd(_p(x), m, c, _esz(x), float(eps), float(momentum), _p(gamma), _p(beta),
+                                 _p(rm), _p(rv), _p(nbt), int(bool(training)), int(bool(relu)), _p(y), _p(save_mean),
+                                 _p(save_invstd), _p(ws), ws.numel(), _stream()), "doda_bn_relu_fwd")
+    return y, save_mean, save_invstd
+
+
+def bn_relu_bwd(x, dy, save_mean, save_invstd, gamma, beta, relu):
+    """-> (dx, dgamma, dbeta) for the training-mode forward above."""
+    m, c, _, _ = _bn_bwd_args("bn_relu_bwd", x, dy)
+    dx, dgamma, dbeta = _bn_bwd_out(x)
+    ws = _ws(lib().doda_bn_workspace_bytes(m, c), x.device)
+    check(lib().doda_bn_relu_bwd(_p(x), _p(dy), m, c, _esz(x), _p(save_mean), _p(save_invstd),
+                                 _p(gamma), _p(beta), int(bool(relu)), _p(dx), _p(dgamma), _p(dbeta),
+                                 _p(ws), ws.numel(), _stream()), "doda_bn_relu_bwd")
+    return dx, dgamma, dbeta
+
+
 def bn_relu_bwd_add(x, dy, save_mean, save_invstd, gamma, beta, relu, add):
     """bn_relu_bwd with a second gradient of x summed into dx inside the apply pass (doda_bn_relu_bwd_add); `add`
     may be a column slice of a wider matrix (e.g. g[:, :c] of torch.cat's gradient): no copy is made."""
-    _feat_ok(x, "x")
-    _feat_ok(dy, "dy")
-    m, c = x.shape
-    ap, ld = _add_ld(add, m, c, "bn_relu_bwd_add")
-    dx = torch.empty_like(x)
-    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    m, c, _, _ = _bn_bwd_args("bn_relu_bwd_add", x, dy)
+    ap, ld = _add_ld(add, m, c, "bn_relu_bwd_add")      # (not optional here)
+    dx, dgamma, dbeta = _bn_bwd_out(x)
     ws = _ws(lib().doda_bn_workspace_bytes(m, c), x.device)
     check(lib().doda_bn_relu_bwd_add(_p(x), _p(dy), m, c, _esz(x), _p(save_mean), _p(save_invstd), _p(gamma), _p(beta),
                                         int(bool(relu)), ap, ld, _p(dx), _p(dgamma), _p(dbeta), _p(ws), ws.numel(),
@@ -709,14 +716,8 @@ def bn_relu_bwd_add(x, dy, save_mean, save_invstd, gamma, beta, relu, add):
 def bn_relu_bwd_stats(x, dy, stats, save_mean, save_invstd, gamma, beta, relu, add=None):
     """BatchNorm(+ReLU) backward over the (sum dz, sum dz * xhat) rows of a data-grad conv epilogue
     (doda_bn_relu_bwd_stats); add as in bn_relu_bwd_add.  -> (dx [+ add], dgamma, dbeta)."""
-    _feat_ok(x, "x")
-    _feat_ok(dy, "dy")
-    _need_cuda(stats)
-    m, c = x.shape
-    ap, ld = _add_ld(add, m, c, "bn_relu_bwd_stats") if add is not None else (None, c)
-    dx = torch.empty_like(x)
-    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    m, c, ap, ld = _bn_bwd_args("bn_relu_bwd_stats", x, dy, add, also=(stats,))
+    dx, dgamma, dbeta = _bn_bwd_out(x)
     coef = torch.empty(3 * c, dtype=torch.float32, device=x.device)
     check(lib().doda_bn_relu_bwd_stats(_p(x), _p(dy), m, c, _esz(x), _p(stats), stats.shape[0], _p(save_mean),
                                           _p(save_invstd), _p(gamma), _p(beta), int(bool(relu)), ap, ld, _p(dx), _p(dgamma),
@@ -732,29 +733,19 @@ def bn_relu_fwd_totals(x, totals, gamma, beta, running_mean, running_var, moment
     _need_cuda(totals)
     m, c = x.shape
     c_a = int(totals.shape[2]) * 4
-    y = torch.empty_like(x)
-    save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
-    save_invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-    check(lib().doda_bn_relu_fwd_totals(_p(x), m, c, _esz(x), _p(totals), _p(totals_b) if totals_b is not None else None, c_a,
-                                        float(eps), float(momentum), _p(gamma), _p(beta),
-                                        _p(running_mean) if running_mean is not None else None,
-                                        _p(running_var) if running_var is not None else None,
-                                        _p(num_batches_tracked) if num_batches_tracked is not None else None, int(bool(relu)),
-                                        _p(y), _p(save_mean), _p(save_invstd), _stream()), "doda_bn_relu_fwd_totals")
+    y, save_mean, save_invstd = _bn_bwd_out(x)
+    check(lib().doda_bn_relu_fwd_totals(_p(x), m, c, _esz(x), _p(totals), _p(totals_b), c_a, float(eps), float(momentum),
+                                        _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(num_batches_tracked),
+                                        int(bool(relu)), _p(y), _p(save_mean), _p(save_invstd), _stream()),
+          "doda_bn_relu_fwd_totals")
     return y, save_mean, save_invstd
 
 
 def bn_relu_bwd_totals(x, dy, totals, save_mean, save_invstd, gamma, beta, relu, add=None):
     """BatchNorm(+ReLU) backward over the fp64 totals of a data-grad conv epilogue (doda_bn_relu_bwd_totals, ONE launch).
     -> (dx [+ add], dgamma, dbeta)."""
-    _feat_ok(x, "x")
-    _feat_ok(dy, "dy")
-    _need_cuda(totals)
-    m, c = x.shape
-    ap, ld = _add_ld(add, m, c, "bn_relu_bwd_totals") if add is not None else (None, c)
-    dx = torch.empty_like(x)
-    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    m, c, ap, ld = _bn_bwd_args("bn_relu_bwd_totals", x, dy, add, also=(totals,))
+    dx, dgamma, dbeta = _bn_bwd_out(x)
     check(lib().doda_bn_relu_bwd_totals(_p(x), _p(dy), m, c, _esz(x), _p(totals), _p(save_mean), _p(save_invstd), _p(gamma),
                                         _p(beta), int(bool(relu)), ap, ld, _p(dx), _p(dgamma), _p(dbeta), _stream()),
           "doda_bn_relu_bwd_totals")

@@ -1,5 +1,5 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h, include/doda_loss.h).
+include/doda_aug.h, include/doda_loss.h, include/doda_eval.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -161,6 +161,24 @@ LOSS_SIGNATURES = {
 LOSS_SYMBOLS = tuple(LOSS_SIGNATURES)
 LOSS_ABI_VERSION = 1  # include/doda_loss.h DODA_LOSS_ABI_VERSION
 LOVASZ_MAX_CLASSES, LOVASZ_MAX_POINTS_PER_VOXEL = 32, 65535
+
+
+# name -> (restype, argtypes); mirrors include/doda_eval.h (the full-cloud evaluation companion ABI, same library)
+class EvalScene(C.Structure):   # doda_eval_scene
+    _fields_ = [("n_end", c_i32), ("m_end", c_i32), ("cell_base", c_i32), ("dims", c_i32 * 3), ("origin", c_f32 * 3),
+                ("side", c_f32), ("inv_side", c_f32)]
+
+
+EVAL_SIGNATURES = {
+    "doda_eval_abi_version": (c_i32, []),
+    "doda_eval_nn": (c_i32, [c_vp, c_vp, c_i64, c_vp, C.POINTER(EvalScene), c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "doda_eval_score_blocks": (c_i32, [c_i64]),
+    "doda_eval_score": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                c_vp, c_i32, c_vp]),
+}
+EVAL_SYMBOLS = tuple(EVAL_SIGNATURES)
+EVAL_ABI_VERSION = 1  # include/doda_eval.h DODA_EVAL_ABI_VERSION
+EVAL_MAX_SCENES, EVAL_MAX_CELLS, EVAL_MAX_CLASSES = 32, 1 << 21, 32
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -170,7 +188,8 @@ _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (SELFTRAIN_SIGNATURES, "doda_st_abi_version", ST_ABI_VERSION, "self-training ABI"),
          (MIX_SIGNATURES, "doda_mix_abi_version", MIX_ABI_VERSION, "cuboid-mixing ABI"),
          (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"),
-         (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"))
+         (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"),
+         (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"))
 
 _lib = None
 

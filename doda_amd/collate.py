@@ -30,6 +30,7 @@ def collate_device(items, device, batch_size=None, voxel_mode=4, full_scale=(128
     locs, locs_float, labels, ids, offsets = [], [], [], [], [0]
     extra_cat = {"selected_idx": [], "mask1": [], "mask2": []}
     mix_idx, tar_tail_splits, tar_ratio = [], [], []
+    locs_float_all, labels_all, offsets_all = [], [], [0]      # the full clouds of an evaluation batch (loader.EvalScenes)
     for i, item in enumerate(items):
         xyz, xyz_mid, label, idx, *others = item
         n = xyz.shape[0]
@@ -50,6 +51,10 @@ def collate_device(items, device, batch_size=None, voxel_mode=4, full_scale=(128
                 tar_tail_splits.extend(o["tar_tail_splits"])
             if "tar_splits_class_ratio" in o:
                 tar_ratio.append(o["tar_splits_class_ratio"])
+            if "xyz_mid_all" in o:
+                locs_float_all.append(_dev(o["xyz_mid_all"], device, torch.float32))
+                labels_all.append(_dev(o["labels_all"], device, torch.int64))
+                offsets_all.append(offsets_all[-1] + o["xyz_mid_all"].shape[0])
     locs = torch.cat(locs, 0).contiguous()
     locs_float = torch.cat(locs_float, 0)
     labels = torch.cat(labels, 0)
@@ -70,6 +75,12 @@ def collate_device(items, device, batch_size=None, voxel_mode=4, full_scale=(128
     for r in tar_ratio:
         ratio = ratio + r
     out["tar_splits_class_ratio"] = ratio
+    if locs_float_all:      # reference dataset/s3dis.py:96-130 (test_collate_fn): the same three extra keys, dtypes and shapes
+        if len(locs_float_all) != len(items):
+            raise ValueError("collate_device: every item of a batch carries its full cloud, or none does")
+        out["locs_float_all"] = torch.cat(locs_float_all, 0)
+        out["labels_all"] = torch.cat(labels_all, 0)
+        out["offsets_all"] = torch.tensor(offsets_all, dtype=torch.int32)
     return out
 
 

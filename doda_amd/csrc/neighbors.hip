@@ -8,15 +8,10 @@
 // exact ties resolve identically (this file is compiled with -ffp-contract=off and uses
 // explicit __fmul_rn/__fadd_rn).
 #include "common.hpp"
+#include "neighbors_common.hpp"      // dist2_rn: one copy, shared with the grid search of eval.hip
 
 namespace {
 constexpr int NQ_BLOCK = 256;
-
-__device__ __forceinline__ float dist2_rn(float ax, float ay, float az, float bx, float by,
-                                          float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 
 // Block-wide candidate sweep.  Each lane has its own [start,end) candidate range; the block
 // walks the union range tile by tile and calls visit(i, x, y, z) for candidates in the lane's

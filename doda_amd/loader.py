@@ -68,6 +68,17 @@ def remove_cache(cache_dir):
     shutil.rmtree(cache_dir, ignore_errors=True)
 
 
+def _voxel_coords(m, voxel_scale):
+    """int32 [n, 3]: xyz_mid * voxel_scale - its minimum, truncated (as the reference's astype: dataset/scannet.py:76-78)."""
+    q = np.empty((m.shape[0], 3), dtype=np.int32)
+    for k in range(3):
+        col = m[:, k] * np.float32(voxel_scale)
+        if col.size:
+            col -= col.min()
+        q[:, k] = col
+    return q
+
+
 class SyntheticScenes(torch.utils.data.Dataset):
     """item i of epoch e -> (xyz int64 [n,3] voxel coordinates, xyz_mid float32 [n,3], labels int64 [n], id): base scene
     i % n_base under a seeded rigid augmentation.  Picklable (paths + numbers only): workers open the cache files."""
@@ -121,15 +132,55 @@ class SyntheticScenes(torch.utils.data.Dataset):
             np.add(xt[2], jit[2], out=m[:, 2])
         else:
             m[:, 0], m[:, 1], m[:, 2] = xt[0], xt[1], xt[2]
-        q = np.empty((n, 3), dtype=np.int32)
-        for k in range(3):
-            col = m[:, k] * np.float32(self.voxel_scale)
-            col -= col.min()
-            q[:, k] = col          # (truncation, as the reference's astype: dataset/scannet.py:78)
+        q = _voxel_coords(m, self.voxel_scale)
         # tensors (the DataLoader hands tensors over in shared memory; numpy arrays would be pickled through a pipe) in the
         # narrowest types that hold the values: 28 instead of 56 bytes per point cross the process boundary and PCIe —
         # doda_amd.collate widens them to the reference's int64 / float32 ON THE DEVICE
         return torch.from_numpy(q), torch.from_numpy(m), torch.from_numpy(labels), int(i)
+
+
+def subsample_indices(n, ds_scale, seed):
+    """The processed cloud of a scene of n points under DATA_PROCESSOR.downsampling_scale (reference dataset/dataset.py:74-77): the
+    first int(n / ds_scale) indices of a permutation, sorted.  Seeded (the reference draws from the global numpy state)."""
+    idx = np.random.default_rng(seed).permutation(int(n))[:int(n / ds_scale)]
+    idx.sort()
+    return idx
+
+
+class EvalScenes:
+    """Evaluation item source over a split's base scenes, unaugmented and unshuffled: item k is base scene k as
+    SyntheticScenes(augment=False) returns it.  With downsampling_scale > 1 (reference dataset/s3dis.py:54-88) the item is the
+    scene's SUBSAMPLE — seeded by the scene's name, so it depends neither on batching nor on the rank count — and carries the full
+    cloud in a fifth entry {"xyz_mid_all", "labels_all"}, which doda_amd.collate turns into the `*_all` keys."""
+
+    def __init__(self, paths, voxel_scale, downsampling_scale=1, seed=0):
+        self.scenes = SyntheticScenes(paths, len(paths), voxel_scale, seed=0, augment=False)
+        self.paths, self.voxel_scale, self.ds, self.seed = list(paths), int(voxel_scale), downsampling_scale, int(seed)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def subsample(self, k):
+        """Sorted indices of base scene k's processed points in its full cloud."""
+        import zlib
+        n = self.scenes._base(k)[0].shape[1]
+        name = os.path.basename(str(self.paths[k])).split(".")[0]
+        return subsample_indices(n, self.ds, (self.seed * 1000003 + zlib.crc32(name.encode())) & 0x7fffffff)
+
+    def __getitem__(self, k):
+        if not self.ds or self.ds <= 1:
+            return self.scenes[k]
+        xt, labels = self.scenes._base(k)
+        sub = self.subsample(k)
+        m_all = np.ascontiguousarray(xt.T)
+        m = np.ascontiguousarray(m_all[sub])
+        return (torch.from_numpy(_voxel_coords(m, self.voxel_scale)), torch.from_numpy(m), torch.from_numpy(labels[sub]), int(k),
+                {"xyz_mid_all": torch.from_numpy(m_all), "labels_all": torch.from_numpy(labels)})
+
+    def batches(self, groups):
+        """groups: lists of base scene indices (doda_amd.test.shard_batches) -> one list of items per group."""
+        for ids in groups:
+            yield [self[k] for k in ids]
 
 
 def _identity(items):

@@ -1024,6 +1024,144 @@ def st_label(store_cls, store_conf, thres32, ignore):
 
 
 # ---- optimizer step -------------------------------------------------------------------------------
+# ---- full-cloud evaluation (include/doda_eval.h, csrc/eval.hip) ---------------------------------------------------
+class EvalTable:
+    """The cell table of a batch's processed points (include/doda_eval.h): `scenes` (ctypes array of doda_eval_scene, m_end still
+    unset), the device tensors order / xyz_sorted / cell_start and the per-scene grid tensors the keys were made from."""
+
+    def __init__(self, scenes, ends, order, xyz_sorted, cell_start, grid):
+        self.scenes, self.ends, self.order, self.xyz_sorted, self.cell_start, self.grid = scenes, ends, order, xyz_sorted, cell_start, grid
+
+
+def _eval_ends(offset, total, what):
+    ends = [int(v) for v in offset.cpu().tolist()]
+    if not ends or any(b < a for a, b in zip([0] + ends[:-1], ends)) or ends[-1] != total:
+        raise RuntimeError("%s: END offsets, non-decreasing, the last one the row count" % what)
+    return ends
+
+
+def _eval_batch_index(ends, device):
+    sizes = [e - s for s, e in zip([0] + ends[:-1], ends)]
+    return torch.repeat_interleave(torch.arange(len(sizes), device=device), torch.tensor(sizes, device=device), output_size=ends[-1])
+
+
+def _eval_keys(xyz, bidx, grid):
+    """int64 [rows]: the cell id of every point — per axis clamp(floor((x - origin) * inv_side), 0, dims - 1) in fp32, the
+    expression eval.hip's eval_cell restates (one rounded subtraction, one rounded multiplication), then cell_base + (cx ny + cy) nz + cz."""
+    origin, inv, dims, base = grid
+    c = ((xyz - origin[bidx]) * inv[bidx][:, None]).floor()
+    c = torch.nan_to_num(c, nan=0.0, posinf=3.0e38, neginf=-3.0e38).clamp(min=0.0)
+    d = dims[bidx]
+    c = torch.minimum(c, (d - 1).to(torch.float32)).to(torch.int64)
+    return base[bidx] + (c[:, 0] * d[:, 1] + c[:, 1]) * d[:, 2] + c[:, 2]
+
+
+def eval_table(xyz, offset, cell_side, max_cells=None):
+    """The cell table of the processed points xyz float32 [n, 3] with END offsets int32 [B] (device tensors), built with torch on the
+    device: per scene a grid from its bounding box with cells of `cell_side` metres — doubled on the host until the scene's grid has
+    at most max_cells (DODA_EVAL_MAX_CELLS) cells —, a stable sort of the cell ids, bincount and cumsum.  One read-back (the offsets
+    and the per-scene bounds)."""
+    from ._lib import EVAL_MAX_CELLS, EVAL_MAX_SCENES, EvalScene
+    _need_cuda(xyz, offset)
+    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3 or offset.dtype != torch.int32 or not float(cell_side) > 0.0:
+        raise RuntimeError("eval_table: xyz float32 [n, 3], offset int32 [B], cell_side > 0")
+    max_cells = EVAL_MAX_CELLS if max_cells is None else min(int(max_cells), EVAL_MAX_CELLS)
+    xyz = xyz.contiguous()
+    n, dev = xyz.shape[0], xyz.device
+    ends = _eval_ends(offset, n, "eval_table")
+    nb = len(ends)
+    if nb > EVAL_MAX_SCENES:
+        raise DodaNativeError("eval_table: %d scenes in one batch (at most %d)" % (nb, EVAL_MAX_SCENES))
+    starts = [0] + ends[:-1]
+    bounds = torch.stack([torch.cat((xyz[s:e].amin(0), xyz[s:e].amax(0))) if e > s else xyz.new_zeros(6)
+                          for s, e in zip(starts, ends)]).cpu().numpy()
+    if not np.isfinite(bounds).all():
+        raise RuntimeError("eval_table: non-finite coordinates")
+    scenes = (EvalScene * nb)()
+    base = 0
+    for b in range(nb):
+        lo, hi = bounds[b, :3].astype(np.float64), bounds[b, 3:].astype(np.float64)
+        side = np.float32(cell_side)
+        while True:
+            dims = np.floor((hi - lo) / float(side)).astype(np.int64) + 1
+            if int(dims.prod()) <= max_cells:
+                break
+            side = np.float32(side * np.float32(2.0))
+        sc = scenes[b]
+        sc.n_end, sc.m_end, sc.cell_base = ends[b], 0, base
+        for k in range(3):
+            sc.dims[k], sc.origin[k] = int(dims[k]), float(bounds[b, k])
+        sc.side, sc.inv_side = float(side), float(np.float32(1.0) / side)
+        base += int(dims.prod())
+    grid = (torch.tensor([[s.origin[k] for k in range(3)] for s in scenes], dtype=torch.float32, device=dev),
+            torch.tensor([s.inv_side for s in scenes], dtype=torch.float32, device=dev),
+            torch.tensor([[s.dims[k] for k in range(3)] for s in scenes], dtype=torch.int64, device=dev),
+            torch.tensor([s.cell_base for s in scenes], dtype=torch.int64, device=dev))
+    key = _eval_keys(xyz, _eval_batch_index(ends, dev), grid)
+    order = torch.sort(key, stable=True)[1]
+    cell_start = torch.zeros(base + 1, dtype=torch.int32, device=dev)
+    cell_start[1:] = torch.cumsum(torch.bincount(key, minlength=base), 0)
+    return EvalTable(scenes, ends, order.to(torch.int32), xyz[order].contiguous(), cell_start, grid)
+
+
+def eval_nn(xyz, new_xyz, offset, new_offset, cell_side=0.08, table=None, sort_queries=True):
+    """(idx int32 [m], dist2 float32 [m]): for every row of new_xyz the nearest row of xyz of its scene, bit-identical to
+    knnquery(nsample = 1) on the same tensors (doda_eval_nn over eval_table's grid).  offset / new_offset: END offsets int32 [B].
+    sort_queries: hand the queries out in cell order (a wave then walks the same cells); the result does not depend on it."""
+    _need_cuda(xyz, new_xyz, offset, new_offset)
+    if new_xyz.dtype != torch.float32 or new_xyz.dim() != 2 or new_xyz.shape[1] != 3 or new_offset.dtype != torch.int32:
+        raise RuntimeError("eval_nn: new_xyz float32 [m, 3], new_offset int32 [B]")
+    if table is None:
+        table = eval_table(xyz, offset, cell_side)
+    new_xyz = new_xyz.contiguous()
+    m, dev = new_xyz.shape[0], new_xyz.device
+    new_ends = _eval_ends(new_offset, m, "eval_nn")
+    if len(new_ends) != len(table.ends):
+        raise RuntimeError("eval_nn: offset and new_offset name the same scenes")
+    scenes = type(table.scenes)()
+    C.memmove(scenes, table.scenes, C.sizeof(scenes))
+    for b, e in enumerate(new_ends):
+        scenes[b].m_end = e
+    qorder = None
+    if sort_queries and m > 0:
+        qorder = torch.argsort(_eval_keys(new_xyz, _eval_batch_index(new_ends, dev), table.grid)).to(torch.int32)
+    idx = torch.empty(m, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(m, dtype=torch.float32, device=dev)
+    check(lib().doda_eval_nn(_p(table.xyz_sorted), _p(table.order), table.order.numel(), _p(table.cell_start), scenes, len(new_ends),
+                             _p(new_xyz), _p(qorder), m, _p(idx), _p(dist2), _stream()), "doda_eval_nn")
+    return idx, dist2
+
+
+def eval_score(feats, weight, bias, p2v, idx, labels_all, ignore_index, hist, want_pred=True):
+    """Full-cloud scoring without the score matrix (doda_eval_score): for full point i the voxel v = p2v[idx[i]] (idx None: the
+    identity).  hist int64 [3, n_cls] += (intersection, prediction area, target area) over the valid points.
+    -> (out float64 [2] = {sum of the valid points' cross-entropy, their number}, pred_all uint8 [m] = the voxels' argmax, or None)."""
+    feats, weight, bias, _, _ = _head_args("eval_score", feats, weight, bias)
+    _need_cuda(p2v, labels_all, hist)
+    n_cls = weight.shape[0]
+    if (weight.dim() != 2 or weight.shape[1] != feats.shape[1] or p2v.dtype != torch.int32 or labels_all.dtype != torch.int64
+            or hist.dtype != torch.int64 or tuple(hist.shape) != (3, n_cls) or not hist.is_contiguous()
+            or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != n_cls or not bias.is_cuda))):
+        raise RuntimeError("eval_score: weight float32 [n_cls, c], bias float32 [n_cls], p2v int32 [n], labels int64 [m], hist int64 [3, n_cls]")
+    p2v, labels_all = p2v.contiguous(), labels_all.contiguous()
+    m = labels_all.shape[0]
+    if idx is not None:
+        _need_cuda(idx)
+        if idx.dtype != torch.int32 or idx.shape[0] != m:
+            raise RuntimeError("eval_score: idx int32 [m], one per label")
+        idx = idx.contiguous()
+    elif p2v.shape[0] != m:
+        raise RuntimeError("eval_score: without idx, one p2v entry per label")
+    nb = int(lib().doda_eval_score_blocks(m))
+    out = torch.empty(2, dtype=torch.float64, device=feats.device)
+    ws = torch.empty(2 * nb, dtype=torch.float64, device=feats.device)
+    pred = torch.empty(m, dtype=torch.uint8, device=feats.device) if want_pred else None
+    check(lib().doda_eval_score(_p(feats), feats.shape[0], feats.shape[1], feats.element_size(), _p(weight), _p(bias), n_cls, _p(p2v),
+                                p2v.shape[0], _p(idx), _p(labels_all), m, int(ignore_index), _p(pred), _p(hist), _p(out), _p(ws), nb,
+                                _stream()), "doda_eval_score")
+    return out, pred
+
+
 class _SgdTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("n", C.c_int64),
                 ("first_step", C.c_int32), ("reserved", C.c_int32)]

@@ -107,6 +107,12 @@ def write_scene_labels(pseudo_dir, name, labels):
     """<pseudo_dir>/txt/<name>.txt, one `%d` per line; an existing file is kept (util/common_utils.py:304-313)."""
     os.makedirs(txt_dir(pseudo_dir), exist_ok=True)
     path = os.path.join(txt_dir(pseudo_dir), name + ".txt")
+    return write_label_file(path, labels)
+
+
+def write_label_file(path, labels):
+    """One `%d` per line into `path`, written under a temporary name and renamed; an existing file is kept (-> False).  Shared with
+    the evaluation entry point's --save_to_file (doda_amd.test)."""
     if os.path.exists(path):
         return False
     tmp = path + ".tmp.%d" % os.getpid()

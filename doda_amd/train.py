@@ -543,9 +543,8 @@ class Trainer:
     @torch.no_grad()
     def validate_epoch(self, epoch):
         from .dsnorm import set_ds_target
-        from .model import criterion_of, voxelize_and_run
+        from .evaluate import score_batch
         cfg = self.cfg
-        criterion = criterion_of(self.model)      # OPTIMIZATION.loss: cross_entropy (default) | lovasz
         self.model.eval()
         if self.reducer is not None:
             self.reducer.sync_buffers()   # evaluation with rank 0's running statistics on every rank
@@ -553,10 +552,7 @@ class Trainer:
             self.model.apply(set_ds_target)
         meters = DeviceMeters(cfg.COMMON_CLASSES.n_classes, cfg.DATA_CONFIG.DATA_CLASS.ignore_label, self.device)
         for batch, pyramid in self._batches(epoch, "val"):
-            scores = voxelize_and_run(cfg, self.model, batch, self.device, feature_dtype=self.fdt,
-                                      inputs_ready=True, pyramid=pyramid)
-            loss = criterion(scores, batch["labels"], ignore_index=cfg.DATA_CONFIG.DATA_CLASS.ignore_label)
-            meters.update(loss, scores.argmax(1), batch["labels"])
+            score_batch(cfg, self.model, batch, meters, self.device, self.fdt, pyramid=pyramid)      # (OPTIMIZATION.loss's criterion)
         meters.all_reduce()
         l, miou, macc, allacc, iou = meters.read()
         self.log("Val result: mIoU/mAcc/allAcc %.4f/%.4f/%.4f." % (miou, macc, allacc))

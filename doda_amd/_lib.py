@@ -1,5 +1,5 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h, include/doda_loss.h, include/doda_eval.h).
+include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -179,6 +179,18 @@ EVAL_SIGNATURES = {
 EVAL_SYMBOLS = tuple(EVAL_SIGNATURES)
 EVAL_ABI_VERSION = 1  # include/doda_eval.h DODA_EVAL_ABI_VERSION
 EVAL_MAX_SCENES, EVAL_MAX_CELLS, EVAL_MAX_CLASSES = 32, 1 << 21, 32
+
+# name -> (restype, argtypes); mirrors include/doda_subsample.h (the training-subsample companion ABI, same library)
+c_u64p = C.POINTER(C.c_uint64)
+SUBSAMPLE_SIGNATURES = {
+    "doda_subsample_abi_version": (c_i32, []),
+    "doda_subsample_workspace_bytes": (c_sz, [c_i64p, c_i32]),
+    "doda_subsample_draw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64p, c_i32, c_i32p, c_u64p, C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_sz, c_vp]),
+}
+SUBSAMPLE_SYMBOLS = tuple(SUBSAMPLE_SIGNATURES)
+SUBSAMPLE_ABI_VERSION = 1  # include/doda_subsample.h DODA_SUBSAMPLE_ABI_VERSION
+SUBSAMPLE_MAX_SEGMENTS, SUBSAMPLE_CHUNK = 64, 1024
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -189,7 +201,8 @@ _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (MIX_SIGNATURES, "doda_mix_abi_version", MIX_ABI_VERSION, "cuboid-mixing ABI"),
          (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"),
          (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"),
-         (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"))
+         (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"),
+         (SUBSAMPLE_SIGNATURES, "doda_subsample_abi_version", SUBSAMPLE_ABI_VERSION, "subsample ABI"))
 
 _lib = None
 

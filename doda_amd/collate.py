@@ -94,13 +94,18 @@ def collate_device_concat(hb, device, voxel_mode=4):
     labels = hb["labels32"].to(device, non_blocking=True).to(torch.int64)
     batch_size = hb["offsets"].numel() - 1
     voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, batch_size, voxel_mode)
-    return {"locs": locs, "voxel_locs": voxel_locs, "p2v_map": p2v_map, "v2p_map": v2p_map,
+    out = {"locs": locs, "voxel_locs": voxel_locs, "p2v_map": p2v_map, "v2p_map": v2p_map,
             "v2p_map_t": v2p_map[:, 1:].t().contiguous(),
             "locs_float": locs_float, "feats": locs_float.clone(), "labels": labels,
             "offsets": hb["offsets"], "spatial_shape": hb["spatial_shape"], "id": hb["id"],
             # (filled by the cuboid-mixing loader, doda_amd.loader.MixedDeviceScenes; empty otherwise)
             "mix_idx": [], "tar_tail_splits": hb.get("tar_tail_splits", []), "selected_idx": [], "mask1": hb.get("mask1", []),
             "mask2": hb.get("mask2", []), "tar_splits_class_ratio": hb.get("tar_splits_class_ratio", [])}
+    if "offsets_all" in hb:      # the full clouds of an evaluation batch (doda_amd.loader.DeviceScenes with a downsampling_scale)
+        out["locs_float_all"] = hb["locs_float_all"].to(device, non_blocking=True)
+        out["labels_all"] = hb["labels_all"].to(device, non_blocking=True).to(torch.int64)
+        out["offsets_all"] = hb["offsets_all"]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -139,6 +139,11 @@ class SyntheticScenes(torch.utils.data.Dataset):
         return torch.from_numpy(q), torch.from_numpy(m), torch.from_numpy(labels), int(i)
 
 
+def subsample_count(n, ds_scale):
+    """Points kept of a scene of n points: the reference's int(n / ds) (dataset/dataset.py:76)."""
+    return int(int(n) / ds_scale)
+
+
 def subsample_indices(n, ds_scale, seed):
     """The processed cloud of a scene of n points under DATA_PROCESSOR.downsampling_scale (reference dataset/dataset.py:74-77): the
     first int(n / ds_scale) indices of a permutation, sorted.  Seeded (the reference draws from the global numpy state)."""
@@ -363,10 +368,22 @@ class DeviceScenes:
     concatenation of dataset/dataset.py:121-187 — or, with a DATA_AUG.aug_list in the dataset config (`aug_cfg`), the reference's
     scene_aug / elastic / crop (doda_amd.aug).  Iterating yields the dictionary host_collate() makes, on the device.
     Same sampling order as EpochSampler; the augmentation draws come from a seeded DEVICE generator (not the worker path's
-    numpy streams: the two loaders produce different, equally distributed batches)."""
+    numpy streams: the two loaders produce different, equally distributed batches).
+
+    downsampling_scale (DATA_PROCESSOR.downsampling_scale, reference dataset/s3dis.py:48-63, dataset/dataset.py:73-77) above 1:
+    a training split (augment=True) makes every item a fresh random subsample of int(n / scale) points of its scene, drawn on the
+    device BEFORE any augmentation (ops.subsample, seeded by the loader's seed and the item id; labels, set_labels' included, are
+    picked with the points); an evaluation split (augment=False) takes EvalScenes' subsample — seeded by the scene's name and
+    `subsample_seed`, computed once per base scene — and its batches carry the full clouds as locs_float_all / labels_all /
+    offsets_all (doda_amd.evaluate scores those).  A scale of 1 or less: nothing of this runs."""
+
+    # The draw of a training split: True = doda_subsample_draw, False = the same draw (the same bits) with torch ops on the device.
+    # The native route becomes the default once tools/subsamplebench.py has shown its median below the torch route's lower quartile
+    # on an MI355X; that run does not exist yet (DESIGN §17 "Measured"), so the torch route stays the default.
+    SUBSAMPLE_NATIVE = False
 
     def __init__(self, paths, length, voxel_scale, seed, batch_size, rank, world, device, augment=True, shuffle=True,
-                 full_scale0=128, aug_cfg=None):
+                 full_scale0=128, aug_cfg=None, downsampling_scale=1, subsample_seed=0):
         self.device = torch.device(device)
         self.length, self.voxel_scale, self.seed, self.bs, self.augment = int(length), float(voxel_scale), int(seed), batch_size, augment
         self.full_scale0 = full_scale0
@@ -380,6 +397,15 @@ class DeviceScenes:
                 self.xyz.append(torch.from_numpy(np.ascontiguousarray(f["xyz_mid"], dtype=np.float32)).to(self.device))
                 self.lab.append(torch.from_numpy(f["labels"].astype(np.int32)).to(self.device))
         self.gen = torch.Generator(device=self.device)
+        self.ds = float(downsampling_scale) if (downsampling_scale and downsampling_scale > 1) else None
+        self.eval_sub = None
+        if self.ds is not None:
+            for p, x in zip(paths, self.xyz):
+                if subsample_count(x.shape[0], self.ds) == 0:
+                    raise ValueError("downsampling_scale %g leaves no point of scene %s (%d points)" % (self.ds, p, x.shape[0]))
+            if not augment:
+                src = EvalScenes(paths, voxel_scale, self.ds, seed=subsample_seed)
+                self.eval_sub = [torch.from_numpy(src.subsample(k)).to(self.device) for k in range(len(paths))]
 
     def set_labels(self, labels):
         """Replace the base scenes' labels: one device int32 tensor [points of base scene k] per base scene (pseudo labels)."""
@@ -403,7 +429,10 @@ class DeviceScenes:
         if self.aug_cfg is not None:
             return self._redrawn(self._augmented, ids)
         m, labels, offsets, bidx = self._rigid(ids)
-        return self._finish(m, labels, offsets, bidx, ids)
+        out = self._finish(m, labels, offsets, bidx, ids)
+        if self.eval_sub is not None:
+            out.update(self._full_clouds(ids))
+        return out
 
     def _redrawn(self, make, ids):
         """make(ids), with a sample that the augmentation left without points drawn again (reference dataset/scannet.py:72-73:
@@ -429,12 +458,33 @@ class DeviceScenes:
         return out
 
     def _concat(self, ids):
-        """The base scenes of the items `ids` concatenated: (xyz_mid [N, 3] float32, labels, offsets)."""
+        """The scenes of the items `ids` concatenated: (xyz_mid [N, 3] float32, labels, offsets) — with a downsampling_scale, their
+        subsamples (what every later stage sees, as in the reference)."""
         base = [(i % self.length) % len(self.xyz) for i in ids]
+        if self.eval_sub is not None:
+            xs, ls = [self.xyz[k][self.eval_sub[k]] for k in base], [self.lab[k][self.eval_sub[k]] for k in base]
+        else:
+            xs, ls = [self.xyz[k] for k in base], [self.lab[k] for k in base]
         offsets = [0]
+        for x in xs:
+            offsets.append(offsets[-1] + x.shape[0])
+        x, labels = torch.cat(xs, 0), torch.cat(ls, 0)
+        if self.ds is not None and self.eval_sub is None:
+            from . import ops
+            ks = [subsample_count(offsets[b + 1] - offsets[b], self.ds) for b in range(len(base))]
+            seeds = [(self.seed * 1000003 + 19 * int(i) + 11) & 0x7fffffffffffffff for i in ids]
+            draw = ops.subsample if self.SUBSAMPLE_NATIVE else ops.subsample_torch
+            x, labels, _, offsets = draw(x, labels, offsets, ks, seeds)
+        return x, labels, offsets
+
+    def _full_clouds(self, ids):
+        """The three keys of an evaluation batch whose processed cloud is a subsample (reference dataset/s3dis.py:96-130)."""
+        base = [(i % self.length) % len(self.xyz) for i in ids]
+        offsets_all = [0]
         for k in base:
-            offsets.append(offsets[-1] + self.xyz[k].shape[0])
-        return torch.cat([self.xyz[k] for k in base], 0), torch.cat([self.lab[k] for k in base], 0), offsets
+            offsets_all.append(offsets_all[-1] + self.xyz[k].shape[0])
+        return {"locs_float_all": torch.cat([self.xyz[k] for k in base], 0), "labels_all": torch.cat([self.lab[k] for k in base], 0).long(),
+                "offsets_all": torch.tensor(offsets_all, dtype=torch.int32)}
 
     def _batch_index(self, offsets):
         """[N]: the sample b of every point of a batch with these offsets."""
@@ -486,13 +536,15 @@ class MixedDeviceScenes(DeviceScenes):
     loader thread and stream."""
 
     def __init__(self, paths, source_paths, length, voxel_scale, seed, batch_size, rank, world, device, tacm_cfg, split_sampler,
-                 augment=True, shuffle=True, full_scale0=128, source_seed=None, aug_cfg=None):
+                 augment=True, shuffle=True, full_scale0=128, source_seed=None, aug_cfg=None, downsampling_scale=1,
+                 source_downsampling_scale=1):
         super().__init__(paths, length, voxel_scale, seed, batch_size, rank, world, device, augment=augment, shuffle=shuffle,
-                         full_scale0=full_scale0)
+                         full_scale0=full_scale0, downsampling_scale=downsampling_scale)
         # the list every mixed sample goes through (reference dataset/mix_dataset.py:18), on the device (doda_amd.aug)
         self.mix_aug_cfg = aug_cfg.with_list(["elastic", "crop", "shuffle"]) if (aug_cfg is not None and aug_cfg.enabled and augment) else None
         self.source = DeviceScenes(source_paths, len(source_paths), voxel_scale, seed + 1 if source_seed is None else source_seed,
-                                   batch_size, rank, world, device, augment=augment, shuffle=False, full_scale0=full_scale0)
+                                   batch_size, rank, world, device, augment=augment, shuffle=False, full_scale0=full_scale0,
+                                   downsampling_scale=source_downsampling_scale)
         self.tacm_cfg, self.split_sampler = tacm_cfg, split_sampler
 
     @torch.no_grad()

@@ -1023,6 +1023,83 @@ def st_label(store_cls, store_conf, thres32, ignore):
     return labels, kept
 
 
+# ---- training subsample (include/doda_subsample.h, csrc/subsample.hip) ----------------------------------------------
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def _mulhilo32(a, b):
+    """(high, low) 32-bit halves of the constant a times the int64 tensor b (values below 2^32), in int64 arithmetic."""
+    p0, p1 = a * (b & 0xFFFF), a * (b >> 16)
+    t = p1 + (p0 >> 16)
+    return t >> 16, ((t & 0xFFFF) << 16) | (p0 & 0xFFFF)
+
+
+def subsample_keys(seed, n, device, key_mask=0xffffffff):
+    """int64 [n]: the keys of points 0 .. n - 1 under `seed` — csrc/subsample_key.hpp (Philox-4x32-10, counter (j, 0, 0, 0), key =
+    the seed's two halves, output word 0) restated with torch integer ops on any device."""
+    c0 = torch.arange(n, dtype=torch.int64, device=device)
+    c1, c2, c3 = torch.zeros_like(c0), torch.zeros_like(c0), torch.zeros_like(c0)
+    k0, k1 = int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & 0xffffffff, (k1 + _PHILOX_W1) & 0xffffffff
+    return c0 & int(key_mask)
+
+
+def _subsample_args(xyz, labels, offsets, ks, seeds):
+    offsets, ks, seeds = [int(v) for v in offsets], [int(v) for v in ks], [int(v) & 0xffffffffffffffff for v in seeds]
+    n_seg = len(offsets) - 1
+    if n_seg < 1 or len(ks) != n_seg or len(seeds) != n_seg:
+        raise RuntimeError("subsample: n_seg + 1 offsets, n_seg counts, n_seg seeds")
+    if (xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3 or labels.dtype != torch.int32
+            or labels.shape != (xyz.shape[0],) or offsets[-1] != xyz.shape[0] or labels.device != xyz.device):
+        raise RuntimeError("subsample: xyz float32 [N, 3], labels int32 [N], offsets[-1] = N")
+    offsets_s = [0]
+    for k in ks:
+        offsets_s.append(offsets_s[-1] + k)
+    return offsets, ks, seeds, n_seg, offsets_s
+
+
+def subsample_torch(xyz, labels, offsets, ks, seeds, key_mask=0xffffffff):
+    """subsample() with torch ops on the tensors' device (any device): the same outputs bit for bit.  Per segment one sort of
+    key * 2^31 + index, the first k indices sorted again."""
+    offsets, ks, seeds, n_seg, offsets_s = _subsample_args(xyz, labels, offsets, ks, seeds)
+    picks = []
+    for b in range(n_seg):
+        n = offsets[b + 1] - offsets[b]
+        if not 0 <= ks[b] <= n:
+            raise RuntimeError("subsample: 0 <= k <= points of the segment")
+        order = (subsample_keys(seeds[b], n, xyz.device, key_mask) << 31) | torch.arange(n, dtype=torch.int64, device=xyz.device)
+        picks.append(torch.sort(torch.sort(order)[0][:ks[b]] & 0x7fffffff)[0])
+    sub = torch.cat(picks)
+    rows = sub + torch.cat([torch.full((k,), offsets[b], dtype=torch.int64, device=xyz.device) for b, k in enumerate(ks)])
+    return xyz.index_select(0, rows), labels.index_select(0, rows), sub.to(torch.int32), offsets_s
+
+
+def subsample(xyz, labels, offsets, ks, seeds, key_mask=0xffffffff):
+    """The random subsample of every scene of a batch (reference dataset/dataset.py:73-77), one native call on the current stream
+    (doda_subsample_draw).  xyz float32 [N, 3], labels int32 [N]; offsets: the n_seg + 1 scene offsets, ks: points to keep per
+    scene, seeds: one 64-bit seed per scene (host lists).  Scene b keeps the ks[b] points smallest in (key(seed_b, j) & key_mask, j),
+    in ascending j.  -> (xyz_s [K, 3], labels_s [K], sub_idx int32 [K] (index inside the scene), offsets_s (host list)).  The
+    workspace is the cached per-stream buffer.  CPU tensors: subsample_torch, the same outputs bit for bit."""
+    if not xyz.is_cuda:
+        return subsample_torch(xyz, labels, offsets, ks, seeds, key_mask)
+    offsets, ks, seeds, n_seg, offsets_s = _subsample_args(xyz, labels, offsets, ks, seeds)
+    xyz, labels = xyz.contiguous(), labels.contiguous()
+    off_h, k_h, seeds_h = (C.c_int64 * (n_seg + 1))(*offsets), (C.c_int32 * n_seg)(*ks), (C.c_uint64 * n_seg)(*seeds)
+    total = offsets_s[-1]
+    out_xyz = torch.empty((total, 3), dtype=torch.float32, device=xyz.device)
+    out_labels = torch.empty(total, dtype=torch.int32, device=xyz.device)
+    out_idx = torch.empty(total, dtype=torch.int32, device=xyz.device)
+    nbytes = lib().doda_subsample_workspace_bytes(off_h, n_seg)
+    ws = _ws(nbytes, xyz.device)
+    check(lib().doda_subsample_draw(_p(xyz), _p(labels), None, None, off_h, n_seg, k_h, seeds_h, int(key_mask) & 0xffffffff, _p(out_xyz),
+                                    _p(out_labels), _p(out_idx), None, None, _p(ws), ws.numel(), _stream()), "doda_subsample_draw")
+    return out_xyz, out_labels, out_idx, offsets_s
+
+
 # ---- optimizer step -------------------------------------------------------------------------------
 # ---- full-cloud evaluation (include/doda_eval.h, csrc/eval.hip) ---------------------------------------------------
 class EvalTable:

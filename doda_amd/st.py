@@ -71,6 +71,17 @@ def init_split_sampler(trainer, pseudo_dir, ckpt_dir, resumed, log=print):
     log("split sampler: tail classes %s, ratio %s" % (list(sampler.tail_class_idx), list(sampler.tail_class_ratio)))
 
 
+def check_pseudo_label_clouds(cfg):
+    """Pseudo labels are generated on the FULL clouds of the target scenes and subsampled with the points (reference
+    util/pseudo_labels_util.py:49-51,85-87 with DATA_PROCESSOR.no_downsample_infer: True, dataset/s3dis.py:48-63).  A target config
+    with a downsampling_scale above 1 and no_downsample_infer false or absent makes the reference write label files of subsample
+    length that it cannot read back: rejected here, before any work."""
+    dp = (cfg.DATA_CONFIG_TAR if "DATA_CONFIG_TAR" in cfg else cfg.DATA_CONFIG).DATA_PROCESSOR
+    if tr.downsampling_scale_of(cfg, "target") > 1 and not dp.get("no_downsample_infer", False):
+        raise ValueError("DATA_PROCESSOR.downsampling_scale is above 1 on the target config: set DATA_PROCESSOR.no_downsample_infer: True "
+                         "(pseudo labels are generated on the full clouds and subsampled with the points)")
+
+
 def main(argv=None):
     from . import dist as ddist
     from . import pseudo_labels as pl
@@ -82,6 +93,8 @@ def main(argv=None):
     from .tacm import TacmConfig
     from .train import check_aug_loader
     check_aug_loader(cfg, args)
+    tr.check_subsample_loader(cfg, args)
+    check_pseudo_label_clouds(cfg)
     if TacmConfig.from_cfg(cfg).enabled and (args.host_loader or args.inline_loader):
         raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
                          "(drop --host_loader / --inline_loader, or disable tacm)")

@@ -308,6 +308,27 @@ def check_aug_loader(cfg, args):
                          "(drop --host_loader / --inline_loader, or remove the aug_list)")
 
 
+def downsampling_scale_of(cfg, split):
+    """DATA_PROCESSOR.downsampling_scale of a split's dataset config (default 1: no subsample).  The target split reads
+    DATA_CONFIG_TAR, the source split DATA_CONFIG; the validation split validates the TARGET domain where the experiment has one
+    (reference tool/train.py:369 builds its val loader from DATA_CONFIG_TAR, as doda_amd.test does), else DATA_CONFIG."""
+    key = "DATA_CONFIG_TAR" if (split in ("target", "val") and "DATA_CONFIG_TAR" in cfg) else "DATA_CONFIG"
+    scale = cfg[key].DATA_PROCESSOR.get("downsampling_scale", 1)
+    return scale if scale else 1
+
+
+def used_splits(args):
+    return ("train", "target", "val") if getattr(args, "self_train", False) else ("train", "val")
+
+
+def check_subsample_loader(cfg, args):
+    """DATA_PROCESSOR.downsampling_scale is drawn on the device-resident loader only, as DATA_AUG.aug_list is."""
+    if (getattr(args, "host_loader", False) or getattr(args, "inline_loader", False)) and \
+            any(downsampling_scale_of(cfg, split) > 1 for split in used_splits(args)):
+        raise ValueError("DATA_PROCESSOR.downsampling_scale is above 1: the subsample is drawn on the device-resident loader only "
+                         "(drop --host_loader / --inline_loader, or remove the downsampling_scale)")
+
+
 class Trainer:
     def __init__(self, args, cfg, device, rank=0, world=1, log=print):
         from . import dist as ddist
@@ -350,6 +371,8 @@ class Trainer:
             raise ValueError("DATA_AUG.tacm is enabled: cuboid mixing runs on the device-resident loader only "
                              "(drop --host_loader / --inline_loader, or disable tacm)")
         check_aug_loader(cfg, args)
+        check_subsample_loader(cfg, args)
+        self.subsampled = any(downsampling_scale_of(cfg, split) > 1 for split in used_splits(args))
         self.step_times = []      # (iterations, seconds) of the steady part of every epoch (see train_epoch)
 
     # one forward + backward of one batch; `domain`: None | "source" | "target" (DSNorm statistics)
@@ -395,12 +418,15 @@ class Trainer:
                 src = self._datasets["train"]
                 dsc = MixedDeviceScenes(ds.paths, src.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank,
                                         self.world, self.device, self.tacm, self.split_sampler, augment=ds.augment, shuffle=True,
-                                        full_scale0=fs0, source_seed=src.seed + seed + 1, aug_cfg=aug_config_of(self.cfg, split))
+                                        full_scale0=fs0, source_seed=src.seed + seed + 1, aug_cfg=aug_config_of(self.cfg, split),
+                                        downsampling_scale=downsampling_scale_of(self.cfg, split),
+                                        source_downsampling_scale=downsampling_scale_of(self.cfg, "train"))
                 self._loaders[split] = (dsc, dsc)
             else:
                 dsc = DeviceScenes(ds.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank, self.world,
                                    self.device, augment=ds.augment, shuffle=split != "val",
-                                   full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split))
+                                   full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split),
+                                   downsampling_scale=downsampling_scale_of(self.cfg, split), subsample_seed=seed)
                 self._loaders[split] = (dsc, dsc)
             if split in self._labels:
                 self._apply_labels(split)
@@ -505,6 +531,8 @@ class Trainer:
                 loss, preds, labels = self._pass(batch, pyramid, "source",
                                                  st.get("SRC", Config()).get("loss_weight", 1.0))
                 tb, tp = next(target)
+                if self.subsampled:      # (host sizes: no read-back)
+                    self.log("Subsampled batch: source %d points, target %d points" % (labels.shape[0], tb["labels"].shape[0]))
                 if self.reducer is not None:
                     self.reducer.arm()      # (the second backward pass completes the gradients: its hook may start the exchange)
                 self._pass(tb, tp, "target", st.get("TAR", Config()).get("loss_weight", 1.0))
@@ -514,6 +542,8 @@ class Trainer:
                 if self.reducer is not None:
                     self.reducer.arm()
                 loss, preds, labels = self._pass(batch, pyramid, "source")
+                if self.subsampled:
+                    self.log("Subsampled batch: source %d points" % labels.shape[0])
             if self.reducer is not None:
                 self.reducer.reduce()
             if cfg.OPTIMIZATION.get("clip_grad", False):
@@ -543,7 +573,7 @@ class Trainer:
     @torch.no_grad()
     def validate_epoch(self, epoch):
         from .dsnorm import set_ds_target
-        from .evaluate import score_batch
+        from .evaluate import has_full_cloud, score_batch
         cfg = self.cfg
         self.model.eval()
         if self.reducer is not None:
@@ -551,8 +581,13 @@ class Trainer:
         if cfg.MODEL.get("dsnorm", False):
             self.model.apply(set_ds_target)
         meters = DeviceMeters(cfg.COMMON_CLASSES.n_classes, cfg.DATA_CONFIG.DATA_CLASS.ignore_label, self.device)
+        full = [0, 0]
         for batch, pyramid in self._batches(epoch, "val"):
             score_batch(cfg, self.model, batch, meters, self.device, self.fdt, pyramid=pyramid)      # (OPTIMIZATION.loss's criterion)
+            if has_full_cloud(batch):
+                full = [full[0] + int(batch["offsets"][-1]), full[1] + int(batch["offsets_all"][-1])]
+        if full[1]:
+            self.log("Val full clouds: %d points scored through %d processed points" % (full[1], full[0]))
         meters.all_reduce()
         l, miou, macc, allacc, iou = meters.read()
         self.log("Val result: mIoU/mAcc/allAcc %.4f/%.4f/%.4f." % (miou, macc, allacc))

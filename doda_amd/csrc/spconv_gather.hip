@@ -27,7 +27,7 @@
 #include "common.hpp"
 #include "tilebook.hpp"
 #include "spconv_common.hpp"
-#include "wgrad_pairs.hpp"
+#include "wgrad_backends.hpp"
 #include <stdlib.h>
 #include <utility>
 #include <type_traits>

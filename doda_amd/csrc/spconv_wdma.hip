@@ -24,10 +24,11 @@
 // The 54 units (offset, half of the tile's k-steps) are dealt to the 16 waves; accumulators stay in registers across
 // all tiles a workgroup has of a 16 x 16 channel block; per (workgroup, block it touches) one partial [27][16][16] is written
 // (block-major chunks: see the schedule in the kernel), summed in a fixed order by wgrad_dma_reduce: deterministic.
-#include "common.hpp"
+// Host side (namespace doda_wdma, the interface of wgrad_backends.hpp): the call's tile jobs grouped by rulebook, every layer
+// expanded into its 16 x 16 channel blocks, sixteen blocks per launch.
 #include "tilebook.hpp"
 #include "spconv_common.hpp"
-#include "wgrad_pairs.hpp"
+#include "wgrad_common.hpp"
 #include <stdlib.h>
 #include <type_traits>
 #include <string.h>
@@ -85,16 +86,6 @@ __device__ __forceinline__ s16x4 wd_tr_b64(unsigned addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 ; %2" : "=v"(v) : "v"(addr), "n"(TAG) : "memory");
     return v;
 }
-__device__ __forceinline__ bf16x8 wd_pack_hi16(const f32x4 &d0, const f32x4 &d1) {
-    // the values are bf16-exact: keep the upper halves.  k-slot q of the lane: q < 4 -> d0[q], else d1[q-4]
-    u32x4 r;
-    r[0] = __builtin_amdgcn_perm(__float_as_uint(d0[1]), __float_as_uint(d0[0]), 0x07060302u);
-    r[1] = __builtin_amdgcn_perm(__float_as_uint(d0[3]), __float_as_uint(d0[2]), 0x07060302u);
-    r[2] = __builtin_amdgcn_perm(__float_as_uint(d1[1]), __float_as_uint(d1[0]), 0x07060302u);
-    r[3] = __builtin_amdgcn_perm(__float_as_uint(d1[3]), __float_as_uint(d1[2]), 0x07060302u);
-    return __builtin_bit_cast(bf16x8, r);
-}
-
 __global__ __launch_bounds__(1024) void wgrad_dma16(const WdJobs jobs, const int32_t *__restrict__ tbl,
                                                     int ld, int n, const TileBookView tb) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * WD_BUF_BYTES];
@@ -317,7 +308,7 @@ __global__ __launch_bounds__(1024) void wgrad_dma16(const WdJobs jobs, const int
                     const bf16x8 a = __builtin_bit_cast(bf16x8, v[kk]);
                     const f32x4 e0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, P[0], zero, 0, 0, 0);
                     const f32x4 e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, P[1], zero, 0, 0, 0);
-                    part = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wd_pack_hi16(e0, e1), bt[kk], part, 0, 0, 0);
+                    part = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pack_hi16(e0, e1), bt[kk], part, 0, 0, 0);
                 }
 #pragma unroll
                 for (int mm = 0; mm < WD_MAX_UNITS; ++mm)
@@ -418,6 +409,20 @@ __global__ __launch_bounds__(512) void wgrad_dma_reduce(const WdRJobs jobs) {
 // barrier together run the two phases one after the other.  Removed)
 bool g_use_wdma = !(getenv("DODA_NO_WDMA") && getenv("DODA_NO_WDMA")[0] == '1');
 
+// One 16 x 16 channel block of a layer's weight gradient: x / dy point at the block's first channel (bf16), rows x_stride /
+// dy_stride bytes apart; the block's corner in the layer's dw [27][ca][cb] and its strides (ldo = ca * cb, ldc = cb).
+struct Block { const void *x, *dy; float *dw; int x_stride, dy_stride, ldo, ldc, accumulate; };
+struct WdArgs { WdJobs jobs; WdRJobs red; };      // the kernel arguments of one launch (at most WD_MAX_JOBS blocks)
+
+int groups_for(int n_rows) {
+    const int nt = (n_rows + TB_T - 1) / TB_T;
+    int groups = (nt + 7) / 8 * 8;
+    return groups > 256 ? 256 : groups;
+}
+// workspace per 16 x 16 channel block
+size_t block_partial_bytes(int n_rows) { return align_up((size_t)groups_for(n_rows) * TB_K * 256 * sizeof(float), 256); }
+int n_blocks(const doda_wgrad_job &j) { return (j.ca / 16) * (j.cb / 16); }
+
 }  // namespace
 
 namespace doda_wdma {
@@ -425,54 +430,99 @@ namespace doda_wdma {
 bool enabled() { return g_use_wdma; }
 void set_enabled(bool on) { g_use_wdma = on; }
 
-int groups_for(int n_rows) {
-    const int nt = (n_rows + TB_T - 1) / TB_T;
-    int groups = (nt + 7) / 8 * 8;
-    return groups > 256 ? 256 : groups;
+// bf16, K = 27, a tilebook of the job's table; 16 -> 16, and — round 4 — 16 .. 64 channels on either side as 16 x 16 channel
+// blocks over row-strided slices
+bool eligible(const doda_wgrad_job &j) {
+    return j.tilebook && j.tbl && j.elem_bytes == 2 && j.ca % 16 == 0 && j.ca <= 64 && j.cb % 16 == 0 && j.cb <= 64 &&
+           j.K == 27 && j.n_rows > 0 && j.a && j.b && j.dw &&
+           j.n_a == j.n_rows && j.ld >= j.n_rows && (size_t)j.n_rows * 128 < 0x7ffffff0ull && (size_t)j.K * j.ld * 4 < 0xffffffffull &&
+           !(((uintptr_t)j.a | (uintptr_t)j.b | (uintptr_t)j.tilebook) & 15) && enabled();
 }
-size_t partial_bytes(int n_rows) { return (size_t)groups_for(n_rows) * TB_K * 256 * sizeof(float); }
-int max_jobs() { return WD_MAX_JOBS; }
 
-// blocks[k]: one 16 x 16 channel block of a layer (all over the same table / tilebook, n_rows rows); part: n x partial_bytes
-int launch(const Block *blocks, int n_blocks, const int32_t *tbl, int ld, int n_rows, const void *tilebook, void *part,
-           hipStream_t s) {
-    const TileBookView tb = tilebook_view(const_cast<void *>(tilebook), n_rows);
-    const int groups = groups_for(n_rows), nt = tb.nt;
-    size_t used = 0;      // partial slots handed out so far (bytes)
-    for (int first = 0; first < n_blocks; first += WD_MAX_JOBS) {
-        const int nj = n_blocks - first < WD_MAX_JOBS ? n_blocks - first : WD_MAX_JOBS;
-        WdJobs jobs;
-        WdRJobs rj;
-        ::memset(&jobs, 0, sizeof(jobs));
-        ::memset(&rj, 0, sizeof(rj));
-        jobs.n = nj;
-        // which ranks touch which block (the kernel's chunking, restated): first rank and count per block
-        int first_rank[WD_MAX_JOBS], count[WD_MAX_JOBS];
-        for (int k = 0; k < nj; ++k) { first_rank[k] = -1; count[k] = 0; }
-        const long long N = (long long)nj * nt;
-        if (N >= groups) {
-            for (int r = 0; r < groups; ++r) {
-                const long long st = (long long)r * N / groups, en = (long long)(r + 1) * N / groups;
-                for (long long b = st / nt; b <= (en - 1) / nt; ++b) {
-                    if (first_rank[b] < 0) first_rank[b] = r;
-                    ++count[b];
+// one launch sequence per rulebook (jobs sharing table + tilebook): their 16 x 16 channel blocks in queue order, the blocks'
+// partials contiguous
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
+    Plan p;
+    std::vector<char> done(idx.size(), 0);
+    for (size_t q = 0; q < idx.size(); ++q) {
+        if (done[q]) continue;
+        const doda_wgrad_job &j0 = jobs[idx[q]];
+        Plan::Launch l{(int)p.order.size(), 0, 0, p.partial_bytes};
+        for (size_t r = q; r < idx.size(); ++r) {
+            const doda_wgrad_job &j = jobs[idx[r]];
+            if (done[r] || j.tilebook != j0.tilebook || j.tbl != j0.tbl || j.n_rows != j0.n_rows || j.ld != j0.ld) continue;
+            done[r] = 1;
+            p.order.push_back(idx[r]);
+            ++l.n_jobs;
+            l.n_blocks += n_blocks(j);
+        }
+        p.partial_bytes += (size_t)l.n_blocks * block_partial_bytes(j0.n_rows);
+        p.launches.push_back(l);
+    }
+    return p;
+}
+
+// the kernel arguments of every launch: a rulebook's blocks, WD_MAX_JOBS at a time
+void write_desc(Plan &p, const doda_wgrad_job *jobs, char *part) {
+    p.args.clear();
+    for (const Plan::Launch &l : p.launches) {
+        const doda_wgrad_job &j0 = jobs[p.order[l.first_job]];
+        std::vector<Block> blocks;
+        for (int r = 0; r < l.n_jobs; ++r) {
+            const doda_wgrad_job &j = jobs[p.order[l.first_job + r]];
+            const int es = 2;
+            for (int ci = 0; ci < j.ca; ci += 16)
+                for (int co = 0; co < j.cb; co += 16)
+                    blocks.push_back(Block{(const char *)j.a + ci * es, (const char *)j.b + co * es, j.dw + (size_t)ci * j.cb + co,
+                                           j.ca * es, j.cb * es, j.ca * j.cb, j.cb, (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0});
+        }
+        const int groups = groups_for(j0.n_rows), nt = (j0.n_rows + TB_T - 1) / TB_T;
+        size_t used = l.part_off;      // partial slots handed out so far (bytes)
+        for (int first = 0; first < l.n_blocks; first += WD_MAX_JOBS) {
+            const int nj = l.n_blocks - first < WD_MAX_JOBS ? l.n_blocks - first : WD_MAX_JOBS;
+            WdArgs a;
+            ::memset(&a, 0, sizeof(a));
+            a.jobs.n = nj;
+            // which ranks touch which block (the kernel's chunking, restated): first rank and count per block
+            int first_rank[WD_MAX_JOBS], count[WD_MAX_JOBS];
+            for (int k = 0; k < nj; ++k) { first_rank[k] = -1; count[k] = 0; }
+            const long long N = (long long)nj * nt;
+            if (N >= groups) {
+                for (int r = 0; r < groups; ++r) {
+                    const long long st = (long long)r * N / groups, en = (long long)(r + 1) * N / groups;
+                    for (long long b = st / nt; b <= (en - 1) / nt; ++b) {
+                        if (first_rank[b] < 0) first_rank[b] = r;
+                        ++count[b];
+                    }
                 }
+            } else {      // fewer items than workgroups: one tile per non-empty rank, slot = tile index
+                for (int k = 0; k < nj; ++k) { first_rank[k] = 0; count[k] = nt; }
             }
-        } else {      // fewer items than workgroups: one tile per non-empty rank, slot = tile index
-            for (int k = 0; k < nj; ++k) { first_rank[k] = 0; count[k] = nt; }
+            for (int k = 0; k < nj; ++k) {
+                const Block &b = blocks[first + k];
+                float *pp = (float *)(part + used);
+                used += (size_t)count[k] * TB_K * 256 * sizeof(float);
+                a.jobs.j[k] = WdJob{b.x, b.dy, pp, (unsigned)b.x_stride, (unsigned)b.dy_stride, first_rank[k], 0};
+                a.red.j[k] = WdRJob{pp, b.dw, b.accumulate, b.ldo, b.ldc, count[k]};
+            }
+            const unsigned char *bytes = (const unsigned char *)&a;
+            p.args.insert(p.args.end(), bytes, bytes + sizeof(a));
         }
-        for (int k = 0; k < nj; ++k) {
-            const Block &b = blocks[first + k];
-            float *p = (float *)((char *)part + used);
-            used += (size_t)count[k] * TB_K * 256 * sizeof(float);
-            jobs.j[k] = WdJob{b.x, b.dy, p, (unsigned)b.x_stride, (unsigned)b.dy_stride, first_rank[k], 0};
-            rj.j[k] = WdRJob{p, b.dw, b.accumulate, b.ldo, b.ldc, count[k]};
+    }
+}
+
+// per launch of write_desc: wgrad_dma16, then its reduce
+int launch(const Plan &p, const doda_wgrad_job *jobs, hipStream_t s) {
+    const WdArgs *a = (const WdArgs *)p.args.data();
+    for (const Plan::Launch &l : p.launches) {
+        const doda_wgrad_job &j0 = jobs[p.order[l.first_job]];
+        const TileBookView tb = tilebook_view(const_cast<void *>(j0.tilebook), j0.n_rows);
+        for (int first = 0; first < l.n_blocks; first += WD_MAX_JOBS, ++a) {
+            hipLaunchKernelGGL(wgrad_dma16, dim3(groups_for(j0.n_rows)), dim3(1024), 0, s, a->jobs, j0.tbl, j0.ld, j0.n_rows, tb);
+            hipLaunchKernelGGL(wgrad_dma_reduce, dim3(TB_K * 256 / 32, a->jobs.n), dim3(512), 0, s, a->red);
         }
-        hipLaunchKernelGGL(wgrad_dma16, dim3(groups), dim3(1024), 0, s, jobs, tbl, ld, n_rows, tb);
-        hipLaunchKernelGGL(wgrad_dma_reduce, dim3(TB_K * 256 / 32, nj), dim3(512), 0, s, rj);
     }
     return doda_check_launch();
 }
 
 }  // namespace doda_wdma
-

@@ -11,17 +11,17 @@
 // accumulators.  Gathers for the next offset are issued before the MFMAs of the current one.
 // Offsets with no present row in the step are skipped wave-uniformly.  Accumulators (<= 7 offsets
 // x TA x TB 16x16 tiles) live in registers for the whole row chunk; per-chunk partials are reduced
-// by a second kernel in fixed order: deterministic, no float atomics.
-#include "wgrad_pairs.hpp"
+// by a second kernel in fixed order (wgrad_common.hpp wgrad_fold): deterministic, no float atomics.
+//
+// This file also holds the entry point of every weight gradient, doda_spconv_wgrad_multi: ONE call plan (make_call_plan: the
+// class of every job, each class's plan, the workspace and descriptor layout) serves the size query and the call, and the
+// four kernel classes — this file's gather-table class (namespace doda_dense) and the three of wgrad_backends.hpp — are
+// planned, described and launched through the same three steps.
+#include "wgrad_common.hpp"
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
 #include <vector>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -311,26 +311,11 @@ struct WJob {            // device descriptor of one layer inside a variant grou
     float *out;          // partials of the job (or dw itself when it has a single row chunk)
     int ca, cb, ld, K, n_rows, rows_per_chunk, n_tag, n_tbg, n_og, blk_end;   // blk_end: inclusive prefix
 };
-struct RJob {            // one reduction: dw[q] (+)= sum_r partial[r][q]
-    const float4 *partial;
-    float4 *dw;
-    long long n_quad;
-    int R, blk_end, accumulate, pad;
-};
-
-template <class J>
-__device__ __forceinline__ int find_job(const J *jobs, int n_jobs, int blk) {
-    int lo = 0, hi = n_jobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (blk < jobs[mid].blk_end) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
+using doda_wgrad::RJob;
 
 template <class T, int TA, int TB, int OGW, bool VOK>
 __global__ __launch_bounds__(256) void wgrad_multi_kernel(const WJob *__restrict__ jobs, int n_jobs) {
-    const int j = find_job(jobs, n_jobs, (int)blockIdx.x);
+    const int j = find_job<WJob, &WJob::blk_end>(jobs, n_jobs, (int)blockIdx.x);
     const WJob d = jobs[j];
     const int first = j == 0 ? 0 : jobs[j - 1].blk_end;
     wgrad_body<T, TA, TB, OGW, VOK>((const typename T::elem *)d.a, d.ca, (const typename T::elem *)d.b, d.cb,
@@ -338,41 +323,15 @@ __global__ __launch_bounds__(256) void wgrad_multi_kernel(const WJob *__restrict
                                     d.out, (int)blockIdx.x - first);
 }
 
-// (256 / RL) element quads x RL chunk lanes per block, fixed order (as wgrad_reduce4<16>): lane r sums chunks r, r + RL, ..., the
-// lane sums are added in ascending r.  RL = d.pad = the smallest power of two >= min(R, 16) (round 6; it was 16 for every job: the
-// coarse levels' jobs have 1 .. 4 chunks, so 3/4 .. 15/16 of a block's threads had nothing to read and a 7.5 M-parameter network
-// took 117 k blocks of 256 bytes each).  For R <= 16 every lane holds at most one chunk either way: the same sums, bit for bit.
+// the call's reductions over chunk-major partials (gather-table and pair-list jobs): the shared fold, flat source
 __global__ __launch_bounds__(256) void wgrad_reduce_multi(const RJob *__restrict__ jobs, int n_jobs) {
-    __shared__ float4 part[256];
-    const int j = find_job(jobs, n_jobs, (int)blockIdx.x);
+    const int j = find_job<RJob, &RJob::blk_end>(jobs, n_jobs, (int)blockIdx.x);
     const RJob d = jobs[j];
-    const int first = j == 0 ? 0 : jobs[j - 1].blk_end;
-    const int RL = d.pad, EL = 256 / RL;                 // RL in {1, 2, 4, 8, 16}
-    const int el = (int)threadIdx.x % EL, rl = (int)threadIdx.x / EL;
-    const long long q = (long long)((int)blockIdx.x - first) * EL + el;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < d.n_quad)
-        for (int r = rl; r < d.R; r += RL) {
-            const float4 v = d.partial[(long long)r * d.n_quad + q];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    part[rl * EL + el] = s;
-    doda_sync();
-    if (rl == 0 && q < d.n_quad) {
-        float4 t = part[el];
-        for (int r = 1; r < RL; ++r) {
-            const float4 v = part[r * EL + el];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
-        if (d.accumulate) {
-            const float4 old = d.dw[q];
-            t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w;
-        }
-        d.dw[q] = t;
-    }
+    wgrad_fold((int)blockIdx.x - (j == 0 ? 0 : jobs[j - 1].blk_end), d.R, d.n_quad, d.n_quad, d.dw, d.accumulate,
+               [&](long long q) { return d.partial + q; });
 }
 
-// Fixed-order reduction of the per-chunk partials: 16 element lanes x 16 chunk lanes per block;
+// The scalar form for element counts that are no multiple of four: 16 element lanes x 16 chunk lanes per block;
 // lane r sums chunks r, r+16, ... and the 16 lane sums are added in ascending r (deterministic).
 __global__ __launch_bounds__(256) void wgrad_reduce(const float *__restrict__ partial, int R,
                                                     long long n_elem, float *__restrict__ dw,
@@ -448,7 +407,7 @@ struct JobPlan {
     Plan p;
     int esz, vok, key;
     int split;         // fp32 job multiplied as bf16 head / tail splits (F32S)
-    size_t ws_off;     // partials of this job inside the workspace (unused when R == 1)
+    size_t ws_off;     // partials of this job inside the class's workspace (unused when it writes dw itself)
     long long n_elem;
 };
 
@@ -504,78 +463,189 @@ struct Staging {
     bool pending = false;
 };
 Staging g_staging;
-}  // namespace
+
+// The gather-table class behind the classes' interface (wgrad_backends.hpp): it takes every job no other class takes.
+namespace doda_dense {
+
+struct Plan {
+    std::vector<int> idx;
+    std::vector<JobPlan> jp;           // per job of idx
+    struct Group { int first, count, blocks, rep; };   // one launch per kernel variant; rep: a job of the variant
+    std::vector<Group> groups;
+    std::vector<int> order, blk_end;   // per descriptor: position in idx, inclusive block prefix inside its group
+    bool valid = true;                 // false: a job this kernel cannot run (DODA_ERR_INVALID)
+    size_t partial_bytes = 0, desc_bytes = 0;
+    int n_reduce = 0;
+};
+
+// partials unless the job's one row chunk can overwrite dw itself
+bool needs_partial(const JobPlan &jp, const doda_wgrad_job &j) { return jp.p.R > 1 || (j.flags & DODA_WGRAD_ACCUMULATE); }
+// whole float quads: the shared fold; else the per-layer scalar reduce
+bool quads(const JobPlan &jp, const doda_wgrad_job &j) { return jp.n_elem % 4 == 0 && (uintptr_t)j.dw % 16 == 0; }
+
+// rows per chunk of the job's plan (the wide class sums over the same chunks)
+int rows_per_chunk(const doda_wgrad_job &j) { return make_plan(j.K, j.ca, j.cb, j.n_rows, j.elem_bytes, true).rows_per_chunk; }
+
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
+    Plan p;
+    p.idx = idx;
+    p.jp.resize(idx.size());
+    std::vector<int> keys;
+    for (size_t k = 0; k < idx.size(); ++k) {
+        JobPlan &jp = p.jp[k];
+        const doda_wgrad_job &j = jobs[idx[k]];
+        if (!plan_job(j, &jp)) { jp.key = -1; p.valid = false; continue; }
+        jp.ws_off = p.partial_bytes;
+        if (needs_partial(jp, j)) {
+            p.partial_bytes += align_up((size_t)jp.p.R * jp.n_elem * 4, 256);
+            p.n_reduce += quads(jp, j) ? 1 : 0;
+        }
+        bool seen = false;
+        for (int key : keys) seen |= key == jp.key;
+        if (!seen) keys.push_back(jp.key);
+    }
+    for (int key : keys) {      // descriptors grouped by kernel variant
+        Plan::Group g{(int)p.order.size(), 0, 0, -1};
+        for (size_t k = 0; k < idx.size(); ++k) {
+            if (p.jp[k].key != key) continue;
+            const auto &q = p.jp[k].p;
+            if (g.rep < 0) g.rep = (int)k;
+            g.blocks += q.R * q.n_tag * q.n_tbg * q.n_og;
+            p.order.push_back((int)k);
+            p.blk_end.push_back(g.blocks);
+            ++g.count;
+        }
+        p.groups.push_back(g);
+    }
+    p.desc_bytes = p.order.size() * sizeof(WJob);
+    return p;
+}
+
+void write_desc(const Plan &p, const doda_wgrad_job *jobs, char *part, void *desc, std::vector<RJob> &reduce, int *reduce_blocks) {
+    WJob *wj = (WJob *)desc;
+    for (size_t q = 0; q < p.order.size(); ++q) {
+        const JobPlan &jp = p.jp[p.order[q]];
+        const doda_wgrad_job &j = jobs[p.idx[p.order[q]]];
+        WJob d;
+        d.a = j.a; d.b = j.b; d.tbl = j.tbl;
+        d.out = needs_partial(jp, j) ? (float *)(part + jp.ws_off) : j.dw;
+        d.ca = j.ca; d.cb = j.cb; d.ld = j.ld; d.K = j.K; d.n_rows = j.n_rows;
+        d.rows_per_chunk = jp.p.rows_per_chunk; d.n_tag = jp.p.n_tag; d.n_tbg = jp.p.n_tbg; d.n_og = jp.p.n_og;
+        d.blk_end = p.blk_end[q];
+        wj[q] = d;
+    }
+    for (size_t k = 0; k < p.idx.size(); ++k) {
+        const doda_wgrad_job &j = jobs[p.idx[k]];
+        if (needs_partial(p.jp[k], j) && quads(p.jp[k], j))
+            doda_wgrad::push_reduce(reduce, reduce_blocks, part + p.jp[k].ws_off, j, p.jp[k].p.R);
+    }
+}
+
+int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
+    const WJob *wj_dev = (const WJob *)desc_dev;
+    for (const Plan::Group &g : p.groups) {
+        const JobPlan &jp = p.jp[g.rep];
+        if (jp.esz == 4 && jp.split) launch_multi_variant<F32S>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
+        else if (jp.esz == 4) launch_multi_variant<F32>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
+        else launch_multi_variant<BF16>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
+    }
+    return doda_check_launch();
+}
+
+// odd element counts: the per-layer scalar reduce
+int launch_scalar_reduce(const Plan &p, const doda_wgrad_job *jobs, char *part, hipStream_t s) {
+    for (size_t k = 0; k < p.idx.size(); ++k) {
+        const JobPlan &jp = p.jp[k];
+        const doda_wgrad_job &j = jobs[p.idx[k]];
+        if (!needs_partial(jp, j) || quads(jp, j)) continue;
+        hipLaunchKernelGGL(wgrad_reduce, dim3(div_up(jp.n_elem, 16)), dim3(256), 0, s, (const float *)(part + jp.ws_off), jp.p.R,
+                           jp.n_elem, j.dw, (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0);
+    }
+    return doda_check_launch();
+}
+
+}  // namespace doda_dense
 
 // job classes of a multi call
 enum { J_SKIP = 0, J_ZERO = 1, J_DENSE = 2, J_PAIRS = 3, J_TILE = 4, J_WIDE = 5 };
 
 // rows from which a rulebook's tile jobs take the LDS-staged kernel even when pair lists are at hand (measurement aid:
 // DODA_WDMA_MIN_ROWS)
-static int wdma_min_rows() {
+int wdma_min_rows() {
     static const int v = getenv("DODA_WDMA_MIN_ROWS") ? atoi(getenv("DODA_WDMA_MIN_ROWS")) : 32768;
     return v;
 }
 
-static int classify(const doda_wgrad_job &j) {
+int classify(const doda_wgrad_job &j) {
     if (j.n_rows == 0 && j.dw && j.K > 0 && j.ca > 0 && j.cb > 0)
         return (j.flags & DODA_WGRAD_ACCUMULATE) ? J_SKIP : J_ZERO;
     // a tilebook of the job's table and 48 .. 224 channels on both sides: the wide LDS-staged kernel (spconv_wwide.hip).  It
     // takes 48 / 64-channel layers before wgrad_dma16, whose 16 x 16 blocks re-stage the tile once per block, and
     // only jobs that would otherwise run the gather-table kernel, whose sums it reproduces (jobs with pair lists keep them)
     if (doda_wwide::eligible(j) && !doda_pairs::eligible(j)) return J_WIDE;
-    // a tilebook of the job's table: the LDS-staged kernel (bf16, K = 27; 16 -> 16, and — round 4 — 16 .. 64 channels on
-    // either side as 16 x 16 channel blocks over row-strided slices)
-    if (j.tilebook && j.tbl && j.elem_bytes == 2 && j.ca % 16 == 0 && j.ca <= 64 && j.cb % 16 == 0 && j.cb <= 64 &&
-        j.K == 27 && j.n_rows > 0 && j.a && j.b && j.dw &&
-        j.n_a == j.n_rows && j.ld >= j.n_rows && (size_t)j.n_rows * 128 < 0x7ffffff0ull && (size_t)j.K * j.ld * 4 < 0xffffffffull &&
-        !(((uintptr_t)j.a | (uintptr_t)j.b | (uintptr_t)j.tilebook) & 15) && doda_wdma::enabled() &&
-        // round 4 (block-major chunks: one or two partials per workgroup whatever the number of layers): faster than the pair
-        // lists from ~40 k rows up — 8 layers per call: 601 k rows 21.3 / 43.3 us per layer, 152 k rows 7.2 / 13.0, level 2
-        // (154 k rows, 32 -> 32 as four blocks) 21.3 / 23.7, 37 k rows 10.3 / 10.1 (tools/wl2.py).  Round 3's schedule (every
-        // workgroup walked every layer: a flush per layer and workgroup) lost below 262 k rows.
-        (j.n_rows >= wdma_min_rows() || !doda_pairs::eligible(j)))
-        return J_TILE;
+    // a tilebook of the job's table: the LDS-staged 16 x 16 tile kernel (spconv_wdma.hip).
+    // Round 4 (block-major chunks: one or two partials per workgroup whatever the number of layers): faster than the pair
+    // lists from ~40 k rows up — 8 layers per call: 601 k rows 21.3 / 43.3 us per layer, 152 k rows 7.2 / 13.0, level 2
+    // (154 k rows, 32 -> 32 as four blocks) 21.3 / 23.7, 37 k rows 10.3 / 10.1 (tools/wl2.py).  Round 3's schedule (every
+    // workgroup walked every layer: a flush per layer and workgroup) lost below 262 k rows.
+    if (doda_wdma::eligible(j) && (j.n_rows >= wdma_min_rows() || !doda_pairs::eligible(j))) return J_TILE;
     // DODA_WGRAD_NO_PAIRS=1 keeps every job on the gather-table kernel (A/B measurements)
     static const bool no_pairs = getenv("DODA_WGRAD_NO_PAIRS") && getenv("DODA_WGRAD_NO_PAIRS")[0] == '1';
     if (doda_pairs::eligible(j) && (!no_pairs || !j.tbl)) return J_PAIRS;
     return J_DENSE;
 }
 
-// row chunks of the gather-table kernel's plan for a wide job: the wide kernel sums over the same chunks (same bits)
-static std::vector<int> wide_chunks(const doda_wgrad_job *jobs_h, const std::vector<int> &idx) {
+// Everything a call does, decided from the host-side job list alone (identical inputs give an identical plan): the class of
+// every job, each class's plan, and where its partials and descriptors lie.
+//   workspace:   [dense partials][pairs][tile][wide], every part a multiple of 256 bytes
+//   descriptors: [dense WJobs][the shared RJob list: dense, then pairs] 16| [pairs PJobs] 16| [wide WwJobs]
+struct CallPlan {
+    std::vector<int> cls;
+    doda_dense::Plan dense;
+    doda_pairs::Plan pairs;
+    doda_wdma::Plan tile;
+    doda_wwide::Plan wide;
+    size_t pairs_part, tile_part, wide_part, part_bytes;   // workspace offsets of the classes' partials; their end
+    size_t rj_off, pj_off, ww_off, desc_bytes;             // descriptor offsets (dense: 0); their end
+    int n_reduce;
+};
+
+CallPlan make_call_plan(const doda_wgrad_job *jobs, int n_jobs) {
+    CallPlan cp;
+    std::vector<int> of[J_WIDE + 1];
+    for (int k = 0; k < n_jobs; ++k) {
+        cp.cls.push_back(classify(jobs[k]));
+        of[cp.cls[k]].push_back(k);
+    }
     std::vector<int> rpc;
-    for (int k : idx) rpc.push_back(make_plan(jobs_h[k].K, jobs_h[k].ca, jobs_h[k].cb, jobs_h[k].n_rows, 2, true).rows_per_chunk);
-    return rpc;
+    for (int k : of[J_WIDE]) rpc.push_back(doda_dense::rows_per_chunk(jobs[k]));
+    cp.dense = doda_dense::plan(jobs, of[J_DENSE]);
+    cp.pairs = doda_pairs::plan(jobs, of[J_PAIRS]);
+    cp.tile = doda_wdma::plan(jobs, of[J_TILE]);
+    cp.wide = doda_wwide::plan(jobs, of[J_WIDE], rpc);
+    cp.pairs_part = cp.dense.partial_bytes;
+    cp.tile_part = cp.pairs_part + cp.pairs.partial_bytes;
+    cp.wide_part = cp.tile_part + cp.tile.partial_bytes;
+    cp.part_bytes = cp.wide_part + cp.wide.partial_bytes;
+    cp.n_reduce = cp.dense.n_reduce + cp.pairs.n_reduce;
+    cp.rj_off = cp.dense.desc_bytes;
+    cp.pj_off = align_up(cp.rj_off + cp.n_reduce * sizeof(RJob), 16);
+    cp.ww_off = align_up(cp.pj_off + cp.pairs.desc_bytes, 16);
+    cp.desc_bytes = cp.ww_off + cp.wide.desc_bytes;
+    return cp;
 }
-
-static size_t tile_blocks(const doda_wgrad_job &j) { return (size_t)(j.ca / 16) * (j.cb / 16); }
-
-static bool dense_needs_partial(const JobPlan &jp, const doda_wgrad_job &j) {
-    return jp.p.R > 1 || (j.flags & DODA_WGRAD_ACCUMULATE);
-}
+}  // namespace
 
 extern "C" size_t doda_spconv_wgrad_multi_workspace_bytes(const doda_wgrad_job *jobs_h, int32_t n_jobs) {
     if (!jobs_h || n_jobs <= 0) return 0;
-    size_t total = 0;
-    std::vector<int> wide_jobs;
-    for (int k = 0; k < n_jobs; ++k) {
-        const int cls = classify(jobs_h[k]);
-        if (cls == J_WIDE) { wide_jobs.push_back(k); continue; }
-        if (cls == J_PAIRS) { total += doda_pairs::partial_bytes(jobs_h[k]); continue; }
-        if (cls == J_TILE) { total += tile_blocks(jobs_h[k]) * align_up(doda_wdma::partial_bytes(jobs_h[k].n_rows), 256); continue; }
-        if (cls != J_DENSE) continue;
-        JobPlan jp;
-        if (!plan_job(jobs_h[k], &jp)) continue;
-        if (dense_needs_partial(jp, jobs_h[k])) total += align_up((size_t)jp.p.R * jp.n_elem * 4, 256);
-    }
-    const std::vector<int> rpc = wide_chunks(jobs_h, wide_jobs);
-    total += doda_wwide::partial_bytes(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size());
+    const size_t total = make_call_plan(jobs_h, n_jobs).part_bytes;
     return total < 256 ? 256 : total;
 }
 
+// a bound that covers the descriptors of every plan of n_jobs jobs (a job has descriptors in one class only)
 extern "C" size_t doda_spconv_wgrad_multi_desc_bytes(int32_t n_jobs) {
-    size_t per = sizeof(WJob) + sizeof(RJob) > doda_pairs::desc_bytes_per_job()
-                     ? sizeof(WJob) + sizeof(RJob) : doda_pairs::desc_bytes_per_job();
+    size_t per = sizeof(WJob) + sizeof(RJob);
+    if (per < doda_pairs::desc_bytes_per_job()) per = doda_pairs::desc_bytes_per_job();
     if (per < doda_wwide::desc_bytes_per_job()) per = doda_wwide::desc_bytes_per_job();
     return n_jobs <= 0 ? 0 : align_up((size_t)n_jobs * per + 256, 256);
 }
@@ -585,127 +655,21 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     if (!jobs_h || n_jobs <= 0 || !ws || !desc_dev) return DODA_ERR_INVALID;
     if (desc_bytes < doda_spconv_wgrad_multi_desc_bytes(n_jobs)) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
-    std::vector<JobPlan> plans(n_jobs);
-    std::vector<int> keys, cls(n_jobs), pair_jobs, tile_jobs, wide_jobs;
-    size_t off = 0;
-    for (int k = 0; k < n_jobs; ++k) {
-        plans[k].key = -1;
-        cls[k] = classify(jobs_h[k]);
-        if (cls[k] == J_ZERO) {
-            hipMemsetAsync(jobs_h[k].dw, 0, (size_t)jobs_h[k].K * jobs_h[k].ca * jobs_h[k].cb * 4, s);
-            continue;
-        }
-        if (cls[k] == J_SKIP) continue;
-        if (cls[k] == J_PAIRS) { pair_jobs.push_back(k); continue; }
-        if (cls[k] == J_TILE) { tile_jobs.push_back(k); continue; }
-        if (cls[k] == J_WIDE) { wide_jobs.push_back(k); continue; }
-        if (!plan_job(jobs_h[k], &plans[k])) return DODA_ERR_INVALID;
-        plans[k].ws_off = off;
-        if (dense_needs_partial(plans[k], jobs_h[k])) off += align_up((size_t)plans[k].p.R * plans[k].n_elem * 4, 256);
-        bool seen = false;
-        for (int key : keys) seen |= key == plans[k].key;
-        if (!seen) keys.push_back(plans[k].key);
-    }
-    doda_pairs::Prepared prep;
-    if (!pair_jobs.empty()) {
-        const int st = doda_pairs::prepare(jobs_h, pair_jobs.data(), (int)pair_jobs.size(), (char *)ws, &off, &prep);
-        if (st != DODA_OK) return st;
-    }
-    // tile jobs: one launch per rulebook (jobs sharing table + tilebook): their 16 x 16 channel blocks in queue order, the
-    // blocks' partials contiguous behind everything else
-    {
-        std::vector<char> done(tile_jobs.size(), 0);
-        for (size_t q = 0; q < tile_jobs.size(); ++q) {
-            if (done[q]) continue;
-            const doda_wgrad_job &j0 = jobs_h[tile_jobs[q]];
-            std::vector<doda_wdma::Block> blocks;
-            for (size_t r = q; r < tile_jobs.size(); ++r) {
-                const doda_wgrad_job &j = jobs_h[tile_jobs[r]];
-                if (done[r] || j.tilebook != j0.tilebook || j.tbl != j0.tbl || j.n_rows != j0.n_rows || j.ld != j0.ld) continue;
-                done[r] = 1;
-                const int es = 2;
-                for (int ci = 0; ci < j.ca; ci += 16)
-                    for (int co = 0; co < j.cb; co += 16)
-                        blocks.push_back(doda_wdma::Block{(const char *)j.a + ci * es, (const char *)j.b + co * es,
-                                                          j.dw + (size_t)ci * j.cb + co, j.ca * es, j.cb * es, j.ca * j.cb, j.cb,
-                                                          (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0});
-            }
-            const size_t bytes = blocks.size() * align_up(doda_wdma::partial_bytes(j0.n_rows), 256);
-            if (ws_bytes < off + bytes) return DODA_ERR_WORKSPACE;
-            const int st = doda_wdma::launch(blocks.data(), (int)blocks.size(), j0.tbl, j0.ld, j0.n_rows, j0.tilebook,
-                                             (char *)ws + off, s);
-            if (st != DODA_OK) return st;
-            off += bytes;
-        }
-    }
-    // wide tile jobs: one launch for all of them, their partials behind the rest
-    std::vector<unsigned char> wide_desc;
-    int wide_wgs = 0, wide_red = 0;
-    if (!wide_jobs.empty()) {
-        const std::vector<int> rpc = wide_chunks(jobs_h, wide_jobs);
-        const size_t bytes = doda_wwide::partial_bytes(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size());
-        if (ws_bytes < off + bytes) return DODA_ERR_WORKSPACE;
-        doda_wwide::prepare(jobs_h, wide_jobs.data(), rpc.data(), (int)wide_jobs.size(), (char *)ws + off, wide_desc, &wide_wgs,
-                            &wide_red);
-        off += bytes;
-    }
-    if (ws_bytes < off) return DODA_ERR_WORKSPACE;
-
-    // dense descriptors grouped by kernel variant, then the reductions
-    std::vector<WJob> wj;
-    std::vector<RJob> rj;
-    struct Group { int first, count, blocks, rep; };
-    std::vector<Group> groups;
-    for (int key : keys) {
-        Group g{(int)wj.size(), 0, 0, -1};
-        for (int k = 0; k < n_jobs; ++k) {
-            if (cls[k] != J_DENSE || plans[k].key != key) continue;
-            const doda_wgrad_job &j = jobs_h[k];
-            const Plan &p = plans[k].p;
-            if (g.rep < 0) g.rep = k;
-            WJob d;
-            d.a = j.a; d.b = j.b; d.tbl = j.tbl;
-            d.out = dense_needs_partial(plans[k], j) ? (float *)((char *)ws + plans[k].ws_off) : j.dw;
-            d.ca = j.ca; d.cb = j.cb; d.ld = j.ld; d.K = j.K; d.n_rows = j.n_rows;
-            d.rows_per_chunk = p.rows_per_chunk; d.n_tag = p.n_tag; d.n_tbg = p.n_tbg; d.n_og = p.n_og;
-            g.blocks += p.R * p.n_tag * p.n_tbg * p.n_og;
-            d.blk_end = g.blocks;
-            wj.push_back(d);
-            ++g.count;
-        }
-        groups.push_back(g);
-    }
+    // Every check comes before the first enqueue: a call that returns an error has left the stream and the caller's
+    // gradients untouched.
+    CallPlan cp = make_call_plan(jobs_h, n_jobs);
+    if (!cp.dense.valid) return DODA_ERR_INVALID;
+    if (ws_bytes < cp.part_bytes || desc_bytes < cp.desc_bytes) return DODA_ERR_WORKSPACE;
+    char *part = (char *)ws;
     int r_blocks = 0;
-    bool scalar_reduce = false;
-    for (int k = 0; k < n_jobs; ++k) {
-        if (cls[k] != J_DENSE || !dense_needs_partial(plans[k], jobs_h[k])) continue;
-        if (plans[k].n_elem % 4 != 0 || (uintptr_t)jobs_h[k].dw % 16 != 0) { scalar_reduce = true; continue; }
-        RJob d;
-        d.partial = (const float4 *)((char *)ws + plans[k].ws_off);
-        d.dw = (float4 *)jobs_h[k].dw;
-        d.n_quad = plans[k].n_elem / 4;
-        d.R = plans[k].p.R;
-        d.accumulate = (jobs_h[k].flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0;
-        d.pad = 0;
-        int rl = 1;
-        while (rl < 16 && rl < d.R) rl *= 2;
-        d.pad = rl;                                        // chunk lanes per block (wgrad_reduce_multi)
-        r_blocks += (int)div_up(d.n_quad, 256 / rl);
-        d.blk_end = r_blocks;
-        rj.push_back(d);
-    }
-    const size_t wbytes = wj.size() * sizeof(WJob), rbytes = rj.size() * sizeof(RJob);
-    const size_t pair_off = align_up(wbytes + rbytes, 16), pbytes = prep.desc.size();
-    const size_t wide_off = align_up(pair_off + pbytes, 16), wdbytes = wide_desc.size();
-    const size_t total_desc = wide_off + wdbytes;
-    if (total_desc > desc_bytes) return DODA_ERR_WORKSPACE;
-    if (total_desc > 0) {
+    doda_wdma::write_desc(cp.tile, jobs_h, part + cp.tile_part);
+    if (cp.desc_bytes > 0) {
         std::lock_guard<std::mutex> lock(g_staging.mu);
         Staging &st = g_staging;
         if (st.pending) { hipEventSynchronize(st.ev); st.pending = false; }
-        if (st.cap < total_desc) {
+        if (st.cap < cp.desc_bytes) {
             if (st.host) hipHostFree(st.host);
-            st.cap = align_up(total_desc, 4096) * 2;
+            st.cap = align_up(cp.desc_bytes, 4096) * 2;
             if (hipHostMalloc(&st.host, st.cap, hipHostMallocDefault) != hipSuccess) { st.host = nullptr; st.cap = 0; return DODA_ERR_NOMEM; }
         }
         int cur_dev = 0;
@@ -713,44 +677,33 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
         if (st.ev && st.ev_dev != cur_dev) { hipEventDestroy(st.ev); st.ev = nullptr; }   // library used from another device
         if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) return DODA_ERR_LAUNCH;
         st.ev_dev = cur_dev;
-        if (wbytes) memcpy(st.host, wj.data(), wbytes);
-        if (rbytes) memcpy((char *)st.host + wbytes, rj.data(), rbytes);
-        if (pbytes) memcpy((char *)st.host + pair_off, prep.desc.data(), pbytes);
-        if (wdbytes) memcpy((char *)st.host + wide_off, wide_desc.data(), wdbytes);
-        if (hipMemcpyAsync(desc_dev, st.host, total_desc, hipMemcpyHostToDevice, s) != hipSuccess) return DODA_ERR_LAUNCH;
+        char *host = (char *)st.host;
+        std::vector<RJob> rj;
+        doda_dense::write_desc(cp.dense, jobs_h, part, host, rj, &r_blocks);
+        doda_pairs::write_desc(cp.pairs, jobs_h, part + cp.pairs_part, host + cp.pj_off, rj, &r_blocks);
+        doda_wwide::write_desc(cp.wide, part + cp.wide_part, host + cp.ww_off);
+        if (!rj.empty()) memcpy(host + cp.rj_off, rj.data(), rj.size() * sizeof(RJob));
+        if (hipMemcpyAsync(desc_dev, st.host, cp.desc_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return DODA_ERR_LAUNCH;
         hipEventRecord(st.ev, s);
         st.pending = true;
     }
-    const WJob *wj_dev = (const WJob *)desc_dev;
-    for (const Group &g : groups) {
-        const JobPlan &jp = plans[g.rep];
-        if (jp.esz == 4 && jp.split) launch_multi_variant<F32S>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
-        else if (jp.esz == 4) launch_multi_variant<F32>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
-        else launch_multi_variant<BF16>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
-    }
-    int st = doda_check_launch();
+    // Order on the stream: the descriptor upload; the memsets of empty jobs; per tile rulebook wgrad_dma16 and its
+    // wgrad_dma_reduce; the gather-table kernels; the pair-list kernels; wgrad_wide and wgrad_wide_reduce; one
+    // wgrad_reduce_multi for the gather-table and pair-list partials; the scalar reduces.  Every class's kernels come before
+    // the reduce that reads their partials.
+    const char *desc = (const char *)desc_dev;
+    for (int k = 0; k < n_jobs; ++k)
+        if (cp.cls[k] == J_ZERO && hipMemsetAsync(jobs_h[k].dw, 0, (size_t)jobs_h[k].K * jobs_h[k].ca * jobs_h[k].cb * 4, s) != hipSuccess)
+            return DODA_ERR_LAUNCH;
+    int st = doda_wdma::launch(cp.tile, jobs_h, s);
+    if (st == DODA_OK) st = doda_dense::launch(cp.dense, desc, s);
+    if (st == DODA_OK && !cp.pairs.idx.empty()) st = doda_pairs::launch(cp.pairs, desc + cp.pj_off, s);
+    if (st == DODA_OK && cp.wide.n > 0) st = doda_wwide::launch(cp.wide, desc + cp.ww_off, s);
     if (st != DODA_OK) return st;
-    if (!pair_jobs.empty()) {
-        st = doda_pairs::launch(prep, (const char *)desc_dev + pair_off, s);
-        if (st != DODA_OK) return st;
-    }
-    if (!wide_jobs.empty()) {
-        st = doda_wwide::launch((const char *)desc_dev + wide_off, (int)wide_jobs.size(), wide_wgs, wide_red, s);
-        if (st != DODA_OK) return st;
-    }
-    if (!rj.empty()) {
-        hipLaunchKernelGGL(wgrad_reduce_multi, dim3(r_blocks), dim3(256), 0, s,
-                           (const RJob *)((const char *)desc_dev + wbytes), (int)rj.size());
+    if (cp.n_reduce > 0) {
+        hipLaunchKernelGGL(wgrad_reduce_multi, dim3(r_blocks), dim3(256), 0, s, (const RJob *)(desc + cp.rj_off), cp.n_reduce);
         st = doda_check_launch();
         if (st != DODA_OK) return st;
     }
-    if (scalar_reduce)   // odd element counts: the per-layer scalar reduce
-        for (int k = 0; k < n_jobs; ++k) {
-            if (cls[k] != J_DENSE || !dense_needs_partial(plans[k], jobs_h[k])) continue;
-            if (plans[k].n_elem % 4 == 0 && (uintptr_t)jobs_h[k].dw % 16 == 0) continue;
-            hipLaunchKernelGGL(wgrad_reduce, dim3(div_up(plans[k].n_elem, 16)), dim3(256), 0, s,
-                               (const float *)((char *)ws + plans[k].ws_off), plans[k].p.R, plans[k].n_elem,
-                               jobs_h[k].dw, (jobs_h[k].flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0);
-        }
-    return doda_check_launch();
+    return doda_dense::launch_scalar_reduce(cp.dense, jobs_h, part, s);
 }

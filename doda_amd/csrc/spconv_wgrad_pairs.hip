@@ -18,13 +18,10 @@
 //     No LDS, no barriers in the loop, every wave independent.
 // Per 32 pairs and 16x16 channel tile: 2 index reads (shared by two steps), 2 row gathers (16 B per
 // lane), 4 transposing MFMAs, 1 contraction MFMA.  MFMA is still far from a bound.
-// Deterministic: per-chunk partials, fixed-order reduce, no float atomics.
-#include "wgrad_pairs.hpp"
+// Deterministic: per-range partials, summed in fixed order by the call's shared reduction (wgrad_common.hpp wgrad_fold: the
+// reductions join the gather-table jobs' in one wgrad_reduce_multi launch); no float atomics.
+#include "wgrad_common.hpp"
 #include <string.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -49,12 +46,6 @@ struct PJob {
     unsigned a_bytes, b_bytes;
     int ca, cb, ld, K, n_rows, n_range, n_og, n_tag, n_tbg, seg_nt, blk_end, pad;
 };
-struct RJob {            // dw[q] (+)= sum_r partial[r][q], q over K*ca*cb/4
-    const float4 *partial;
-    float4 *dw;
-    long long n_quad;
-    int R, accumulate, blk_end, pad;
-};
 // block -> job: the inclusive block prefixes travel in the kernel arguments (scalar cache), not in a
 // dependent chain of global loads
 constexpr int MAX_GROUP = 48;
@@ -65,26 +56,6 @@ __device__ __forceinline__ int find_end(const Ends &e, int blk) {
 #pragma unroll 1
     for (int k = 0; k < e.n - 1; ++k) j += blk >= e.end[k] ? 1 : 0;
     return j;
-}
-
-template <class J>
-__device__ __forceinline__ int find_job(const J *jobs, int n_jobs, int blk) {
-    int lo = 0, hi = n_jobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (blk < jobs[mid].blk_end) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bf16x8 pack_hi16(const f32x4 &d0, const f32x4 &d1) {
-    // the values are bf16-exact: keep the upper halves.  k-slot q of the lane: q < 4 -> d0[q], else d1[q-4]
-    u32x4 r;
-    r[0] = __builtin_amdgcn_perm(__float_as_uint(d0[1]), __float_as_uint(d0[0]), 0x07060302u);
-    r[1] = __builtin_amdgcn_perm(__float_as_uint(d0[3]), __float_as_uint(d0[2]), 0x07060302u);
-    r[2] = __builtin_amdgcn_perm(__float_as_uint(d1[1]), __float_as_uint(d1[0]), 0x07060302u);
-    r[3] = __builtin_amdgcn_perm(__float_as_uint(d1[3]), __float_as_uint(d1[2]), 0x07060302u);
-    return __builtin_bit_cast(bf16x8, r);
 }
 
 // TA x TB 16-channel blocks of (a, b) per wave.
@@ -253,38 +224,6 @@ __global__ __launch_bounds__(256) void wgrad_pairs_kernel(const PJob *__restrict
         }
 }
 
-// dw[q] (+)= sum_r partial[r][q]: 16 quads x 16 range lanes per block, lane r sums ranges r, r+16, ...
-// and the lane sums are added in ascending r: fixed order.
-__global__ __launch_bounds__(256) void wgrad_pairs_reduce(const RJob *__restrict__ jobs, int n_jobs) {
-    __shared__ float4 part[16][16];
-    const int jn = find_job(jobs, n_jobs, (int)blockIdx.x);
-    const RJob d = jobs[jn];
-    const int first = jn == 0 ? 0 : jobs[jn - 1].blk_end;
-    const int el = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const long long q = (long long)((int)blockIdx.x - first) * 16 + el;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < d.n_quad)
-        for (int r = rl; r < d.R; r += 16) {
-            const float4 v = d.partial[(long long)r * d.n_quad + q];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    part[rl][el] = s;
-    doda_sync();
-    if (rl == 0 && q < d.n_quad) {
-        float4 t = part[0][el];
-#pragma unroll 4
-        for (int r = 1; r < 16; ++r) {
-            const float4 v = part[r][el];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
-        if (d.accumulate) {
-            const float4 old = d.dw[q];
-            t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w;
-        }
-        d.dw[q] = t;
-    }
-}
-
 struct Geo {
     int ta, tb, n_tag, n_tbg, n_og, n_range;
     bool direct;   // one range and no accumulation: the waves write dw themselves
@@ -329,99 +268,86 @@ bool eligible(const doda_wgrad_job &j) {
     return true;
 }
 
-size_t partial_bytes(const doda_wgrad_job &j) {
+static size_t partial_bytes(const doda_wgrad_job &j) {
     const Geo g = make_geo(j);
     if (g.direct) return 0;
     return align_up((size_t)g.n_range * j.K * j.ca * j.cb * 4, 256);
 }
 
-size_t desc_bytes_per_job() { return sizeof(PJob) + sizeof(RJob); }
+size_t desc_bytes_per_job() { return sizeof(PJob) + sizeof(doda_wgrad::RJob); }
 
-int prepare(const doda_wgrad_job *jobs, const int *which, int n, char *ws_base, size_t *ws_off, Prepared *out) {
-    out->desc.clear();
-    out->groups.clear();
-    std::vector<PJob> pj;
-    std::vector<RJob> rj;
-    std::vector<size_t> offs(n);
+// descriptors grouped by kernel variant (at most MAX_GROUP per launch), the jobs of a variant in queue order
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
+    Plan p;
+    p.idx = idx;
+    const int n = (int)idx.size();
     for (int k = 0; k < n; ++k) {
-        offs[k] = *ws_off;
-        *ws_off += partial_bytes(jobs[which[k]]);
+        p.part_off.push_back(p.partial_bytes);
+        p.partial_bytes += partial_bytes(jobs[idx[k]]);
+        p.n_reduce += make_geo(jobs[idx[k]]).direct ? 0 : 1;
     }
     for (int ta = 1; ta <= 2; ++ta)
         for (int tb = 1; tb <= 2; ++tb) {
-            Prepared::Group grp{ta, tb, (int)pj.size(), 0, 0};
+            Plan::Group grp{ta, tb, (int)p.order.size(), 0, 0};
             auto flush = [&]() {
-                if (grp.count) out->groups.push_back(grp);
-                grp = Prepared::Group{ta, tb, (int)pj.size(), 0, 0};
+                if (grp.count) p.groups.push_back(grp);
+                grp = Plan::Group{ta, tb, (int)p.order.size(), 0, 0};
             };
             for (int k = 0; k < n; ++k) {
-                const doda_wgrad_job &j = jobs[which[k]];
-                const Geo g = make_geo(j);
+                const Geo g = make_geo(jobs[idx[k]]);
                 if (g.ta != ta || g.tb != tb) continue;
                 if (grp.count == MAX_GROUP) flush();
-                PJob d;
-                memset(&d, 0, sizeof(d));
-                d.a = j.a; d.b = j.b;
-                d.pin = j.pair_in; d.pout = j.pair_out; d.pnum = j.pair_num; d.seg = j.pair_seg;
-                d.partial = g.direct ? j.dw : (float *)(ws_base + offs[k]);
-                d.a_bytes = (unsigned)((size_t)j.n_a * j.ca * 2);
-                d.b_bytes = (unsigned)((size_t)j.n_rows * j.cb * 2);
-                d.ca = j.ca; d.cb = j.cb; d.ld = j.pair_ld; d.K = j.K; d.n_rows = j.n_rows;
-                d.n_range = g.n_range; d.n_og = g.n_og; d.n_tag = g.n_tag; d.n_tbg = g.n_tbg;
-                d.seg_nt = j.pair_seg_nt;
                 grp.blocks += g.n_range * g.n_og * g.n_tag * g.n_tbg;
-                d.blk_end = grp.blocks;
-                pj.push_back(d);
+                p.order.push_back(k);
+                p.blk_end.push_back(grp.blocks);
                 ++grp.count;
             }
             flush();
         }
-    int r_blocks = 0;
-    for (int k = 0; k < n; ++k) {
-        const doda_wgrad_job &j = jobs[which[k]];
-        const Geo g = make_geo(j);
-        if (g.direct) continue;
-        RJob d;
-        memset(&d, 0, sizeof(d));
-        d.partial = (const float4 *)(ws_base + offs[k]);
-        d.dw = (float4 *)j.dw;
-        d.n_quad = (long long)j.K * j.ca * j.cb / 4;
-        d.R = g.n_range;
-        d.accumulate = (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0;
-        r_blocks += div_up(d.n_quad, 16);
-        d.blk_end = r_blocks;
-        rj.push_back(d);
-    }
-    out->reduce_off = pj.size() * sizeof(PJob);
-    out->n_reduce = (int)rj.size();
-    out->reduce_blocks = r_blocks;
-    out->desc.resize(pj.size() * sizeof(PJob) + rj.size() * sizeof(RJob));
-    if (!pj.empty()) memcpy(out->desc.data(), pj.data(), pj.size() * sizeof(PJob));
-    if (!rj.empty()) memcpy(out->desc.data() + out->reduce_off, rj.data(), rj.size() * sizeof(RJob));
-    return DODA_OK;
+    p.desc_bytes = p.order.size() * sizeof(PJob);
+    return p;
 }
 
-int launch(const Prepared &p, const void *desc_dev, hipStream_t s) {
+void write_desc(const Plan &p, const doda_wgrad_job *jobs, char *part, void *desc, std::vector<doda_wgrad::RJob> &reduce,
+                int *reduce_blocks) {
+    PJob *pj = (PJob *)desc;
+    for (size_t q = 0; q < p.order.size(); ++q) {
+        const int k = p.order[q];
+        const doda_wgrad_job &j = jobs[p.idx[k]];
+        const Geo g = make_geo(j);
+        PJob d;
+        memset(&d, 0, sizeof(d));
+        d.a = j.a; d.b = j.b;
+        d.pin = j.pair_in; d.pout = j.pair_out; d.pnum = j.pair_num; d.seg = j.pair_seg;
+        d.partial = g.direct ? j.dw : (float *)(part + p.part_off[k]);
+        d.a_bytes = (unsigned)((size_t)j.n_a * j.ca * 2);
+        d.b_bytes = (unsigned)((size_t)j.n_rows * j.cb * 2);
+        d.ca = j.ca; d.cb = j.cb; d.ld = j.pair_ld; d.K = j.K; d.n_rows = j.n_rows;
+        d.n_range = g.n_range; d.n_og = g.n_og; d.n_tag = g.n_tag; d.n_tbg = g.n_tbg;
+        d.seg_nt = j.pair_seg_nt;
+        d.blk_end = p.blk_end[q];
+        pj[q] = d;
+    }
+    for (size_t k = 0; k < p.idx.size(); ++k) {
+        const doda_wgrad_job &j = jobs[p.idx[k]];
+        const Geo g = make_geo(j);
+        if (!g.direct) doda_wgrad::push_reduce(reduce, reduce_blocks, part + p.part_off[k], j, g.n_range);
+    }
+}
+
+int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
     const PJob *pj = (const PJob *)desc_dev;
-    const PJob *pj_h = (const PJob *)p.desc.data();
-    for (const Prepared::Group &g : p.groups) {
+    for (const Plan::Group &g : p.groups) {
         Ends ends;
         memset(&ends, 0, sizeof(ends));
         ends.n = g.count;
-        for (int k = 0; k < g.count; ++k) ends.end[k] = pj_h[g.first + k].blk_end;
+        for (int k = 0; k < g.count; ++k) ends.end[k] = p.blk_end[g.first + k];
         if (g.ta == 1 && g.tb == 1) launch_variant<1, 1>(g.blocks, pj + g.first, ends, s);
         else if (g.ta == 2 && g.tb == 1) launch_variant<2, 1>(g.blocks, pj + g.first, ends, s);
         else if (g.ta == 1 && g.tb == 2) launch_variant<1, 2>(g.blocks, pj + g.first, ends, s);
         else launch_variant<2, 2>(g.blocks, pj + g.first, ends, s);
     }
-    int st = doda_check_launch();
-    if (st != DODA_OK) return st;
-    if (p.n_reduce > 0) {
-        hipLaunchKernelGGL(wgrad_pairs_reduce, dim3(p.reduce_blocks), dim3(256), 0, s,
-                           (const RJob *)((const char *)desc_dev + p.reduce_off), p.n_reduce);
-        st = doda_check_launch();
-    }
-    return st;
+    return doda_check_launch();
 }
 
 }  // namespace doda_pairs

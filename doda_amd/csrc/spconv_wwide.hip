@@ -17,22 +17,17 @@
 // Same sums as the gather-table kernel, bit for bit: a workgroup's rows are one ROW CHUNK of that kernel's plan for the
 // layer (make_plan: multiples of 64 rows, so a chunk starts and ends on a 32-row k-step of a tile), its k-steps run in
 // ascending row order into the same v_mfma_f32_16x16x32_bf16 chains with the same operands (absent rows are zeros in both;
-// an all-zero step adds +0 to an accumulator that started at +0), and wgrad_wide_reduce adds a slice's chunk partials in
-// wgrad_reduce_multi's order.  Switching a layer between the two kernels changes no bit of its dW.
-#include "common.hpp"
+// an all-zero step adds +0 to an accumulator that started at +0), and wgrad_wide_reduce adds a slice's chunk partials with
+// the fold wgrad_reduce_multi uses (wgrad_common.hpp wgrad_fold).  Switching a layer between the two kernels changes no bit
+// of its dW.
+#include "wgrad_common.hpp"
 #include "tilebook.hpp"
-#include "wgrad_pairs.hpp"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
 
 namespace {
-
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-typedef short s16x4w __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
 
 constexpr int WW_WAVES = 16;
 constexpr int WW_MO = (TB_K + WW_WAVES - 1) / WW_WAVES;       // offsets per wave (2)
@@ -58,22 +53,12 @@ struct WwJob {
     int pad;
 };
 
-template <class J>
-__device__ __forceinline__ int ww_find(const J *jobs, int n, int blk, bool red) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (blk < (red ? jobs[mid].red_end : jobs[mid].wg_end)) hi = mid; else lo = mid + 1;
-    }
-    return lo;
+__device__ __forceinline__ s16x4 ww_tr(unsigned addr) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(uintptr_t)addr);
 }
-
-__device__ __forceinline__ s16x4w ww_tr(unsigned addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4w *)(uintptr_t)addr);
-}
-__device__ __forceinline__ bf16x8w ww_frag(unsigned a_lo, unsigned a_hi) {
-    const s16x4w lo = ww_tr(a_lo), hi = ww_tr(a_hi);
-    return __builtin_bit_cast(bf16x8w, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+__device__ __forceinline__ bf16x8 ww_frag(unsigned a_lo, unsigned a_hi) {
+    const s16x4 lo = ww_tr(a_lo), hi = ww_tr(a_hi);
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 template <int TA, int TB>
@@ -99,13 +84,13 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
     unsigned char *rows_s = dy_s + TB_T * RB;
     const unsigned dy_base = (unsigned)(uintptr_t)dy_s, rows_base = (unsigned)(uintptr_t)rows_s;
 
-    f32x4w acc[WW_MO][TA][TB];
+    f32x4 acc[WW_MO][TA][TB];
 #pragma unroll
     for (int m = 0; m < WW_MO; ++m)
 #pragma unroll
         for (int a = 0; a < TA; ++a)
 #pragma unroll
-            for (int b = 0; b < TB; ++b) acc[m][a][b] = (f32x4w){0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < TB; ++b) acc[m][a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // the wave's k-step ks: B fragments (dy rows 32 ks + 8 g + 0..7, channel i of each block), then per owned offset the
     // A fragments (rows through the local indices, or slot t + 1 in the dense fallback for offset only_o)
@@ -114,7 +99,7 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
 #pragma unroll 1
         for (int ks = ks_begin; ks < ks_end; ++ks) {
             const int r = 32 * ks + 8 * g + q4;
-            bf16x8w bf[TB];
+            bf16x8 bf[TB];
 #pragma unroll
             for (int b = 0; b < TB; ++b) {
                 const unsigned a0 = dy_base + (unsigned)(r * RB + b * 32 + c4 * 8);
@@ -137,7 +122,7 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
                 const unsigned x0 = rows_base + s0 * RA + (unsigned)(c4 * 8), x1 = rows_base + s1 * RA + (unsigned)(c4 * 8);
 #pragma unroll
                 for (int a = 0; a < TA; ++a) {
-                    const bf16x8w af = ww_frag(x0 + 32u * a, x1 + 32u * a);
+                    const bf16x8 af = ww_frag(x0 + 32u * a, x1 + 32u * a);
 #pragma unroll
                     for (int b = 0; b < TB; ++b)
                         acc[m][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[b], acc[m][a][b], 0, 0, 0);
@@ -147,7 +132,7 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
     };
 
     // zero row (slot 0)
-    for (int e = tid; e < RA / 16; e += 1024) reinterpret_cast<u32x4w *>(rows_s)[e] = (u32x4w){0u, 0u, 0u, 0u};
+    for (int e = tid; e < RA / 16; e += 1024) reinterpret_cast<u32x4 *>(rows_s)[e] = (u32x4){0u, 0u, 0u, 0u};
     for (int tile = tile_begin; tile < tile_end; ++tile) {
         const int t0 = tile * TB_T;
         const int ks_begin = max(0, (r_begin - t0) / 32), ks_end = min(TB_T / 32, (r_end - t0 + 31) / 32);
@@ -159,14 +144,14 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
             const int e = (tid & 3) * 256 + ((tid >> 7) & 7) * 32 + ((tid >> 2) & 31);
             list_s[e] = tb_ulist[(size_t)tile * TB_UMAX + tid];
             for (int v = tid; v < TB_LIDX_BYTES / 16; v += 1024)
-                reinterpret_cast<u32x4w *>(smem + WW_LIST_BYTES)[v] =
-                    reinterpret_cast<const u32x4w *>(tb_lidx + (size_t)tile * (TB_LIDX_BYTES / 4))[v];
+                reinterpret_cast<u32x4 *>(smem + WW_LIST_BYTES)[v] =
+                    reinterpret_cast<const u32x4 *>(tb_lidx + (size_t)tile * (TB_LIDX_BYTES / 4))[v];
         }
         for (int v = tid; v < TB_T * (RB / 16); v += 1024) {
             const int t = v / (RB / 16), f = v - t * (RB / 16);
-            u32x4w val = (u32x4w){0u, 0u, 0u, 0u};
-            if (t0 + t < d.n_rows) val = *reinterpret_cast<const u32x4w *>(d.dy + (size_t)(t0 + t) * d.cb + cb0 + f * 8);
-            *reinterpret_cast<u32x4w *>(dy_s + t * RB + f * 16) = val;
+            u32x4 val = (u32x4){0u, 0u, 0u, 0u};
+            if (t0 + t < d.n_rows) val = *reinterpret_cast<const u32x4 *>(d.dy + (size_t)(t0 + t) * d.cb + cb0 + f * 8);
+            *reinterpret_cast<u32x4 *>(dy_s + t * RB + f * 16) = val;
         }
         doda_sync();
         if (listed) {
@@ -174,8 +159,8 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
             for (int v = tid; v < ucount * (RA / 16); v += 1024) {
                 const int e = v / (RA / 16), f = v - e * (RA / 16);
                 const int row = list_s[e];
-                *reinterpret_cast<u32x4w *>(rows_s + (e + 1) * RA + f * 16) =
-                    *reinterpret_cast<const u32x4w *>(d.x + (size_t)row * d.ca + ca0 + f * 8);
+                *reinterpret_cast<u32x4 *>(rows_s + (e + 1) * RA + f * 16) =
+                    *reinterpret_cast<const u32x4 *>(d.x + (size_t)row * d.ca + ca0 + f * 8);
             }
             doda_sync();
             multiply(false, 0, ks_begin, ks_end);
@@ -186,9 +171,9 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
                 for (int v = tid; v < TB_T * (RA / 16); v += 1024) {
                     const int t = v / (RA / 16), f = v - t * (RA / 16);
                     const int row = t0 + t < d.n_rows ? d.tbl[(size_t)o * d.ld + t0 + t] : -1;
-                    u32x4w val = (u32x4w){0u, 0u, 0u, 0u};
-                    if (row >= 0) val = *reinterpret_cast<const u32x4w *>(d.x + (size_t)row * d.ca + ca0 + f * 8);
-                    *reinterpret_cast<u32x4w *>(rows_s + (t + 1) * RA + f * 16) = val;
+                    u32x4 val = (u32x4){0u, 0u, 0u, 0u};
+                    if (row >= 0) val = *reinterpret_cast<const u32x4 *>(d.x + (size_t)row * d.ca + ca0 + f * 8);
+                    *reinterpret_cast<u32x4 *>(rows_s + (t + 1) * RA + f * 16) = val;
                 }
                 doda_sync();
                 multiply(true, o, ks_begin, ks_end);
@@ -218,7 +203,7 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
 
 __global__ __launch_bounds__(1024) void wgrad_wide(const WwJob *__restrict__ jobs, int n_jobs) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[WW_SMEM];
-    const int j = ww_find(jobs, n_jobs, (int)blockIdx.x, false);
+    const int j = find_job<WwJob, &WwJob::wg_end>(jobs, n_jobs, (int)blockIdx.x);
     const WwJob d = jobs[j];
     const int local = (int)blockIdx.x - (j == 0 ? 0 : jobs[j - 1].wg_end);
 #define WW_CASE(A, B) if (d.ta == A && d.tb_ == B) { ww_body<A, B>(d, local, smem); return; }
@@ -226,47 +211,18 @@ __global__ __launch_bounds__(1024) void wgrad_wide(const WwJob *__restrict__ job
 #undef WW_CASE
 }
 
-// dw[o][ci][co] (+)= sum_p part[slice][p][o][ci'][co'] in wgrad_reduce_multi's form and order: a block holds EL = 256 / RL
-// element quads x RL chunk lanes (RL = the smallest power of two >= min(P, 16)); lane l sums chunks l, l + RL, ... starting
-// from 0, and the lane sums are added in ascending l (then dw, when accumulating)
+// dw[o][ci][co] (+)= sum_p part[slice][p][o][ci'][co']: the shared fold over the P chunk partials of the quad's slice
 __global__ __launch_bounds__(256) void wgrad_wide_reduce(const WwJob *__restrict__ jobs, int n_jobs) {
-    __shared__ float4 part[256];
-    const int j = ww_find(jobs, n_jobs, (int)blockIdx.x, true);
+    const int j = find_job<WwJob, &WwJob::red_end>(jobs, n_jobs, (int)blockIdx.x);
     const WwJob d = jobs[j];
-    const int blk = (int)blockIdx.x - (j == 0 ? 0 : jobs[j - 1].red_end);
-    int RL = 1;
-    while (RL < 16 && RL < d.P) RL *= 2;
-    const int EL = 256 / RL, el = (int)threadIdx.x % EL, rl = (int)threadIdx.x / EL;
-    const long long q = (long long)blk * EL + el, n_quad = (long long)TB_K * d.ca * d.cb / 4;
     const int CIS = 16 * d.ta, COS = 16 * d.tb_, SLICE = TB_K * CIS * COS;
-    const float *src = nullptr;
-    if (q < n_quad) {
+    wgrad_fold((int)blockIdx.x - (j == 0 ? 0 : jobs[j - 1].red_end), d.P, (long long)TB_K * d.ca * d.cb / 4, SLICE / 4,
+               reinterpret_cast<float4 *>(d.dw), d.accumulate, [&](long long q) {
         const long long e = 4 * q;
         const int co = (int)(e % d.cb), ci = (int)((e / d.cb) % d.ca), o = (int)(e / ((long long)d.ca * d.cb));
         const int slice = (ci / CIS) * d.n_sb + co / COS;
-        src = d.part + ((size_t)slice * d.P) * SLICE + ((size_t)o * CIS + ci % CIS) * COS + co % COS;
-    }
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (src)
-        for (int r = rl; r < d.P; r += RL) {
-            const float4 v = *reinterpret_cast<const float4 *>(src + (size_t)r * SLICE);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    part[rl * EL + el] = s;
-    doda_sync();
-    if (rl == 0 && src) {
-        float4 t = part[el];
-        for (int r = 1; r < RL; ++r) {
-            const float4 v = part[r * EL + el];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
-        float4 *dst = reinterpret_cast<float4 *>(d.dw) + q;
-        if (d.accumulate) {
-            const float4 old = *dst;
-            t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w;
-        }
-        *dst = t;
-    }
+        return reinterpret_cast<const float4 *>(d.part + ((size_t)slice * d.P) * SLICE + ((size_t)o * CIS + ci % CIS) * COS + co % COS);
+    });
 }
 
 // slice shape of a job: TB = the widest output-channel slice of at most 7 blocks dividing cb / 16, TA = the widest input
@@ -299,17 +255,18 @@ bool eligible(const doda_wgrad_job &j) {
 
 // The launch's plan: jobs longest first (most rows), one workgroup per (channel slice, row chunk of the gather-table
 // kernel's plan: rows_per_chunk[k] for job idx[k]).  Identical inputs give an identical plan.
-struct Plan { std::vector<int> order; std::vector<WwJob> d; int wgs = 0, red_blocks = 0; size_t part_bytes = 0; };
-
-static Plan plan(const doda_wgrad_job *jobs, const int *idx, const int *rows_per_chunk, int n) {
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx, const std::vector<int> &rows_per_chunk) {
     Plan pl;
-    for (int k = 0; k < n; ++k) pl.order.push_back(k);
-    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int a, int b) { return jobs[idx[a]].n_rows > jobs[idx[b]].n_rows; });
-    for (int kk : pl.order) {
+    pl.n = (int)idx.size();
+    std::vector<int> order;
+    for (int k = 0; k < pl.n; ++k) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return jobs[idx[a]].n_rows > jobs[idx[b]].n_rows; });
+    std::vector<WwJob> desc;
+    for (int kk : order) {
         const doda_wgrad_job &j = jobs[idx[kk]];
         WwJob d;
         d.x = (const unsigned short *)j.a; d.dy = (const unsigned short *)j.b; d.tbl = j.tbl; d.tb = j.tilebook;
-        d.dw = j.dw; d.part = nullptr;
+        d.dw = j.dw;
         d.ca = j.ca; d.cb = j.cb; d.ld = j.ld; d.n_rows = j.n_rows; d.nt = (j.n_rows + TB_T - 1) / TB_T;
         ww_shape(j.ca, j.cb, &d.ta, &d.tb_);
         d.n_sb = j.cb / (16 * d.tb_);
@@ -317,39 +274,32 @@ static Plan plan(const doda_wgrad_job *jobs, const int *idx, const int *rows_per
         d.P = (j.n_rows + d.rpc - 1) / d.rpc;
         d.accumulate = (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0;
         const int slices = (j.ca / (16 * d.ta)) * d.n_sb;
-        d.part = (float *)(uintptr_t)pl.part_bytes;      // offset until launch()
-        pl.part_bytes += align_up((size_t)slices * d.P * TB_K * 256 * d.ta * d.tb_ * 4, 256);
+        d.part = (float *)(uintptr_t)pl.partial_bytes;      // offset until write_desc()
+        pl.partial_bytes += align_up((size_t)slices * d.P * TB_K * 256 * d.ta * d.tb_ * 4, 256);
         pl.wgs += slices * d.P;
         d.wg_end = pl.wgs;
-        int rl = 1;
-        while (rl < 16 && rl < d.P) rl *= 2;
-        pl.red_blocks += (int)div_up((long long)TB_K * j.ca * j.cb / 4, 256 / rl);   // (wgrad_wide_reduce: 256 / RL quads per block)
+        pl.red_blocks += doda_wgrad::reduce_blocks((long long)TB_K * j.ca * j.cb / 4, d.P);
         d.red_end = pl.red_blocks;
         d.pad = 0;
-        pl.d.push_back(d);
+        desc.push_back(d);
     }
+    pl.desc_bytes = desc.size() * sizeof(WwJob);
+    pl.desc.resize(pl.desc_bytes);
+    if (pl.desc_bytes) memcpy(pl.desc.data(), desc.data(), pl.desc_bytes);
     return pl;
 }
 
-size_t partial_bytes(const doda_wgrad_job *jobs, const int *idx, const int *rows_per_chunk, int n) {
-    return n ? plan(jobs, idx, rows_per_chunk, n).part_bytes : 0;
-}
 size_t desc_bytes_per_job() { return sizeof(WwJob); }
 
-// descriptors: host copy appended to `desc` (the caller uploads it); returns the launch's plan
-void prepare(const doda_wgrad_job *jobs, const int *idx, const int *rows_per_chunk, int n, void *part,
-             std::vector<unsigned char> &desc, int *wgs, int *red_blocks) {
-    Plan pl = plan(jobs, idx, rows_per_chunk, n);
-    for (WwJob &d : pl.d) d.part = (float *)((char *)part + (uintptr_t)d.part);
-    desc.resize(pl.d.size() * sizeof(WwJob));
-    memcpy(desc.data(), pl.d.data(), desc.size());
-    *wgs = pl.wgs;
-    *red_blocks = pl.red_blocks;
+void write_desc(const Plan &p, char *part, void *desc) {
+    if (p.desc_bytes) memcpy(desc, p.desc.data(), p.desc_bytes);
+    WwJob *d = (WwJob *)desc;
+    for (int k = 0; k < p.n; ++k) d[k].part = (float *)(part + (uintptr_t)d[k].part);
 }
 
-int launch(const void *desc_dev, int n, int wgs, int red_blocks, hipStream_t s) {
-    hipLaunchKernelGGL(wgrad_wide, dim3(wgs), dim3(1024), 0, s, (const WwJob *)desc_dev, n);
-    hipLaunchKernelGGL(wgrad_wide_reduce, dim3(red_blocks), dim3(256), 0, s, (const WwJob *)desc_dev, n);
+int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
+    hipLaunchKernelGGL(wgrad_wide, dim3(p.wgs), dim3(1024), 0, s, (const WwJob *)desc_dev, p.n);
+    hipLaunchKernelGGL(wgrad_wide_reduce, dim3(p.red_blocks), dim3(256), 0, s, (const WwJob *)desc_dev, p.n);
     return doda_check_launch();
 }
 

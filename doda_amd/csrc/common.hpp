@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/doda_hip.h"
 
 #define DODA_WAVE 64
@@ -24,6 +25,14 @@ static inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static inline long long env_ll(const char *name, long long dflt) {
     const char *e = getenv(name);
     return e && *e ? atoll(e) : dflt;
+}
+
+// a run-time flag as a compile-time constant: with_bool(flag, [&](auto b) { kernel<decltype(b)::value>(...); })
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F>
+static inline void with_bool(bool flag, F &&f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 static inline uint32_t next_pow2(uint32_t x) {

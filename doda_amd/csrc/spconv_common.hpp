@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "bn_totals.hpp"
+#include "gather_plan.hpp"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -99,7 +100,7 @@ struct EpiArgs {   // plain data, shared across translation units
     const float *bn_mean, *bn_invstd, *bn_gamma, *bn_beta;   // [nc] each
     int bn_relu;
     int res_bcast;           // ABI 6: `res` is ONE row [nc] added to every output row (a bias): conv_fast only
-    int f32_split;           // round 5: fp32 units as two bf16 MFMAs on head / tail splits (mma_f32_k16); set by run_gather
+    int f32_split;           // round 5: fp32 units as two bf16 MFMAs on head / tail splits (mma_f32_k16); set by run_gather from the route's policy
     double *stats_tot;       // ABI 9: [DODA_STATS_SLOTS][2][nc / 4][16] totals (4 of 16 used), accumulated with fp64 atomics INSTEAD of the rows, or null
     // ABI 11: row strides in ELEMENTS of x / y / res / bn_x (0: dense — kc, nc, nc, nc): a column slice of a wider matrix, e.g. one
     // half of a U-Net level's concatenation (reference model/unet_block.py:89-93), is read / written in place.  conv_fast only.
@@ -343,25 +344,19 @@ __device__ __forceinline__ u32x4 pre_piece(const u32x4 &x, const u32x4 &u, const
 }  // namespace
 #endif
 
+// Operands of a planned gather call: what a family's launcher hands to the kernel the route names (gather_plan.hpp)
+struct GatherOperands {
+    const void *x, *wp;
+    const int32_t *tbl;
+    void *y;
+    const void *res, *tilebook;
+    int kc, nc, K, ld, n_out;
+    EpiArgs ep;
+    const PreArgs *pre;    // null, or the folded BatchNorm of a route with PRE != 0
+};
 namespace doda_tile {
-bool enabled();   // doda_set_option(DODA_OPT_TILE_KERNEL)
-void set_enabled(bool on);
-bool pipeline_enabled();   // doda_set_option(DODA_OPT_TILE_PIPELINE): conv_tile16 for 16 -> 16 layers of many tiles
-void set_pipeline(bool on);
-bool dual_enabled();       // doda_set_option(DODA_OPT_TILE_DUAL): both channel blocks of a 32-output-channel layer in one pass
-void set_dual(bool on);
-bool up_enabled();         // doda_set_option(DODA_OPT_CONV_UP): conv_up32 for one-source-per-row tables
-void set_up(bool on);
-// conv_tile over `tilebook` (doda_tilebook_build of tbl).  mode 0: bf16 16 channels, 1: bf16 32 channels, 2: fp32 16
-// channels; out32: fp32 output rows.  *n_part (if given) receives the number of statistics rows.
-int launch_conv_tile(int mode, bool out32, const void *x, unsigned x_bytes, const void *wp, unsigned wp_bytes, int nc, int NB,
-                     const int32_t *tbl, int ld, int n_out, const void *tilebook, void *y, unsigned y_bytes, const void *res,
-                     const EpiArgs &ep, int *n_part, hipStream_t s);
-// conv_up32: bf16, 32 input channels, K <= 8, a table with (about) one source row per output row (inverse convolution forward,
-// strided convolution data gradient); wp = wide-packed fragments [o][nb][64] x 16 B.  *n_part: statistics rows (one per 256 rows).
-int launch_conv_up32(bool out32, const void *x, unsigned x_bytes, const void *wp, unsigned wp_bytes, int nc, int NB, int K,
-                     const int32_t *tbl, int ld, int n_out, void *y, unsigned y_bytes, const void *res, const EpiArgs &ep,
-                     int *n_part, hipStream_t s);
+// conv_up32 / conv_tile / conv_tile16 (spconv_tile.hip), as route.family says
+int launch(const GatherRoute &route, const GatherOperands &a, hipStream_t s);
 }  // namespace doda_tile
 
 namespace doda_layers {
@@ -374,9 +369,6 @@ void set_bwd_rows(long long v);
 }  // namespace doda_layers
 
 namespace doda_wlds {
-bool enabled();
-void set_enabled(bool on);
-// bf16 48 -> 48 channels, K = 27, weights in LDS (spconv_wlds.hip); wp = wide-packed fragments [27][2][3][64] x 16 B
-int launch_conv48(const void *x, unsigned x_bytes, const void *wp, const int32_t *tbl, unsigned tbl_bytes, int ld, int n_out,
-                  void *y, unsigned y_bytes, const void *res, const EpiArgs &ep, int *n_part, hipStream_t s);
+// conv_wlds48: bf16 48 -> 48 channels, K = 27, weights in LDS (spconv_wlds.hip); wp = wide-packed fragments [27][2][3][64] x 16 B
+int launch(const GatherRoute &route, const GatherOperands &a, hipStream_t s);
 }  // namespace doda_wlds

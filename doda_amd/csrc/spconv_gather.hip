@@ -937,278 +937,124 @@ constexpr bool pre_shape() {
     return SPLIT && ((NBW == 1 && S == 1) || (NBW == 4 && S == 2)) && (std::is_same<P, PBF16W>::value || std::is_same<P, PF32>::value);
 }
 
-template <class P, int NBW, int S, bool SPLIT = false>
-int launch_fast(const typename P::elem *x, int kc, const void *wp, size_t wp_bytes, int nc, int NB,
-                const int32_t *tbl, int ld, int K, int n_out, long long n_in, void *y, bool out32,
-                const void *res, const EpiArgs &ep_in, int *n_part, hipStream_t s, const PreArgs *pre = nullptr) {
-    if constexpr (std::is_same<P, PF32>::value) {   // fp32 layers of many rows: the bf16 head / tail instantiation
-        if (ep_in.f32_split && !(pre && pre->kind))
-            return launch_fast<PF32S, NBW, S, SPLIT>(x, kc, wp, wp_bytes, nc, NB, tbl, ld, K, n_out, n_in, y, out32, res, ep_in, n_part, s);
-    }
-    const dim3 grid(div_up(n_out, (SPLIT ? 1 : 4) * 16 * S) * div_up(NB, NBW)), block(256);
-    if (n_part) *n_part = div_up(n_out, (SPLIT ? 1 : 4) * 16 * S);
-    const EpiArgs &ep = ep_in;
+// the legal (NBW, S, SPLIT) triples of conv_fast; conv_gather takes the unsplit ones.  The set of triples defines what is compiled;
+// their order only the order in which the compiler emits the kernels (the last entry first).  With this order every kernel's
+// instruction stream equalled the one under the ladders this table replaced; another order may schedule a kernel differently.
+template <int NBW_, int S_, bool SPLIT_> struct Shape { static constexpr int NBW = NBW_, S = S_; static constexpr bool SPLIT = SPLIT_; };
+template <class... Sh> struct Shapes {};
+typedef Shapes<Shape<8, 1, false>, Shape<4, 1, false>, Shape<4, 2, false>, Shape<3, 1, false>, Shape<2, 1, false>, Shape<2, 2, false>,
+               Shape<2, 4, false>, Shape<1, 1, false>, Shape<1, 2, false>, Shape<3, 2, true>, Shape<4, 2, true>, Shape<1, 1, true>> FastShapes;
+template <class F, class... Sh>
+int with_shape(const GatherRoute &r, Shapes<Sh...>, F &&f) {
+    int st = DODA_ERR_UNSUPPORTED;
+    (void)((r.NBW == Sh::NBW && r.S == Sh::S && r.split == Sh::SPLIT && (st = f(Sh{}), true)) || ...);
+    return st;
+}
+
+template <class P, class Sh>
+int launch_fast(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
+    constexpr int NBW = Sh::NBW, S = Sh::S;
+    constexpr bool SPLIT = Sh::SPLIT;
     // Ring depth.  Re-measured after the EXEC-masked gathers and the wide / pair units went in: with
     // every load hitting L1 (ablation) the kernel time did not move, i.e. the unit loop is paced by
     // instruction issue and by how many waves a SIMD can interleave, not by memory latency.  Depth 8
     // cost 124 VGPRs (4 waves per SIMD); depth 3: level-1 16->16 52 -> 38 us, level-2 32->32 37 -> 32 us.
     // (round 6: depth 6 for the 16-row split blocks of the coarse levels — ~20 units per wave, one wave per SIMD — measured the same
     // 8.1-8.2 us per launch: those kernels are not paced by the ring either)
-    constexpr int D = 3;
-    const size_t esz = sizeof(typename P::elem);
-    const unsigned xb = (unsigned)(ep.x_ld ? ((size_t)(n_in - 1) * ep.x_ld + kc) * esz : (size_t)n_in * kc * esz);
-    const unsigned tb = (unsigned)((size_t)K * ld * 4);
-    const PreArgs none{};
-    if (pre && pre->kind) {
-        if constexpr (pre_shape<P, NBW, S, SPLIT>()) {
-            if (out32 && esz != 4) return DODA_ERR_UNSUPPORTED;
-            const unsigned yb = (unsigned)(ep.y_ld ? ((size_t)(n_out - 1) * ep.y_ld + nc) * esz : (size_t)n_out * nc * esz);
-#define DODA_PRE_GO(KIND)                                                                                            \
-            do {                                                                                                     \
-                if (ep.stats)                                                                                        \
-                    hipLaunchKernelGGL((conv_fast<P, NBW, S, D, false, SPLIT, true, KIND>), grid, block, 0, s, x, xb, kc, wp,  \
-                                       (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, *pre);     \
-                else                                                                                                 \
-                    hipLaunchKernelGGL((conv_fast<P, NBW, S, D, false, SPLIT, false, KIND>), grid, block, 0, s, x, xb, kc, wp, \
-                                       (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, *pre);     \
-            } while (0)
-            if ((pre->kind & 0xff) == 1) DODA_PRE_GO(1);
-            else if ((pre->kind & 0xff) == 2) DODA_PRE_GO(2);
-            else if ((pre->kind & 0xff) == 3) DODA_PRE_GO(3);
-            else return DODA_ERR_INVALID;
-#undef DODA_PRE_GO
+    constexpr int D = GP_RING_DEPTH;
+    const auto go = [&](auto kernel, const PreArgs &pre) {
+        hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.block), 0, s, (const typename P::elem *)a.x, r.x_bytes, a.kc, a.wp, r.w_bytes, a.nc,
+                           r.geo.NB, a.tbl, r.tbl_bytes, a.ld, a.K, a.n_out, a.y, r.y_bytes, a.res, a.ep, pre);
+    };
+    if constexpr (pre_shape<P, NBW, S, SPLIT>()) {   // (plan_gather names a PRE for these shapes only)
+        if (r.pre) {
+            with_bool(r.stats, [&](auto st) {
+                constexpr bool ST = decltype(st)::value;
+                if (r.pre == 1) go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 1>, *a.pre);
+                else if (r.pre == 2) go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 2>, *a.pre);
+                else go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 3>, *a.pre);
+            });
             return doda_check_launch();
-        } else {
-            return DODA_ERR_UNSUPPORTED;
         }
     }
-    if (out32 && sizeof(typename P::elem) != 4) {
-        const unsigned yb = (unsigned)(ep.y_ld ? ((size_t)(n_out - 1) * ep.y_ld + nc) * 4 : (size_t)n_out * nc * 4);
-        if (ep.stats)
-            hipLaunchKernelGGL((conv_fast<P, NBW, S, D, true, SPLIT, true>), grid, block, 0, s, x, xb, kc, wp,
-                               (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, none);
-        else
-            hipLaunchKernelGGL((conv_fast<P, NBW, S, D, true, SPLIT, false>), grid, block, 0, s, x, xb, kc, wp,
-                               (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, none);
-    } else {
-        const unsigned yb = (unsigned)(ep.y_ld ? ((size_t)(n_out - 1) * ep.y_ld + nc) * esz : (size_t)n_out * nc * esz);
-        if (ep.stats)
-            hipLaunchKernelGGL((conv_fast<P, NBW, S, D, false, SPLIT, true>), grid, block, 0, s, x, xb, kc, wp,
-                               (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, none);
-        else
-            hipLaunchKernelGGL((conv_fast<P, NBW, S, D, false, SPLIT, false>), grid, block, 0, s, x, xb, kc, wp,
-                               (unsigned)wp_bytes, nc, NB, tbl, tb, ld, K, n_out, y, yb, res, ep, none);
-    }
+    with_bool(r.out32, [&](auto o32) { with_bool(r.stats, [&](auto st) {
+        go(conv_fast<P, NBW, S, D, decltype(o32)::value, SPLIT, decltype(st)::value>, PreArgs{});
+    }); });
     return doda_check_launch();
 }
 
-template <class T, int NBW, int S>
-int launch(const typename T::elem *x, int kc, const typename T::frag *wp, int nc, int NB,
-           const int32_t *tbl, int ld, int K, int n_out, typename T::elem *y, int vec_ok,
-           const typename T::elem *res, hipStream_t s) {
-    const dim3 grid(div_up(n_out, 4 * 16 * S) * div_up(NB, NBW)), block(256);
-    hipLaunchKernelGGL((conv_gather<T, NBW, S>), grid, block, 0, s, x, kc, wp, nc, NB, tbl, ld, K,
-                       n_out, y, vec_ok, res);
-    return doda_check_launch();
-}
-
-template <class T> struct FastPolicy;
-template <> struct FastPolicy<F32> { typedef PF32 narrow; typedef PF32 wide; typedef PF32 pair; };
-template <> struct FastPolicy<BF16> { typedef PBF16 narrow; typedef PBF16W wide; typedef PBF16P pair; };
-
-// Fragment packing the fast kernel uses for a layer: 0x10 wide (bf16, >= 32 input channels),
-// 0x20 pair (bf16, exactly 16 input channels, more than one offset), 0 narrow.
-inline int pack_mode(int K, int kc, int elem_bytes) {
-    if (elem_bytes == 2 && kc >= 32 && kc % 8 == 0) return 0x10;
-    if (elem_bytes == 2 && kc == 16 && K >= 2) return 0x20;
-    return 0;
-}
-
-template <class T>
-int run_gather(const void *x_, int kc, const float *w, int nc, const int32_t *tbl, int ld, int K,
-               int n_out, void *y_, int wl, void *ws, size_t ws_bytes, long long n_in, bool out32,
-               const void *res, hipStream_t s,
-               const EpiArgs &ep_arg = EpiArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr},
-               int *n_part = nullptr, const void *tilebook = nullptr, int tilebook_rows = 0, const PreArgs *pre = nullptr) {
+template <class T, class Sh>
+int launch_generic(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
     typedef typename T::elem elem;
-    typedef typename T::frag frag;
-    const elem *x = (const elem *)x_;
-    elem *y = (elem *)y_;
-    const int NB = (nc + 15) / 16;
-    EpiArgs ep = ep_arg;
-    {   // OPT-IN: fp32 layers of at least DODA_F32_SPLIT_ROWS output rows (e.g. 65536; 0: all; unset / -1: none) multiply bf16
-        // head / tail splits of both operands (spconv_common.hpp mma_f32_k16).  Measured (round 5): fp32 step 11.85 -> 11.1 ms
-        // with every weight gradient and the >= 65536-row gathers split, every 1e-4 kernel test and the golden's gradient
-        // NORMS (5e-3) still green — but the elementwise distance of the U-Net's gradients from the fp64 golden grows from
-        // ~1e-3 to ~7e-3 (2^-16 products through 70 layers), and fp32 is this repository's PARITY precision: exact by default
-        static const long long min_rows = [] { const char *e = getenv("DODA_F32_SPLIT_ROWS"); return e && *e ? atoll(e) : -1ll; }();
-        ep.f32_split = (sizeof(elem) == 4 && min_rows >= 0 && (long long)n_out >= min_rows) ? 1 : 0;
-    }
-    // all rows the table may reference must sit inside the 2 GB buffer window of the fast path
-    const bool x_rows_bytes_ok = n_in > 0 && (size_t)n_in * kc * sizeof(elem) < 0x7ffffff0ull;
-    const size_t va = 4 * sizeof(elem);  // vector access granule
-    const int vec_ok = (kc % 4 == 0) && (nc % 4 == 0) && ((uintptr_t)x % va == 0) &&
-                       ((uintptr_t)y % va == 0);
-    // ABI 11: row strides (column slices of wider matrices) and the folded BatchNorm in conv_fast; ABI 12: the LDS-staged kernels
-    // (conv_tile*, conv_up32, conv_wlds48) take strided OUTPUT-side operands (y, residual, BatchNorm input) — their gathered x stays dense
-    const bool strided = (ep.x_ld && ep.x_ld != (unsigned)kc) || ep.y_ld || ep.res_ld || ep.bnx_ld;
-    const bool x_dense = !ep.x_ld || ep.x_ld == (unsigned)kc;
-    const bool folded = pre && pre->kind != 0;
-    const size_t x_ld = ep.x_ld ? ep.x_ld : (size_t)kc, y_ld = ep.y_ld ? ep.y_ld : (size_t)nc;
-    const bool ld_ok = x_ld % 4 == 0 && y_ld % 4 == 0 && ep.res_ld % 4 == 0 && ep.bnx_ld % 4 == 0 &&
-                       (size_t)n_in * x_ld * sizeof(elem) < 0x7ffffff0ull && (size_t)n_out * y_ld * 4 < 0x7fffffffull &&
-                       (size_t)n_out * (ep.res_ld ? ep.res_ld : (size_t)nc) * 4 < 0x7fffffffull &&
-                       (size_t)n_out * (ep.bnx_ld ? ep.bnx_ld : (size_t)nc) * 4 < 0x7fffffffull;
-    const bool fast = (kc % 4 == 0) && (nc % 4 == 0) && ((uintptr_t)x % 16 == 0) &&
-                      ((uintptr_t)y % 16 == 0) && ((size_t)n_out * nc * 4 < 0x7fffffffull) &&
-                      ((size_t)K * ld * 4 < 0xffffffffull) && x_rows_bytes_ok && ld_ok;
-    if ((strided || folded) && !fast) return DODA_ERR_UNSUPPORTED;
-    if (out32 && sizeof(elem) != 4 && !fast) return DODA_ERR_UNSUPPORTED;
-    if (ep.stats && !fast) return DODA_ERR_UNSUPPORTED;   // the statistics ride in the fast kernel's epilogue only
-    const int mode = pack_mode(K, kc, (int)sizeof(elem));
-    const bool wide = fast && mode == 0x10, pair = fast && mode == 0x20;
+    if constexpr (!Sh::SPLIT)
+        hipLaunchKernelGGL((conv_gather<T, Sh::NBW, Sh::S>), dim3(r.grid), dim3(r.block), 0, s, (const elem *)a.x, a.kc,
+                           (const typename T::frag *)a.wp, a.nc, r.geo.NB, a.tbl, a.ld, a.K, a.n_out, (elem *)a.y, (int)r.vec_ok,
+                           (const elem *)a.res);
+    return Sh::SPLIT ? DODA_ERR_UNSUPPORTED : doda_check_launch();
+}
+
+// conv_gather / conv_fast: the route's element size and policy as the storage / policy class
+int launch_dense(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
+    return with_shape(r, FastShapes{}, [&](auto sh) {
+        typedef decltype(sh) Sh;
+        if (r.family == GF_GENERIC) return r.esz == 4 ? launch_generic<F32, Sh>(r, a, s) : launch_generic<BF16, Sh>(r, a, s);
+        if (r.esz == 4) return r.policy == GP_F32_SPLIT ? launch_fast<PF32S, Sh>(r, a, s) : launch_fast<PF32, Sh>(r, a, s);
+        return r.policy == GP_WIDE ? launch_fast<PBF16W, Sh>(r, a, s) : r.policy == GP_PAIR ? launch_fast<PBF16P, Sh>(r, a, s)
+                                                                                          : launch_fast<PBF16, Sh>(r, a, s);
+    });
+}
+
+// The process-wide switches of the selection: the environment once, at the first gather call or option call, then doda_set_option
+GatherSwitches switches_from_env() {
+    GatherSwitches sw;
+    sw.f32_split_rows = env_ll("DODA_F32_SPLIT_ROWS", -1);
+    sw.pre_small_blocks = env_ll("DODA_PRE_SMALL_BLOCKS", 2048);
+    sw.f32_conv_tile = !(getenv("DODA_F32_CONV_TILE") && getenv("DODA_F32_CONV_TILE")[0] == '0');
+    const int m = (int)env_ll("DODA_TILE16_MIN_TILES", GP_TILE_MAX_GROUPS + 1);
+    sw.tile16_min_tiles = m < GP_TILE16_GROUPS ? GP_TILE16_GROUPS : m;   // (every one of its 512 workgroups must own a tile)
+    sw.tile_dual = !(getenv("DODA_TILE_DUAL") && getenv("DODA_TILE_DUAL")[0] == '0');
+    sw.conv_up = !(getenv("DODA_CONV_UP") && getenv("DODA_CONV_UP")[0] == '0');
+    return sw;
+}
+GatherSwitches &gather_switches() {
+    static GatherSwitches sw = switches_from_env();
+    return sw;
+}
+static_assert(GP_TILE_ROWS == TB_T && GP_TILE_K == TB_K && GP_PRE_MAX_C == PRE_MAX_C, "gather_plan.hpp restates these constants");
+
+// validate (doda_spconv_gather_ex), plan, pack, launch: an error return has enqueued nothing
+int run_gather(const GatherCall &c, GatherOperands &a, const float *w, void *ws, int *n_part, hipStream_t s) {
+    const GatherRoute r = plan_gather(c, gather_switches());
     {   // DODA_TRACE_GATHER=1: one line per call on stderr (which layer shapes reach which kernel: tools/gathermap.py)
         static const bool trace = getenv("DODA_TRACE_GATHER") && getenv("DODA_TRACE_GATHER")[0] == '1';
-        if (trace)
-            fprintf(stderr, "doda_gather K=%d kc=%d nc=%d n_out=%d n_in=%lld layout=%d esz=%d out32=%d stats=%d bn=%d res=%d tilebook=%d\n",
-                    K, kc, nc, n_out, n_in, wl & 0xff, (int)sizeof(elem), (int)out32, ep.stats ? 1 : 0, ep.bn_x ? 1 : 0,
-                    res ? 1 : 0, tilebook ? 1 : 0);
+        if (trace) {
+            char name[96];
+            route_name(r, name, sizeof name);
+            fprintf(stderr, "doda_gather K=%d kc=%d nc=%d n_out=%d n_in=%lld layout=%d esz=%d out32=%d stats=%d bn=%d res=%d tilebook=%d route=%s grid=%u block=%u parts=%d\n",
+                    c.K, c.kc, c.nc, c.n_out, c.n_in, c.layout, c.esz, (int)c.out32, c.stats ? 1 : 0, a.ep.bn_x ? 1 : 0,
+                    a.res ? 1 : 0, c.tilebook ? 1 : 0, name, r.grid, r.block, r.n_part);
+        }
     }
-    const int n_chunk = wide ? (kc + 31) / 32 : (kc + 15) / 16;
-    const size_t need = pair ? (size_t)K * NB * 32 * 16 : (size_t)K * n_chunk * NB * 64 * (wide ? 16 : sizeof(frag));
-    const void *wp;
-    if (wl & 0x100) {  // `w` already holds fragment-packed weights (doda_spconv_pack_multi)
-        if (mode != 0 && !fast) return DODA_ERR_UNSUPPORTED;  // packed for a mode this call cannot take
-        wp = (const void *)w;
-    } else {
-        if (!ws || ws_bytes < need) return DODA_ERR_WORKSPACE;
-        wp = ws;
-        const long long total = pair ? (long long)K * NB * 32 : (long long)K * n_chunk * NB * 64;
-        if (wide || pair)
-            hipLaunchKernelGGL(pack_weights_wide, dim3(div_up(total, 256)), dim3(256), 0, s, w, K, kc, nc,
-                               n_chunk, NB, wl & 3, (u32x4_t *)ws, pair ? 1 : 0);
+    if (r.status != DODA_OK) return r.status;
+    if (c.packed) a.wp = w;   // `w` already holds fragment-packed weights (doda_spconv_pack_multi)
+    else {
+        a.wp = ws;
+        const dim3 grid(div_up(r.geo.frags, 256)), block(256);
+        if (r.geo.mode != 0)
+            hipLaunchKernelGGL(pack_weights_wide, grid, block, 0, s, w, c.K, c.kc, c.nc, r.geo.n_chunk, r.geo.NB, c.layout, (u32x4_t *)ws,
+                               r.geo.mode == 0x20 ? 1 : 0);
+        else if (c.esz == 4)
+            hipLaunchKernelGGL((pack_weights<F32>), grid, block, 0, s, w, c.K, c.kc, c.nc, r.geo.n_chunk, r.geo.NB, c.layout, (F32::frag *)ws);
         else
-            hipLaunchKernelGGL((pack_weights<T>), dim3(div_up(total, 256)), dim3(256), 0, s, w, K, kc,
-                               nc, n_chunk, NB, wl & 3, (frag *)ws);
+            hipLaunchKernelGGL((pack_weights<BF16>), grid, block, 0, s, w, c.K, c.kc, c.nc, r.geo.n_chunk, r.geo.NB, c.layout, (BF16::frag *)ws);
     }
-    if (ep.res_bcast && !fast) return DODA_ERR_UNSUPPORTED;   // (the broadcast residual lives in conv_fast's epilogue)
-    if (folded) {
-        // the folded BatchNorm: 16-byte pieces of rows in the output's dtype (bf16 >= 32 channels, fp32), at most PRE_MAX_C
-        // channels, every operand 16-byte aligned; split blocks — 16 rows x one channel block while the grid stays small,
-        // 32 rows x four channel blocks above (the shapes the unfolded call would take at the coarse levels)
-        const size_t va16 = 16 / sizeof(elem);
-        const int pk = pre->kind & 0xff;     // (the high bits carry the DODA_PRE_ABLATE mask of debug builds)
-        if (out32 || pair || (sizeof(elem) == 2 && !wide) || kc > PRE_MAX_C || kc % (int)va16 != 0 || x_ld % va16 != 0 ||
-            !pre->side || pre->side_ld % va16 != 0 || ((uintptr_t)pre->side % 16) != 0 || pre->rows != (int)n_in ||
-            (pk >= 2 && (!pre->aux || pre->aux_ld % va16 != 0 || ((uintptr_t)pre->aux % 16) != 0 || !pre->mean || !pre->invstd ||
-                                !pre->tot.ta || (size_t)n_in * pre->aux_ld * sizeof(elem) >= 0x7ffffff0ull)) ||
-            (pk >= 3 && (!pre->add || pre->add_ld % va16 != 0 || ((uintptr_t)pre->add % 16) != 0 ||
-                                (size_t)n_in * pre->add_ld * sizeof(elem) >= 0x7ffffff0ull)) ||
-            (pk == 1 && !pre->tot.ta && (!pre->tot.rm || !pre->tot.rv)) || !pre->gamma || !pre->beta)
-            return DODA_ERR_UNSUPPORTED;
-        typedef typename FastPolicy<T>::wide PWp;
-        typedef typename FastPolicy<T>::narrow PNp;
-        const long long wf = ((long long)n_out + 15) / 16;
-        static const long long small_max = [] { const char *e = getenv("DODA_PRE_SMALL_BLOCKS"); return e && *e ? atoll(e) : 2048ll; }();
-        if (wf * NB <= small_max) {
-            if (wide) return launch_fast<PWp, 1, 1, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s, pre);
-            return launch_fast<PNp, 1, 1, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s, pre);
-        }
-        if (wide) return launch_fast<PWp, 4, 2, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s, pre);
-        return launch_fast<PNp, 4, 2, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s, pre);
+    a.ep.f32_split = r.policy == GP_F32_SPLIT;
+    *n_part = r.n_part;
+    switch (r.family) {
+    case GF_GENERIC: case GF_FAST: return launch_dense(r, a, s);
+    case GF_WLDS48: return doda_wlds::launch(r, a, s);
+    default: return doda_tile::launch(r, a, s);
     }
-    // K <= 8, 32 input channels, fewer input rows than output rows (the k2 s2 rulebook read from the fine side: one source row
-    // per output row): conv_up32 (spconv_tile.hip).  DODA_CONV_UP=0 / doda_set_option(DODA_OPT_CONV_UP, 0): conv_fast as before.
-    {
-        if (doda_tile::up_enabled() && wide && sizeof(elem) == 2 && kc == 32 && K <= 8 && K > 1 && n_in < (long long)n_out && nc % 16 == 0 &&
-            !ep.res_bcast && x_dense && doda_tile::enabled()) {
-            const unsigned xb = (unsigned)((size_t)n_in * kc * sizeof(elem));
-            const unsigned yb = (unsigned)((((size_t)n_out - 1) * y_ld + nc) * (out32 ? 4 : sizeof(elem)));
-            return doda_tile::launch_conv_up32(out32, x_, xb, wp, (unsigned)need, nc, NB, K, tbl, ld, n_out, y_, yb, res, ep, n_part, s);
-        }
-    }
-    // A tilebook of this table and rows of 32 / 64 bytes: the LDS-staged tile kernel (spconv_tile.hip)
-    if (!ep.res_bcast && x_dense) {
-        // (fp32 rows: the tile kernel's fp32 mode is bound by the fp32 matrix rate like the dense-table kernel and measured
-        // within a few percent of it; DODA_F32_CONV_TILE=0 keeps fp32 forward / data-grad calls on conv_fast even when the
-        // table carries a tilebook — the fp32 weight gradient uses the tilebook either way)
-        static const bool f32_tile = !(getenv("DODA_F32_CONV_TILE") && getenv("DODA_F32_CONV_TILE")[0] == '0');
-        const int tmode = pair ? 0 : (wide && kc == 32) ? 1 : (fast && sizeof(elem) == 4 && kc == 16 && f32_tile) ? 2 : -1;
-        // (statistics: the tile kernels' per-lane accumulators hold up to two channel blocks, the dual-pass 64-byte-row kernel four)
-        const bool stats_fit = !ep.stats || NB <= 2 || (tmode == 1 && NB == 4 && doda_tile::dual_enabled());
-        if (tmode >= 0 && tilebook && K == TB_K && tilebook_rows == n_out && doda_tile::enabled() && stats_fit) {
-            const unsigned xb = (unsigned)((size_t)n_in * kc * sizeof(elem));
-            const unsigned yb = (unsigned)((((size_t)n_out - 1) * y_ld + nc) * (out32 ? 4 : sizeof(elem)));
-            return doda_tile::launch_conv_tile(tmode, out32 || sizeof(elem) == 4, x_, xb, wp, (unsigned)need, nc, NB, tbl, ld,
-                                               n_out, tilebook, y_, yb, res, ep, n_part, s);
-        }
-    }
-    // 48 -> 48 channels on a mid-size level: the layer's fragments in LDS, one workgroup per CU (spconv_wlds.hip)
-    if (!ep.res_bcast && x_dense && wide && kc == 48 && nc == 48 && K == 27 && !out32 && n_out >= 8192 && n_out <= 262144 && doda_wlds::enabled()) {
-        const unsigned xb = (unsigned)((size_t)n_in * kc * sizeof(elem));
-        const unsigned yb = (unsigned)((((size_t)n_out - 1) * y_ld + nc) * sizeof(elem));
-        return doda_wlds::launch_conv48(x_, xb, wp, tbl, (unsigned)((size_t)K * ld * 4), ld, n_out, y_, yb, res, ep, n_part, s);
-    }
-    // Tile choice: many rows -> more subtiles per wave and all channel blocks in one wave (x is
-    // gathered once); few rows -> one subtile, channel blocks spread over the grid so the chip
-    // still sees thousands of waves.
-    const long long waves_full = ((long long)n_out + 15) / 16;
-    typedef typename FastPolicy<T>::narrow PN;
-    typedef typename FastPolicy<T>::wide PW;
-    typedef typename FastPolicy<T>::pair PP;
-#define GO(NBW, S)                                                                                 \
-    do {                                                                                           \
-        if (wide) return launch_fast<PW, NBW, S>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-        if (pair) return launch_fast<PP, NBW, S>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-        if (fast) return launch_fast<PN, NBW, S>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-        return launch<T, NBW, S>(x, kc, (const frag *)wp, nc, NB, tbl, ld, K, n_out, y, vec_ok, (const elem *)res, s); \
-    } while (0)
-    {   // few rows, long unit chains: split the offsets of a 16-row tile over the block's waves
-        // measured (rocprofv3, per dispatch): 795 / 210 / 49 blocks 12.7 -> 9.5, 12.2 -> 6.1,
-        // 16.0 -> 6.3 us; 2808 blocks (level 4) 18.0 -> 24.7 us, so only below ~1k blocks
-#define GS(NBW, S)                                                                                 \
-    do {                                                                                           \
-        if (wide) return launch_fast<PW, NBW, S, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-        if (pair) return launch_fast<PP, NBW, S, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-        return launch_fast<PN, NBW, S, true>(x, kc, wp, need, nc, NB, tbl, ld, K, n_out, n_in, y_, out32, res, ep, n_part, s); \
-    } while (0)
-        // (two channel blocks / 32-row tiles per split block were tried at level 4: 14.2 us against
-        // 13.0 us for the unsplit <4,1> tile, so the split stays at one block, 16 rows)
-        if (fast && (long long)K * n_chunk >= 12 && waves_full * NB <= 1024) GS(1, 1);
-        // mid levels, 3-4 channel blocks: 32-row split blocks load each weight fragment once per 32
-        // rows instead of once per 16 (level 3, 46k rows x 48 ch: 22.0 -> 19.6 us; level 4, 11k x 64:
-        // 13.9 -> 11.9 us); 64-row split blocks and 2-block layers lose (23.2 / 36.3 us)
-        if (fast && (long long)K * n_chunk >= 12) {
-            if (NB == 3 && waves_full >= 512 && waves_full < 8192) GS(3, 2);
-            if (NB == 4 && waves_full >= 512 && waves_full < 2048) GS(4, 2);
-        }
-#undef GS
-    }
-    if (NB == 1) {  // measured at M = 600k, 16 ch: S=2 51 us, S=4 56 us, S=1 56 us
-        if (waves_full >= 4096) GO(1, 2);
-        GO(1, 1);
-    }
-    if (NB == 2) {
-        // level 2 (183k rows, 32 ch): bf16 <2,4> 27.7 us, <2,2> 30.2, <2,1> 35.0; fp32 98.8 / 93.6 / 92.8
-        if (waves_full >= 8192 && sizeof(elem) == 2) GO(2, 4);
-        if (waves_full >= 8192) GO(2, 2);
-        if (waves_full >= 2048) GO(2, 1);
-        GO(1, 1);
-    }
-    if (NB == 3) {   // 48 channels: three channel blocks exactly (a <4,*> tile would load and multiply a zero block)
-        if (waves_full >= 512) GO(3, 1);   // level 3 (46k rows): <3,1> 23.2 us, <4,1> 27.8, <3,2> 22.8 (fp32 74.6)
-        GO(1, 1);
-    }
-    if (NB <= 4) {
-        if (waves_full >= 8192) GO(4, 2);
-        if (waves_full >= 512) GO(4, 1);   // level 4 (11k rows, 64 ch): <4,1> 13.0 us, <2,1> 17.3, <2,2> 14.9
-        GO(1, 1);
-    }
-    if (waves_full >= 4096) GO(8, 1);
-    if (waves_full >= 1024) GO(4, 1);
-    if (waves_full >= 256) GO(2, 1);
-    GO(1, 1);
-#undef GO
 }
 
 bool bad_args(const void *x, int kc, const float *w, int nc, const int32_t *tbl, int ld, int K,
@@ -1227,9 +1073,8 @@ bool bad_args(const void *x, int kc, const float *w, int nc, const int32_t *tbl,
 extern "C" size_t doda_spconv_gather_workspace_bytes(int32_t K, int32_t kc, int32_t nc,
                                                      int32_t elem_bytes) {
     if (K <= 0 || kc <= 0 || nc <= 0) return 0;
-    if (elem_bytes == 2)  // covers both the 16-channel (8 B) and the 32-channel (16 B) fragment packing
-        return align_up((size_t)K * ((kc + 31) / 32) * ((nc + 15) / 16) * 64 * 16, 256);
-    return align_up((size_t)K * ((kc + 15) / 16) * ((nc + 15) / 16) * 64 * 4 * (size_t)elem_bytes, 256);
+    // bf16: the wide packing, which covers the narrow (8 B fragments of 16 channels) and the pair form
+    return align_up(pack_geometry(K, kc, nc, elem_bytes, elem_bytes == 2 ? 0x10 : 0).bytes, 256);
 }
 
 extern "C" size_t doda_spconv_pack_desc_bytes(void) { return sizeof(PackDesc); }
@@ -1245,11 +1090,11 @@ extern "C" int doda_spconv_pack_plan_h(void *descs_h, int32_t n_desc, int32_t *b
         if (d[k].K <= 0 || d[k].K > MAX_K || d[k].kc <= 0 || d[k].nc <= 0 || (d[k].layout & ~3) ||
             (d[k].layout & 3) > 2 || (d[k].elem_bytes != 2 && d[k].elem_bytes != 4))
             return DODA_ERR_INVALID;
-        d[k].layout |= pack_mode(d[k].K, d[k].kc, d[k].elem_bytes);   // the mode the gather will expect
-        d[k].n_chunk = (d[k].layout & 0x10) ? (d[k].kc + 31) / 32 : (d[k].kc + 15) / 16;
-        d[k].NB = (d[k].nc + 15) / 16;
-        acc += div_up((d[k].layout & 0x20) ? (long long)d[k].K * d[k].NB * 32
-                                           : (long long)d[k].K * d[k].n_chunk * d[k].NB * 64, 256);
+        const PackGeometry g = pack_geometry(d[k].K, d[k].kc, d[k].nc, d[k].elem_bytes);
+        d[k].layout |= g.mode;   // the mode the gather will expect
+        d[k].n_chunk = g.n_chunk;
+        d[k].NB = g.NB;
+        acc += div_up(g.frags, 256);
         if (acc > 0x7fffffff) return DODA_ERR_UNSUPPORTED;
         blk_end_h[k] = (int32_t)acc;
     }
@@ -1267,27 +1112,29 @@ extern "C" int doda_spconv_pack_multi(const void *descs_dev, const int32_t *blk_
 
 // ---- gather with epilogue options (residual add, BatchNorm statistics) ------------------------------
 // A/B switches of the kernel selection (measurements and parity tests; every option defaults to 1)
-extern "C" int doda_set_option(int32_t option, int32_t value) {
+static bool *gather_switch(int32_t option) {
     switch (option) {
-    case DODA_OPT_TILE_KERNEL: doda_tile::set_enabled(value != 0); return DODA_OK;
-    case DODA_OPT_WLDS_KERNEL: doda_wlds::set_enabled(value != 0); return DODA_OK;
+    case DODA_OPT_TILE_KERNEL: return &gather_switches().tile;
+    case DODA_OPT_WLDS_KERNEL: return &gather_switches().wlds;
+    case DODA_OPT_TILE_PIPELINE: return &gather_switches().tile_pipeline;
+    case DODA_OPT_TILE_DUAL: return &gather_switches().tile_dual;
+    case DODA_OPT_CONV_UP: return &gather_switches().conv_up;
+    default: return nullptr;
+    }
+}
+extern "C" int doda_set_option(int32_t option, int32_t value) {
+    if (bool *sw = gather_switch(option)) { *sw = value != 0; return DODA_OK; }
+    switch (option) {
     case DODA_OPT_WDMA_KERNEL: doda_wdma::set_enabled(value != 0); return DODA_OK;
-    case DODA_OPT_TILE_PIPELINE: doda_tile::set_pipeline(value != 0); return DODA_OK;
-    case DODA_OPT_TILE_DUAL: doda_tile::set_dual(value != 0); return DODA_OK;
-    case DODA_OPT_CONV_UP: doda_tile::set_up(value != 0); return DODA_OK;
     case DODA_OPT_PRE_FWD_ROWS: doda_layers::set_fwd_rows(value); return DODA_OK;
     case DODA_OPT_PRE_BWD_ROWS: doda_layers::set_bwd_rows(value); return DODA_OK;
     default: return DODA_ERR_INVALID;
     }
 }
 extern "C" int32_t doda_get_option(int32_t option) {
+    if (const bool *sw = gather_switch(option)) return *sw ? 1 : 0;
     switch (option) {
-    case DODA_OPT_TILE_KERNEL: return doda_tile::enabled() ? 1 : 0;
-    case DODA_OPT_WLDS_KERNEL: return doda_wlds::enabled() ? 1 : 0;
     case DODA_OPT_WDMA_KERNEL: return doda_wdma::enabled() ? 1 : 0;
-    case DODA_OPT_TILE_PIPELINE: return doda_tile::pipeline_enabled() ? 1 : 0;
-    case DODA_OPT_TILE_DUAL: return doda_tile::dual_enabled() ? 1 : 0;
-    case DODA_OPT_CONV_UP: return doda_tile::up_enabled() ? 1 : 0;
     case DODA_OPT_PRE_FWD_ROWS: return (int32_t)doda_layers::fwd_rows();
     case DODA_OPT_PRE_BWD_ROWS: return (int32_t)doda_layers::bwd_rows();
     default: return -1;
@@ -1306,9 +1153,11 @@ extern "C" int doda_spconv_gather_ex(const void *x, int32_t n_in, int32_t kc, in
         if (st == DODA_OK && epi && epi->stats_rows_h) *epi->stats_rows_h = 0;
         return st;
     }
-    EpiArgs ep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
+    GatherOperands a{};
+    EpiArgs &ep = a.ep;
     const void *res = nullptr;
     int n_part = 0;
+    GatherCall c{};
     if (epi) {
         res = epi->residual;
         ep.res_bcast = (res && epi->residual_bcast) ? 1 : 0;
@@ -1326,7 +1175,6 @@ extern "C" int doda_spconv_gather_ex(const void *x, int32_t n_in, int32_t kc, in
         }
     }
     PreArgs pre{};
-    const PreArgs *prep = nullptr;
     if (epi) {
         if (epi->x_ld < 0 || epi->y_ld < 0 || epi->residual_ld < 0 || epi->bn_x_ld < 0) return DODA_ERR_INVALID;
         ep.x_ld = (unsigned)epi->x_ld; ep.y_ld = (unsigned)epi->y_ld;
@@ -1358,16 +1206,25 @@ extern "C" int doda_spconv_gather_ex(const void *x, int32_t n_in, int32_t kc, in
             pre.gamma = q->gamma; pre.beta = q->beta; pre.mean = q->mean; pre.invstd = q->invstd;
             pre.side = q->side; pre.side_ld = (unsigned)q->side_ld;
             pre.aux = q->aux; pre.add = q->add; pre.aux_ld = (unsigned)q->aux_ld; pre.add_ld = (unsigned)q->add_ld;
-            prep = &pre;
+            a.pre = &pre;
+            c.pre_kind = q->kind; c.pre_rows = q->rows;
+            c.side_ld = pre.side_ld; c.aux_ld = pre.aux_ld; c.add_ld = pre.add_ld;
+            c.side = pre.side && al16(pre.side); c.aux = pre.aux && al16(pre.aux); c.add = pre.add && al16(pre.add);
+            c.saved = pre.mean && pre.invstd; c.totals = pre.tot.ta != nullptr; c.running = pre.tot.rm && pre.tot.rv;
+            c.affine = pre.gamma && pre.beta;
         }
+        c.tilebook = epi->tilebook != nullptr; c.tilebook_rows = epi->tilebook_rows;
+        a.tilebook = epi->tilebook;
     }
-    if (elem_bytes == 4)
-        st = run_gather<F32>(x, kc, w, nc, tbl, ld, K, n_out, y, w_layout, ws, ws_bytes, n_in, false, res,
-                             as_stream(stream), ep, &n_part, epi ? epi->tilebook : nullptr, epi ? epi->tilebook_rows : 0, prep);
-    else
-        st = run_gather<BF16>(x, kc, w, nc, tbl, ld, K, n_out, y, w_layout, ws, ws_bytes, n_in, y_is_f32 != 0, res,
-                              as_stream(stream), ep, &n_part, epi ? epi->tilebook : nullptr,
-                              epi ? epi->tilebook_rows : 0, prep);
+    c.K = K; c.kc = kc; c.nc = nc; c.n_out = n_out; c.ld = ld; c.esz = elem_bytes; c.n_in = n_in;
+    c.out32 = elem_bytes == 2 && y_is_f32 != 0;
+    c.layout = w_layout & 3; c.packed = (w_layout & 0x100) != 0; c.ws_bytes = ws ? ws_bytes : 0;
+    c.x_al = (int)((uintptr_t)x & 15); c.y_al = (int)((uintptr_t)y & 15);
+    c.x_ld = ep.x_ld; c.y_ld = ep.y_ld; c.res_ld = ep.res_ld; c.bnx_ld = ep.bnx_ld;
+    c.res_bcast = ep.res_bcast != 0; c.stats = ep.stats != nullptr;
+    a.x = x; a.tbl = tbl; a.y = y; a.res = res;
+    a.kc = kc; a.nc = nc; a.K = K; a.ld = ld; a.n_out = n_out;
+    st = run_gather(c, a, w, ws, &n_part, as_stream(stream));
     if (st == DODA_OK && epi && epi->stats_rows_h) *epi->stats_rows_h = n_part;
     return st;
 }

@@ -1,6 +1,6 @@
 // LDS-staged sparse-convolution kernel over a tilebook (tilebook.hpp / tilebook.hip): conv_tile (forward and data
 // gradient of the bf16 16- / 32-channel and fp32 16-channel SubM layers).  Dispatched from spconv_gather.hip
-// (run_gather) through doda_tile::launch_conv_tile;
+// (run_gather) through doda_tile::launch, on the route gather_plan.hpp chose;
 // replaces spconv v1.2's indice_conv / indice_conv_backward data path (reference call sites
 // model/unet_block.py:26,29,48) for the layers whose rulebook carries a tilebook.
 #include "common.hpp"
@@ -804,106 +804,39 @@ __global__ __launch_bounds__(256) void conv_up32(const void *__restrict__ x, uns
     }
 }
 
-constexpr int BT_MAX_GROUPS = 768;   // 3 workgroups per CU x 256 CUs
-// (A/B switches: DODA_TILE_DUAL=0 / doda_set_option(DODA_OPT_TILE_DUAL, 0) keeps the 32-output-channel layers on one channel block
-// per pass; doda_set_option(DODA_OPT_TILE_PIPELINE, 0) keeps the 16 -> 16 layers on conv_tile)
-bool g_dual = !(getenv("DODA_TILE_DUAL") && getenv("DODA_TILE_DUAL")[0] == '0');
-bool g_pipeline = true;
-bool g_up = !(getenv("DODA_CONV_UP") && getenv("DODA_CONV_UP")[0] == '0');
-bool dual_blocks() { return g_dual; }
-constexpr int T16_MAX_GROUPS = 512;  // conv_tile16: 2 workgroups per CU
-// conv_tile16 pays off from the point where conv_tile's workgroups run more than one tile each (a single tile per
-// workgroup has nothing to prefetch, and three shallow workgroups per CU then beat two)
-int tile16_min_tiles() {
-    static const int v = [] {
-        const char *e = getenv("DODA_TILE16_MIN_TILES");
-        const int m = e && *e ? atoi(e) : BT_MAX_GROUPS + 1;
-        return m < T16_MAX_GROUPS ? T16_MAX_GROUPS : m;   // (every one of its 512 workgroups must own a tile)
-    }();
-    return v;
-}
-
-bool g_use_tile = true;   // doda_set_option(DODA_OPT_TILE_KERNEL) (A/B measurements)
-
 }  // namespace
 
-bool doda_tile::enabled() { return g_use_tile; }
-void doda_tile::set_enabled(bool on) { g_use_tile = on; }
-bool doda_tile::pipeline_enabled() { return g_pipeline; }
-void doda_tile::set_pipeline(bool on) { g_pipeline = on; }
-bool doda_tile::dual_enabled() { return g_dual; }
-void doda_tile::set_dual(bool on) { g_dual = on; }
-bool doda_tile::up_enabled() { return g_up; }
-void doda_tile::set_up(bool on) { g_up = on; }
-
-int doda_tile::launch_conv_up32(bool out32, const void *x, unsigned xb, const void *wp, unsigned wpb, int nc, int NB, int K,
-                                const int32_t *tbl, int ld, int n_out, void *y, unsigned yb, const void *res, const EpiArgs &ep,
-                                int *n_part, hipStream_t s) {
-    const int groups = (n_out + TB_T - 1) / TB_T;
-    if (n_part) *n_part = groups;
-    const dim3 grid(groups), block(256);
-#define GU(O32, ST) hipLaunchKernelGGL((conv_up32<O32, ST>), grid, block, 0, s, x, xb, wp, wpb, nc, NB, K, tbl, ld, n_out, y, yb, res, ep)
-    if (out32) { if (ep.stats) GU(true, true); else GU(true, false); }
-    else { if (ep.stats) GU(false, true); else GU(false, false); }
-#undef GU
+int doda_tile::launch(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
+    const dim3 grid(r.grid), block(r.block);
+    const EpiArgs &ep = a.ep;
+    const int NB = r.geo.NB;
+    const TileBookView tb = r.family == GF_UP32 ? TileBookView{} : tilebook_view(const_cast<void *>(a.tilebook), a.n_out);
+    with_bool(r.out32, [&](auto o32) { with_bool(r.stats, [&](auto st) {
+        constexpr bool O32 = decltype(o32)::value, ST = decltype(st)::value;
+        // conv_tile<MODE, OUT32, STATS, MAXNB, DUAL>: MODE 2 (fp32 rows) is always OUT32; the dual kernel serves 32 and 64 output
+        // channels with MAXNB 2, and 64 with their statistics with MAXNB 4
+        const auto tile = [&](auto mode, auto maxnb, auto dual) {
+            hipLaunchKernelGGL((conv_tile<decltype(mode)::value, O32, ST, decltype(maxnb)::value, decltype(dual)::value>), grid, block, 0, s,
+                               a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, NB, a.tbl, a.ld, a.n_out, tb, a.y, r.y_bytes, a.res, ep);
+        };
+        const auto plain = [&](auto mode) {
+            if (r.maxnb == 2) tile(mode, Int<2>{}, std::false_type{});
+            else tile(mode, Int<1>{}, std::false_type{});
+        };
+        if (r.family == GF_UP32)
+            hipLaunchKernelGGL((conv_up32<O32, ST>), grid, block, 0, s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, NB, a.K, a.tbl, a.ld, a.n_out,
+                               a.y, r.y_bytes, a.res, ep);
+        else if (r.family == GF_TILE16)
+            hipLaunchKernelGGL((conv_tile16<O32, ST>), grid, block, 0, s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, a.tbl, a.ld, a.n_out, tb,
+                               a.y, r.y_bytes, a.res, ep);
+        else if (r.dual) {
+            if constexpr (ST) { if (r.maxnb == 4) return tile(Int<1>{}, Int<4>{}, std::true_type{}); }
+            tile(Int<1>{}, Int<2>{}, std::true_type{});
+        } else {
+            if constexpr (O32) { if (r.mode == 2) return plain(Int<2>{}); }
+            if (r.mode == 1) plain(Int<1>{});
+            else plain(Int<0>{});
+        }
+    }); });
     return doda_check_launch();
 }
-
-int doda_tile::launch_conv_tile(int mode, bool out32, const void *x, unsigned xb, const void *wp, unsigned wpb, int nc, int NB,
-                                const int32_t *tbl, int ld, int n_out, const void *tilebook, void *y, unsigned yb,
-                                const void *res, const EpiArgs &ep_in, int *n_part, hipStream_t s) {
-    const TileBookView tb = tilebook_view(const_cast<void *>(tilebook), n_out);
-    if (mode == 0 && NB == 1 && g_pipeline && tb.nt >= tile16_min_tiles()) {
-        const int groups16 = T16_MAX_GROUPS;
-        if (n_part) *n_part = groups16;
-        const dim3 grid(groups16), block(256);
-        const EpiArgs &ep = ep_in;
-#define G16(O32, ST)                                                                               \
-    hipLaunchKernelGGL((conv_tile16<O32, ST>), grid, block, 0, s, x, xb, wp, wpb, nc, tbl, ld, n_out, tb, y, yb, res, ep)
-        if (out32) { if (ep.stats) G16(true, true); else G16(true, false); }
-        else { if (ep.stats) G16(false, true); else G16(false, false); }
-#undef G16
-        return doda_check_launch();
-    }
-    int groups = (tb.nt + 7) / 8 * 8;   // persistent: 3 (64-byte rows: 2) workgroups per CU, a multiple of the 8 XCDs
-    const int max_groups = mode == 0 ? BT_MAX_GROUPS : BT_MAX_GROUPS * 2 / 3;
-    if (groups > max_groups) groups = max_groups;
-    const dim3 grid(groups), block(256);
-    if (ep_in.stats && NB > 2 && !(mode == 1 && NB == 4 && dual_blocks())) return DODA_ERR_UNSUPPORTED;   // (run_gather does not send such calls here)
-    const bool two = NB > 1 && ep_in.stats;                   // statistics of a second channel block
-    if (n_part) *n_part = groups;      // one statistics row per persistent workgroup
-    const EpiArgs &ep = ep_in;
-#define GT1(M, O32, ST, NBS)                                                                       \
-    hipLaunchKernelGGL((conv_tile<M, O32, ST, NBS>), grid, block, 0, s, x, xb, wp, wpb, nc, NB, tbl, ld, n_out, tb, y, yb, res, ep)
-#define GTD(O32, ST)                                                                               \
-    hipLaunchKernelGGL((conv_tile<1, O32, ST, 2, true>), grid, block, 0, s, x, xb, wp, wpb, nc, NB, tbl, ld, n_out, tb, y, yb, res, ep)
-#define GT(M, O32, ST)                                                                             \
-    do {                                                                                           \
-        if (ST && two) GT1(M, O32, ST, 2); else GT1(M, O32, ST, 1);                                \
-    } while (0)
-#define GM(M)                                                                                      \
-    do {                                                                                           \
-        if (out32) { if (ep.stats) GT(M, true, true); else GT(M, true, false); }                   \
-        else { if (ep.stats) GT(M, false, true); else GT(M, false, false); }                       \
-    } while (0)
-    if (mode == 2) { if (ep.stats) GT(2, true, true); else GT(2, true, false); }
-    else if (mode == 1 && NB == 2 && dual_blocks()) {   // 32 output channels: both channel blocks in one pass
-        if (out32) { if (ep.stats) GTD(true, true); else GTD(true, false); }
-        else { if (ep.stats) GTD(false, true); else GTD(false, false); }
-    }
-    else if (mode == 1 && NB == 4 && dual_blocks()) {   // 64 output channels: two dual passes (the 32 -> 64 data gradient of level 2)
-#define GTQ(O32, ST) hipLaunchKernelGGL((conv_tile<1, O32, ST, 4, true>), grid, block, 0, s, x, xb, wp, wpb, nc, NB, tbl, ld, n_out, tb, y, yb, res, ep)
-        if (out32) { if (ep.stats) GTQ(true, true); else GTD(true, false); }
-        else { if (ep.stats) GTQ(false, true); else GTD(false, false); }
-#undef GTQ
-    }
-    else if (mode == 1) GM(1);
-    else GM(0);
-#undef GM
-#undef GT
-#undef GT1
-#undef GTD
-    return doda_check_launch();
-}
-
-

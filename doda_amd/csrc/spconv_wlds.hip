@@ -16,8 +16,6 @@ constexpr int WK = 27, WCH = 48, WNB = 3;
 constexpr int W_SLOTS = 96;                         // 16-byte fragments per (offset, channel block): 64 + 32
 constexpr int W_LDS_BYTES = WK * WNB * W_SLOTS * 16;   // 124 416
 
-bool g_use_wlds = true;
-
 // statistics / residual / store of one 16-column block held by 8 waves x S subtiles (cf. tile_epilogue)
 // Round 4: the residual / BatchNorm-input rows arrive as arguments — requested at the top of the tile, before the table and the
 // gathers (three channel blocks used to wait one after the other for their own loads at the END of the tile's chain) — and the
@@ -222,16 +220,7 @@ __global__ __launch_bounds__(512) void conv_wlds48(const unsigned short *__restr
 
 }  // namespace
 
-bool doda_wlds::enabled() { return g_use_wlds; }
-void doda_wlds::set_enabled(bool on) { g_use_wlds = on; }
-
-int doda_wlds::launch_conv48(const void *x, unsigned x_bytes, const void *wp, const int32_t *tbl, unsigned tbl_bytes, int ld,
-                             int n_out, void *y, unsigned y_bytes, const void *res, const EpiArgs &ep_in, int *n_part,
-                             hipStream_t s) {
-    const int n_tiles = (n_out + 255) / 256;
-    const int grid = n_tiles < 256 ? n_tiles : 256;
-    if (n_part) *n_part = n_tiles;
-    const EpiArgs &ep = ep_in;
+int doda_wlds::launch(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
     static bool attr_done = false;
     if (!attr_done) {   // more than 64 KB of dynamic LDS needs the opt-in
         if (hipFuncSetAttribute((const void *)conv_wlds48<true>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES) != hipSuccess ||
@@ -239,11 +228,9 @@ int doda_wlds::launch_conv48(const void *x, unsigned x_bytes, const void *wp, co
             return DODA_ERR_LAUNCH;
         attr_done = true;
     }
-    if (ep.stats)
-        hipLaunchKernelGGL((conv_wlds48<true>), dim3(grid), dim3(512), W_LDS_BYTES, s, (const unsigned short *)x, x_bytes,
-                           (const u32x4 *)wp, tbl, tbl_bytes, ld, n_out, y, y_bytes, res, ep);
-    else
-        hipLaunchKernelGGL((conv_wlds48<false>), dim3(grid), dim3(512), W_LDS_BYTES, s, (const unsigned short *)x, x_bytes,
-                           (const u32x4 *)wp, tbl, tbl_bytes, ld, n_out, y, y_bytes, res, ep);
+    with_bool(r.stats, [&](auto ST) {
+        hipLaunchKernelGGL((conv_wlds48<decltype(ST)::value>), dim3(r.grid), dim3(r.block), W_LDS_BYTES, s, (const unsigned short *)a.x, r.x_bytes,
+                           (const u32x4 *)a.wp, a.tbl, r.tbl_bytes, a.ld, a.n_out, a.y, r.y_bytes, a.res, a.ep);
+    });
     return doda_check_launch();
 }

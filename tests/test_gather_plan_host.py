@@ -1,0 +1,125 @@
+"""doda_amd/csrc/gather_plan.hpp on the CPU: the route plan of doda_spconv_gather_ex is one pure host function, so which kernel
+instantiation a call reaches, with which grid and how many statistics rows, is checked without a GPU.  A stand-alone program
+(tests/host/gather_plan_main.cpp, g++, once more with -fsanitize=address,undefined) answers for the probe list of
+tools/gatherroutes.py — asserted against tests/data/gather_routes.json, the routes recorded on an MI355X (kernel trace) from the
+ladders the plan replaced — and for a dense sweep over row counts, whose routes must be compiled instantiations
+(tests/data/gather_instantiations.json, the kernel symbols of the three code objects) with grids that cover the rows."""
+import importlib.util
+import json
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "gather_plan_main.cpp")
+
+
+def _probes():
+    spec = importlib.util.spec_from_file_location("gatherroutes", os.path.join(ROOT, "tools", "gatherroutes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def planner(request, tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("gather_plan") / ("plan_" + request.param))
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if request.param == "sanitized" else ["-O2"]
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", *flags, SRC, "-o", exe], check=True)
+
+    def ask(lines):
+        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [re.match(r"status=(-?\d+) route=(.*) grid=(\d+) block=(\d+) parts=(\d+) frags=(\d+) wbytes=(\d+)$", l)
+               for l in r.stdout.splitlines()]
+        assert len(out) == len(lines) and all(out)
+        return [dict(status=int(m[1]), route=m[2], grid=int(m[3]), block=int(m[4]), parts=int(m[5]), frags=int(m[6]))
+                for m in out]
+    return ask
+
+
+def test_probe_list_reaches_the_recorded_routes(planner):
+    gr = _probes()
+    table = json.load(open(os.path.join(ROOT, "tests", "data", "gather_routes.json")))
+    for group in ("main", "f32split"):
+        ps = gr.probes(group)
+        rec = table[group]
+        assert [p["name"] for p in ps] == [r["name"] for r in rec]
+        for p, r, got in zip(ps, rec, planner([gr.plan_line(p, group) for p in ps])):
+            assert got["status"] == r["status"] == p["err"], (p["name"], got)
+            if r["status"] != 0:
+                assert got["route"] == "none" and got["grid"] == 0
+                continue
+            assert (got["route"], got["grid"], got["block"]) == (r["kernel"], r["grid"], r["block"]), (p["name"], got, r)
+            if r["parts"] >= 0:     # (recorded where the call asked for statistics)
+                assert got["parts"] == r["parts"], (p["name"], got, r)
+            if r["pack"]:           # the pack kernel the call enqueues first: one thread per fragment
+                wide = p["esz"] == 2 and not got["route"].startswith("conv_gather") and (
+                    (p["kc"] >= 32 and p["kc"] % 8 == 0) or (p["kc"] == 16 and p["K"] >= 2))
+                name = "pack_weights_wide" if wide else "pack_weights<%s>" % ("F32" if p["esz"] == 4 else "BF16")
+                assert r["pack"] == [name, (got["frags"] + 255) // 256, 256], (p["name"], got, r)
+
+
+def test_conv_tile16_starts_at_769_tiles(planner):
+    """196 608 rows are 768 tiles, 196 609 are 769: DODA_TILE16_MIN_TILES' default, and the switch that moves it."""
+    got = planner(["kc=16 nc=16 tilebook=1 n_out=196608", "kc=16 nc=16 tilebook=1 n_out=196609",
+                   "kc=16 nc=16 tilebook=1 n_out=196609 sw.tile16_min_tiles=770", "kc=16 nc=16 tilebook=1 n_out=196609 sw.tile_pipeline=0"])
+    assert [g["route"] for g in got] == ["conv_tile<0, false, false, 1, false>", "conv_tile16<false, false>",
+                                         "conv_tile<0, false, false, 1, false>", "conv_tile<0, false, false, 1, false>"]
+    assert [g["grid"] for g in got] == [768, 512, 768, 768]
+
+
+def _sweep_rows():
+    rows = set(range(1, 80)) | set(range(4099, 300001, 4099)) | {300000}
+    for wf in (170, 171, 256, 341, 342, 512, 682, 683, 1024, 2048, 4096, 8192, 12288, 16384):   # thresholds, in 16-row tiles (/ NB)
+        rows |= set(range(16 * (wf - 3), 16 * (wf + 3) + 2))
+    return sorted(r for r in rows if 1 <= r <= 300000)
+
+
+def test_every_route_of_a_dense_sweep_is_compiled_and_covers_its_rows(planner):
+    compiled = set(json.load(open(os.path.join(ROOT, "tests", "data", "gather_instantiations.json"))))
+    calls = []
+    for n in _sweep_rows():
+        for nc in (16, 32, 48, 64, 96):
+            for esz in (2, 4):
+                for stats in (0, 1):
+                    for kc, K, n_in, tb, pre in ((16, 27, n, 0, 0), (16, 27, n, 1, 0), (32, 27, n, 0, 0), (32, 27, n, 1, 0), (48, 27, n, 0, 0),
+                                                 (32, 8, n // 4 + 1, 0, 0), (32, 27, n, 0, 1), (16, 1, n, 0, 0), (3, 27, n, 0, 0)):
+                        calls.append(dict(n_out=n, nc=nc, esz=esz, stats=stats, kc=kc, K=K, n_in=n_in, tilebook=tb, pre_kind=pre))
+    got = planner([" ".join("%s=%d" % it for it in c.items()) for c in calls])
+    cdiv = lambda a, b: (a + b - 1) // b
+    seen = set()
+    for c, g in zip(calls, got):
+        n, NB = c["n_out"], cdiv(c["nc"], 16)
+        if g["status"] != 0:      # the only rejections of this sweep: statistics on the generic kernel, a prologue on 16-byte-less rows
+            assert g["status"] == -4 and g["route"] == "none", (c, g)
+            continue
+        assert g["route"] in compiled, (c, g)
+        seen.add(g["route"])
+        fam, args = re.match(r"(\w+)<(.*)>$", g["route"]).groups()
+        a = [s.strip() for s in args.split(",")]
+        nt = cdiv(n, 256)
+        if c["tilebook"] and c["esz"] == 2 and c["kc"] == 16 and c["K"] == 27 and c["nc"] == 16:   # 16 -> 16 over a tilebook: the tile count decides
+            assert fam == ("conv_tile16" if nt >= 769 else "conv_tile"), (c, g)
+        if fam in ("conv_fast", "conv_gather"):
+            nbw, s = int(a[1]), int(a[2])
+            split = fam == "conv_fast" and a[5] == "true"
+            rpb = (1 if split else 4) * 16 * s
+            assert g["block"] == 256 and g["grid"] == cdiv(n, rpb) * cdiv(NB, nbw), (c, g)
+            assert (g["grid"] // cdiv(NB, nbw)) * rpb >= n
+            assert g["parts"] == (cdiv(n, rpb) if fam == "conv_fast" else 0), (c, g)
+            if fam == "conv_fast":
+                assert (a[6] == "true") == bool(c["stats"]) and int(a[7]) == c["pre_kind"], (c, g)
+        elif fam == "conv_up32":
+            assert g["grid"] == g["parts"] == nt and g["block"] == 256 and g["grid"] * 256 >= n, (c, g)
+        elif fam == "conv_tile16":
+            assert g["grid"] == g["parts"] == 512 and nt >= 769 and NB == 1 and g["block"] == 256, (c, g)
+        elif fam == "conv_tile":
+            cap = 768 if a[0] == "0" else 512
+            assert g["grid"] == g["parts"] == min(cdiv(nt, 8) * 8, cap) and g["block"] == 256, (c, g)
+            assert not c["stats"] or NB <= int(a[3]), (c, g)      # the statistics of every channel block fit the instantiation
+        else:
+            assert fam == "conv_wlds48" and g["block"] == 512 and g["parts"] == nt and g["grid"] == min(nt, 256), (c, g)
+    assert {re.match(r"\w+", r).group(0) for r in seen} == {"conv_fast", "conv_gather", "conv_up32", "conv_tile", "conv_tile16", "conv_wlds48"}

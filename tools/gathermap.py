@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Which layer shapes of one bench step go through doda_spconv_gather_ex, and how often (DODA_TRACE_GATHER=1 lines of the library,
-counted per step).  Read next to the conv_* rows of a kernel-statistics summary to see which instantiation serves which layer."""
+counted per step).  Every line ends with the route the call took (gather_plan.hpp): route=<kernel instantiation> grid= block= parts= —
+the kernel next to the shape, without a profiler."""
 import collections, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, DODA_TRACE_GATHER="1")

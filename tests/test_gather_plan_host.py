@@ -3,7 +3,10 @@ instantiation a call reaches, with which grid and how many statistics rows, is c
 (tests/host/gather_plan_main.cpp, g++, once more with -fsanitize=address,undefined) answers for the probe list of
 tools/gatherroutes.py — asserted against tests/data/gather_routes.json, the routes recorded on an MI355X (kernel trace) from the
 ladders the plan replaced — and for a dense sweep over row counts, whose routes must be compiled instantiations
-(tests/data/gather_instantiations.json, the kernel symbols of the three code objects) with grids that cover the rows."""
+(tests/data/gather_instantiations.json, the kernel symbols of the three code objects) with grids that cover the rows.  An extended sweep (tools/gathernumerics.py: out32, the prologue kinds, K, kc,
+the broadcast residual, every switch off, f32_split_rows = 0) settles every compiled name: the numerics probes of
+tests/test_gpu_gather_numerics.py (tests/data/gather_numerics.json, regenerated here from the plan) reach it, or
+tests/data/gather_unreached.json states the condition of the plan that excludes it."""
 import importlib.util
 import json
 import os
@@ -18,6 +21,13 @@ SRC = os.path.join(ROOT, "tests", "host", "gather_plan_main.cpp")
 
 def _probes():
     spec = importlib.util.spec_from_file_location("gatherroutes", os.path.join(ROOT, "tools", "gatherroutes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _numerics():
+    spec = importlib.util.spec_from_file_location("gathernumerics", os.path.join(ROOT, "tools", "gathernumerics.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -123,3 +133,27 @@ def test_every_route_of_a_dense_sweep_is_compiled_and_covers_its_rows(planner):
         else:
             assert fam == "conv_wlds48" and g["block"] == 512 and g["parts"] == nt and g["grid"] == min(nt, 256), (c, g)
     assert {re.match(r"\w+", r).group(0) for r in seen} == {"conv_fast", "conv_gather", "conv_up32", "conv_tile", "conv_tile16", "conv_wlds48"}
+
+
+def test_extended_sweep_settles_every_instantiation(planner):
+    """Every one of the 318 compiled names is reached by a numerics probe or listed as unreachable, never both, never neither; the
+    recorded probe list is the one the plan generates, and every probe is the smallest shape with a ragged last wave tile."""
+    gn = _numerics()
+    compiled = set(json.load(open(os.path.join(ROOT, "tests", "data", "gather_instantiations.json"))))
+    listed = json.load(open(os.path.join(ROOT, "tests", "data", "gather_unreached.json")))
+    unreached = {u["route"] for u in listed}
+    assert len(unreached) == len(listed) and all(u["condition"].strip() for u in listed)
+    produced = set()
+    probes = gn.generate(planner, produced)
+    assert not produced & unreached, sorted(produced & unreached)
+    recorded = gn.load_probes()
+    probed = {p["route"] for p in recorded}
+    assert produced <= probed, sorted(produced - probed)
+    assert len(compiled) == 318 and produced | unreached == compiled and len(produced) + len(unreached) == 318
+    assert probes == recorded        # regenerate: see tools/gathernumerics.py generate()
+    assert {p["group"] for p in recorded} == set(gn.GROUPS)
+    # the planner names the recorded route for the recorded shape, and no probe has only full wave tiles
+    for p, g in zip(recorded, planner([gn.plan_line(p) for p in recorded])):
+        assert (g["status"], g["route"], g["grid"], g["parts"]) == (0, p["route"], p["grid"], p["parts"]), (p, g)
+        assert p["n_out"] % 16 != 0 and p["n_out"] >= 37 and p["ld"] == p["n_out"] + 3 and p["n_in"] != p["n_out"], p
+        assert not p["res_bcast"] or p["group"].startswith("fast")

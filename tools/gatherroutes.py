@@ -6,6 +6,11 @@
       the statistics rows; for the error probes whether y and the workspace kept their sentinel.  With DODA_TRACE_GATHER=1 the
       library's trace lines (route= grid= block= parts=) appear on stderr in the same order.  The group f32split expects
       DODA_F32_SPLIT_ROWS=0 in the environment.
+  python tools/gatherroutes.py --numerics GROUP
+      one call per reachable kernel instantiation of the group (tools/gathernumerics.py: the list is generated from the plan,
+      tests/data/gather_numerics.json) against the fp64 reference: per call one JSON line with the traced route, the shape, the
+      errors of y, of each statistics sum and of the prologue's side output, and whether every guard kept its sentinel.  Meant
+      for a fresh process; sets DODA_TRACE_GATHER=1 (and DODA_F32_SPLIT_ROWS=0 for the group f32split) itself.
   python tools/gatherroutes.py --families
       one call per kernel family at a small shape: the largest error against the fp64 reference, one JSON line per call.
   python tools/gatherroutes.py --instantiations doda_amd/csrc/_obj/spconv_gather.o .../spconv_tile.o .../spconv_wlds.o
@@ -317,6 +322,13 @@ def fold(trace_csv, results):
 if __name__ == "__main__":
     if sys.argv[1] == "--run":
         run(sys.argv[2], int(sys.argv[sys.argv.index("--max-rows") + 1]) if "--max-rows" in sys.argv else 1 << 30)
+    elif sys.argv[1] == "--numerics":
+        os.environ["DODA_TRACE_GATHER"] = "1"       # (read by the library at its first gather call)
+        os.environ.pop("DODA_F32_SPLIT_ROWS", None)
+        if sys.argv[2] == "f32split":
+            os.environ["DODA_F32_SPLIT_ROWS"] = "0"
+        import gathernumerics
+        gathernumerics.run_group(sys.argv[2])
     elif sys.argv[1] == "--families":
         families()
     elif sys.argv[1] == "--instantiations":

@@ -230,6 +230,38 @@ inline GatherRoute plan_gather(const GatherCall &c, const GatherSwitches &sw) {
     return dense(wf >= 4096 ? 8 : wf >= 1024 ? 4 : wf >= 256 ? 2 : 1, 1, false);
 }
 
+// ---- The compiled set.  The launchers instantiate a kernel under `if constexpr` of these predicates and nothing else; each admits
+// exactly the names plan_gather returns for its family (tests/test_gather_plan_host.py: admitted = built = swept = probed).
+// conv_tile16 and conv_up32 exist for every (OUT32, STATS), conv_wlds48 for both STATS.
+// The legal (NBW, S, SPLIT) triples of conv_fast; conv_gather takes the unsplit ones.  The set of triples defines what is compiled;
+// their order only the order in which the compiler emits the kernels (the last entry first).  With this order every kernel's
+// instruction stream equalled the one under the ladders this table replaced; another order may schedule a kernel differently.
+template <int NBW_, int S_, bool SPLIT_> struct Shape { static constexpr int NBW = NBW_, S = S_; static constexpr bool SPLIT = SPLIT_; };
+template <class... Sh> struct Shapes {};
+typedef Shapes<Shape<8, 1, false>, Shape<4, 1, false>, Shape<4, 2, false>, Shape<3, 1, false>, Shape<2, 1, false>, Shape<2, 2, false>,
+               Shape<2, 4, false>, Shape<1, 1, false>, Shape<1, 2, false>, Shape<3, 2, true>, Shape<4, 2, true>, Shape<1, 1, true>> FastShapes;
+template <class... Sh>
+constexpr bool listed(Shapes<Sh...>, int nbw, int s, bool split) { return ((Sh::NBW == nbw && Sh::S == s && Sh::SPLIT == split) || ...); }
+// the triples dense() names for rows of `esz` bytes: two channel blocks from 8192 wave tiles on take <2, 2> in fp32 and <2, 4> in bf16
+constexpr bool dense_shape(int esz, int nbw, int s, bool split) { return listed(FastShapes{}, nbw, s, split) && !(nbw == 2 && s == (esz == 2 ? 2 : 4)); }
+constexpr bool generic_compiled(int esz, int nbw, int s, bool split) { return !split && dense_shape(esz, nbw, s, split); }
+// conv_fast<policy, NBW, S, D, OUT32, SPLIT, STATS, PRE>, for both STATS.  OUT32 is fp32 output rows of a bf16 call.  The folded
+// BatchNorm (PRE, PreArgs): 16-byte pieces of same-dtype rows (bf16 >= 32 channels, fp32), split blocks of 16 rows x one or 32
+// rows x four channel blocks — the shapes of the coarse U-Net levels, where a BatchNorm sweep of its own is a launch-floor kernel
+constexpr bool fast_compiled(int esz, GatherPolicy p, int nbw, int s, bool split, bool out32, int pre) {
+    const bool policy = esz == 2 ? p != GP_F32_SPLIT : (p == GP_NARROW || p == GP_F32_SPLIT);
+    const bool folded = pre >= 1 && pre <= 3 && split && ((nbw == 1 && s == 1) || (nbw == 4 && s == 2)) && !out32 &&
+                        p == (esz == 2 ? GP_WIDE : GP_NARROW);
+    return policy && dense_shape(esz, nbw, s, split) && !(out32 && esz == 4) && (pre == 0 || folded);
+}
+// conv_tile<MODE, OUT32, STATS, MAXNB, DUAL>: MODE 2 (fp32 rows) is always OUT32; the dual kernel (64-byte rows) serves 32 and 64
+// output channels with MAXNB 2, and 64 with their statistics with MAXNB 4; without it a second channel block per pass exists only
+// for the statistics
+constexpr bool tile_compiled(int mode, bool out32, bool stats, int maxnb, bool dual) {
+    return mode >= 0 && mode <= 2 && (mode != 2 || out32) &&
+           (dual ? mode == 1 && (maxnb == 2 || (maxnb == 4 && stats)) : maxnb == 1 || (maxnb == 2 && stats));
+}
+
 // The instantiation as a kernel trace shows it, namespaces stripped; "none" for an error route.  Returns the length.
 inline int route_name(const GatherRoute &r, char *buf, size_t n) {
     const auto b = [](bool v) { return v ? "true" : "false"; };

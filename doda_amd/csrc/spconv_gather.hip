@@ -29,8 +29,6 @@
 #include "spconv_common.hpp"
 #include "wgrad_backends.hpp"
 #include <stdlib.h>
-#include <utility>
-#include <type_traits>
 
 namespace {
 
@@ -930,20 +928,7 @@ __global__ __launch_bounds__(256) void conv_fast(const typename P::elem *__restr
     }
 }
 
-// kernel shapes that carry the folded BatchNorm (PreArgs): 16-byte pieces of same-dtype rows, split blocks — the shapes of the
-// coarse U-Net levels, where a BatchNorm sweep of its own is a launch-floor kernel
-template <class P, int NBW, int S, bool SPLIT>
-constexpr bool pre_shape() {
-    return SPLIT && ((NBW == 1 && S == 1) || (NBW == 4 && S == 2)) && (std::is_same<P, PBF16W>::value || std::is_same<P, PF32>::value);
-}
-
-// the legal (NBW, S, SPLIT) triples of conv_fast; conv_gather takes the unsplit ones.  The set of triples defines what is compiled;
-// their order only the order in which the compiler emits the kernels (the last entry first).  With this order every kernel's
-// instruction stream equalled the one under the ladders this table replaced; another order may schedule a kernel differently.
-template <int NBW_, int S_, bool SPLIT_> struct Shape { static constexpr int NBW = NBW_, S = S_; static constexpr bool SPLIT = SPLIT_; };
-template <class... Sh> struct Shapes {};
-typedef Shapes<Shape<8, 1, false>, Shape<4, 1, false>, Shape<4, 2, false>, Shape<3, 1, false>, Shape<2, 1, false>, Shape<2, 2, false>,
-               Shape<2, 4, false>, Shape<1, 1, false>, Shape<1, 2, false>, Shape<3, 2, true>, Shape<4, 2, true>, Shape<1, 1, true>> FastShapes;
+// the route's (NBW, S, SPLIT) as a Shape of FastShapes (gather_plan.hpp)
 template <class F, class... Sh>
 int with_shape(const GatherRoute &r, Shapes<Sh...>, F &&f) {
     int st = DODA_ERR_UNSUPPORTED;
@@ -951,46 +936,43 @@ int with_shape(const GatherRoute &r, Shapes<Sh...>, F &&f) {
     return st;
 }
 
-template <class P, class Sh>
+template <class P, GatherPolicy POLICY, class Sh>
 int launch_fast(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
-    constexpr int NBW = Sh::NBW, S = Sh::S;
-    constexpr bool SPLIT = Sh::SPLIT;
-    // Ring depth.  Re-measured after the EXEC-masked gathers and the wide / pair units went in: with
+    // Ring depth (GP_RING_DEPTH).  Re-measured after the EXEC-masked gathers and the wide / pair units went in: with
     // every load hitting L1 (ablation) the kernel time did not move, i.e. the unit loop is paced by
     // instruction issue and by how many waves a SIMD can interleave, not by memory latency.  Depth 8
     // cost 124 VGPRs (4 waves per SIMD); depth 3: level-1 16->16 52 -> 38 us, level-2 32->32 37 -> 32 us.
     // (round 6: depth 6 for the 16-row split blocks of the coarse levels — ~20 units per wave, one wave per SIMD — measured the same
     // 8.1-8.2 us per launch: those kernels are not paced by the ring either)
-    constexpr int D = GP_RING_DEPTH;
-    const auto go = [&](auto kernel, const PreArgs &pre) {
-        hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.block), 0, s, (const typename P::elem *)a.x, r.x_bytes, a.kc, a.wp, r.w_bytes, a.nc,
-                           r.geo.NB, a.tbl, r.tbl_bytes, a.ld, a.K, a.n_out, a.y, r.y_bytes, a.res, a.ep, pre);
-    };
-    if constexpr (pre_shape<P, NBW, S, SPLIT>()) {   // (plan_gather names a PRE for these shapes only)
-        if (r.pre) {
-            with_bool(r.stats, [&](auto st) {
-                constexpr bool ST = decltype(st)::value;
-                if (r.pre == 1) go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 1>, *a.pre);
-                else if (r.pre == 2) go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 2>, *a.pre);
-                else go(conv_fast<P, NBW, S, D, false, SPLIT, ST, 3>, *a.pre);
-            });
-            return doda_check_launch();
+    int status = DODA_ERR_UNSUPPORTED;
+    const auto go = [&](auto o32, auto st, auto pre) {
+        constexpr bool O32 = decltype(o32)::value;
+        constexpr int PRE = decltype(pre)::value;
+        if constexpr (fast_compiled(sizeof(typename P::elem), POLICY, Sh::NBW, Sh::S, Sh::SPLIT, O32, PRE)) {
+            hipLaunchKernelGGL((conv_fast<P, Sh::NBW, Sh::S, GP_RING_DEPTH, O32, Sh::SPLIT, decltype(st)::value, PRE>), dim3(r.grid),
+                               dim3(r.block), 0, s, (const typename P::elem *)a.x, r.x_bytes, a.kc, a.wp, r.w_bytes, a.nc, r.geo.NB, a.tbl,
+                               r.tbl_bytes, a.ld, a.K, a.n_out, a.y, r.y_bytes, a.res, a.ep, PRE ? *a.pre : PreArgs{});
+            status = doda_check_launch();
         }
-    }
+    };
     with_bool(r.out32, [&](auto o32) { with_bool(r.stats, [&](auto st) {
-        go(conv_fast<P, NBW, S, D, decltype(o32)::value, SPLIT, decltype(st)::value>, PreArgs{});
+        if (r.pre == 1) go(o32, st, Int<1>{});
+        else if (r.pre == 2) go(o32, st, Int<2>{});
+        else if (r.pre == 3) go(o32, st, Int<3>{});
+        else go(o32, st, Int<0>{});
     }); });
-    return doda_check_launch();
+    return status;
 }
 
 template <class T, class Sh>
 int launch_generic(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
     typedef typename T::elem elem;
-    if constexpr (!Sh::SPLIT)
+    constexpr bool compiled = generic_compiled(sizeof(elem), Sh::NBW, Sh::S, Sh::SPLIT);
+    if constexpr (compiled)
         hipLaunchKernelGGL((conv_gather<T, Sh::NBW, Sh::S>), dim3(r.grid), dim3(r.block), 0, s, (const elem *)a.x, a.kc,
                            (const typename T::frag *)a.wp, a.nc, r.geo.NB, a.tbl, a.ld, a.K, a.n_out, (elem *)a.y, (int)r.vec_ok,
                            (const elem *)a.res);
-    return Sh::SPLIT ? DODA_ERR_UNSUPPORTED : doda_check_launch();
+    return compiled ? doda_check_launch() : DODA_ERR_UNSUPPORTED;
 }
 
 // conv_gather / conv_fast: the route's element size and policy as the storage / policy class
@@ -998,9 +980,9 @@ int launch_dense(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
     return with_shape(r, FastShapes{}, [&](auto sh) {
         typedef decltype(sh) Sh;
         if (r.family == GF_GENERIC) return r.esz == 4 ? launch_generic<F32, Sh>(r, a, s) : launch_generic<BF16, Sh>(r, a, s);
-        if (r.esz == 4) return r.policy == GP_F32_SPLIT ? launch_fast<PF32S, Sh>(r, a, s) : launch_fast<PF32, Sh>(r, a, s);
-        return r.policy == GP_WIDE ? launch_fast<PBF16W, Sh>(r, a, s) : r.policy == GP_PAIR ? launch_fast<PBF16P, Sh>(r, a, s)
-                                                                                          : launch_fast<PBF16, Sh>(r, a, s);
+        if (r.esz == 4) return r.policy == GP_F32_SPLIT ? launch_fast<PF32S, GP_F32_SPLIT, Sh>(r, a, s) : launch_fast<PF32, GP_NARROW, Sh>(r, a, s);
+        return r.policy == GP_WIDE   ? launch_fast<PBF16W, GP_WIDE, Sh>(r, a, s)
+               : r.policy == GP_PAIR ? launch_fast<PBF16P, GP_PAIR, Sh>(r, a, s) : launch_fast<PBF16, GP_NARROW, Sh>(r, a, s);
     });
 }
 

@@ -808,35 +808,32 @@ __global__ __launch_bounds__(256) void conv_up32(const void *__restrict__ x, uns
 
 int doda_tile::launch(const GatherRoute &r, const GatherOperands &a, hipStream_t s) {
     const dim3 grid(r.grid), block(r.block);
-    const EpiArgs &ep = a.ep;
-    const int NB = r.geo.NB;
     const TileBookView tb = r.family == GF_UP32 ? TileBookView{} : tilebook_view(const_cast<void *>(a.tilebook), a.n_out);
+    int status = DODA_OK;
     with_bool(r.out32, [&](auto o32) { with_bool(r.stats, [&](auto st) {
         constexpr bool O32 = decltype(o32)::value, ST = decltype(st)::value;
-        // conv_tile<MODE, OUT32, STATS, MAXNB, DUAL>: MODE 2 (fp32 rows) is always OUT32; the dual kernel serves 32 and 64 output
-        // channels with MAXNB 2, and 64 with their statistics with MAXNB 4
-        const auto tile = [&](auto mode, auto maxnb, auto dual) {
-            hipLaunchKernelGGL((conv_tile<decltype(mode)::value, O32, ST, decltype(maxnb)::value, decltype(dual)::value>), grid, block, 0, s,
-                               a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, NB, a.tbl, a.ld, a.n_out, tb, a.y, r.y_bytes, a.res, ep);
+        const auto tile = [&](auto mode, auto maxnb, auto dual) {   // (tile_compiled, gather_plan.hpp: what exists, and why)
+            if constexpr (tile_compiled(decltype(mode)::value, O32, ST, decltype(maxnb)::value, decltype(dual)::value))
+                hipLaunchKernelGGL((conv_tile<decltype(mode)::value, O32, ST, decltype(maxnb)::value, decltype(dual)::value>), grid, block, 0,
+                                   s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, r.geo.NB, a.tbl, a.ld, a.n_out, tb, a.y, r.y_bytes, a.res, a.ep);
+            else status = DODA_ERR_UNSUPPORTED;
         };
         const auto plain = [&](auto mode) {
             if (r.maxnb == 2) tile(mode, Int<2>{}, std::false_type{});
             else tile(mode, Int<1>{}, std::false_type{});
         };
         if (r.family == GF_UP32)
-            hipLaunchKernelGGL((conv_up32<O32, ST>), grid, block, 0, s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, NB, a.K, a.tbl, a.ld, a.n_out,
-                               a.y, r.y_bytes, a.res, ep);
+            hipLaunchKernelGGL((conv_up32<O32, ST>), grid, block, 0, s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, r.geo.NB, a.K, a.tbl, a.ld, a.n_out,
+                               a.y, r.y_bytes, a.res, a.ep);
         else if (r.family == GF_TILE16)
             hipLaunchKernelGGL((conv_tile16<O32, ST>), grid, block, 0, s, a.x, r.x_bytes, a.wp, r.w_bytes, a.nc, a.tbl, a.ld, a.n_out, tb,
-                               a.y, r.y_bytes, a.res, ep);
+                               a.y, r.y_bytes, a.res, a.ep);
         else if (r.dual) {
-            if constexpr (ST) { if (r.maxnb == 4) return tile(Int<1>{}, Int<4>{}, std::true_type{}); }
-            tile(Int<1>{}, Int<2>{}, std::true_type{});
-        } else {
-            if constexpr (O32) { if (r.mode == 2) return plain(Int<2>{}); }
-            if (r.mode == 1) plain(Int<1>{});
-            else plain(Int<0>{});
-        }
+            if (r.maxnb == 4) tile(Int<1>{}, Int<4>{}, std::true_type{});
+            else tile(Int<1>{}, Int<2>{}, std::true_type{});
+        } else if (r.mode == 2) plain(Int<2>{});
+        else if (r.mode == 1) plain(Int<1>{});
+        else plain(Int<0>{});
     }); });
-    return doda_check_launch();
+    return status != DODA_OK ? status : doda_check_launch();
 }

@@ -3,12 +3,57 @@
 //   status=<s> route=<route_name> grid=<g> block=<b> parts=<n_part> frags=<pack fragments> wbytes=<pack bytes>
 // Absent keys: a dense, aligned bf16 call with a large enough workspace, n_in = ld = n_out, no epilogue options; a prologue's
 // operands all present, aligned and dense.
+// With the argument `--compiled`: no stdin; one line per instantiation that the predicates of gather_plan.hpp admit, as route_name
+// writes it, from a walk over the whole parameter grid.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../doda_amd/csrc/gather_plan.hpp"
 
-int main() {
+static void admit(bool yes, GatherRoute r) {
+    if (!yes) return;
+    char name[96];
+    r.status = DODA_OK;
+    route_name(r, name, sizeof name);
+    puts(name);
+}
+
+static void print_compiled() {
+    for (int esz = 2; esz <= 4; esz += 2)
+        for (int nbw = 0; nbw <= 9; ++nbw)
+            for (int s = 0; s <= 5; ++s)
+                for (int split = 0; split < 2; ++split) {
+                    GatherRoute r{};
+                    r.esz = (uint8_t)esz; r.NBW = (uint8_t)nbw; r.S = (uint8_t)s; r.split = split;
+                    r.family = GF_GENERIC;
+                    admit(generic_compiled(esz, nbw, s, split), r);
+                    r.family = GF_FAST;
+                    for (int p = GP_NARROW; p <= GP_F32_SPLIT; ++p)
+                        for (int o32 = 0; o32 < 2; ++o32)
+                            for (int st = 0; st < 2; ++st)
+                                for (int pre = -1; pre <= 4; ++pre) {
+                                    r.policy = (GatherPolicy)p; r.out32 = o32; r.stats = st; r.pre = (uint8_t)pre;
+                                    admit(fast_compiled(esz, r.policy, nbw, s, split, o32, pre), r);
+                                }
+                }
+    for (int o32 = 0; o32 < 2; ++o32)
+        for (int st = 0; st < 2; ++st) {
+            GatherRoute r{};
+            r.out32 = o32; r.stats = st;
+            for (int mode = -1; mode <= 3; ++mode)
+                for (int maxnb = 0; maxnb <= 5; ++maxnb)
+                    for (int dual = 0; dual < 2; ++dual) {
+                        r.family = GF_TILE; r.mode = (uint8_t)mode; r.maxnb = (uint8_t)maxnb; r.dual = dual;
+                        admit(tile_compiled(mode, o32, st, maxnb, dual), r);
+                    }
+            r.family = GF_TILE16; admit(true, r);     // conv_tile16, conv_up32: every (OUT32, STATS); conv_wlds48: both STATS
+            r.family = GF_UP32; admit(true, r);
+            r.family = GF_WLDS48; admit(!o32, r);
+        }
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "--compiled")) { print_compiled(); return 0; }
     char line[4096];
     while (fgets(line, sizeof line, stdin)) {
         GatherCall c{};

@@ -4,9 +4,10 @@ instantiation a call reaches, with which grid and how many statistics rows, is c
 tools/gatherroutes.py — asserted against tests/data/gather_routes.json, the routes recorded on an MI355X (kernel trace) from the
 ladders the plan replaced — and for a dense sweep over row counts, whose routes must be compiled instantiations
 (tests/data/gather_instantiations.json, the kernel symbols of the three code objects) with grids that cover the rows.  An extended sweep (tools/gathernumerics.py: out32, the prologue kinds, K, kc,
-the broadcast residual, every switch off, f32_split_rows = 0) settles every compiled name: the numerics probes of
-tests/test_gpu_gather_numerics.py (tests/data/gather_numerics.json, regenerated here from the plan) reach it, or
-tests/data/gather_unreached.json states the condition of the plan that excludes it."""
+the broadcast residual, every switch off, f32_split_rows = 0) settles every compiled name: the instantiations the predicates of
+gather_plan.hpp admit (the program's `--compiled` mode; the launchers instantiate nothing else), the kernel symbols of the built
+objects, the routes of that sweep and the routes of the numerics probes of tests/test_gpu_gather_numerics.py
+(tests/data/gather_numerics.json, regenerated here from the plan) are one set of 247 names."""
 import importlib.util
 import json
 import os
@@ -47,6 +48,7 @@ def planner(request, tmp_path_factory):
         assert len(out) == len(lines) and all(out)
         return [dict(status=int(m[1]), route=m[2], grid=int(m[3]), block=int(m[4]), parts=int(m[5]), frags=int(m[6]))
                 for m in out]
+    ask.compiled = lambda: subprocess.run([exe, "--compiled"], capture_output=True, text=True, check=True, timeout=300).stdout.splitlines()
     return ask
 
 
@@ -136,20 +138,21 @@ def test_every_route_of_a_dense_sweep_is_compiled_and_covers_its_rows(planner):
 
 
 def test_extended_sweep_settles_every_instantiation(planner):
-    """Every one of the 318 compiled names is reached by a numerics probe or listed as unreachable, never both, never neither; the
-    recorded probe list is the one the plan generates, and every probe is the smallest shape with a ragged last wave tile."""
+    """The names the predicates admit, the compiled names, the routes of the extended sweep and the routes of the numerics probes are
+    the same 247; the recorded probe list is the one the plan generates, and every probe is the smallest shape with a ragged last
+    wave tile."""
     gn = _numerics()
     compiled = set(json.load(open(os.path.join(ROOT, "tests", "data", "gather_instantiations.json"))))
-    listed = json.load(open(os.path.join(ROOT, "tests", "data", "gather_unreached.json")))
-    unreached = {u["route"] for u in listed}
-    assert len(unreached) == len(listed) and all(u["condition"].strip() for u in listed)
+    admitted = planner.compiled()
+    assert len(admitted) == len(set(admitted)) == 247
     produced = set()
     probes = gn.generate(planner, produced)
-    assert not produced & unreached, sorted(produced & unreached)
     recorded = gn.load_probes()
     probed = {p["route"] for p in recorded}
-    assert produced <= probed, sorted(produced - probed)
-    assert len(compiled) == 318 and produced | unreached == compiled and len(produced) + len(unreached) == 318
+    assert set(admitted) == compiled == produced == probed, [sorted(set(admitted) ^ s) for s in (compiled, produced, probed)]
+    families = [re.match(r"\w+", n).group(0) for n in admitted]
+    assert {f: families.count(f) for f in families} == {"conv_fast": 200, "conv_gather": 16, "conv_tile": 21, "conv_tile16": 4,
+                                                        "conv_up32": 4, "conv_wlds48": 2}
     assert probes == recorded        # regenerate: see tools/gathernumerics.py generate()
     assert {p["group"] for p in recorded} == set(gn.GROUPS)
     # the planner names the recorded route for the recorded shape, and no probe has only full wave tiles

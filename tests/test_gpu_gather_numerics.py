@@ -1,8 +1,8 @@
 """What the kernels behind doda_spconv_gather_ex COMPUTE, for every instantiation the route plan (csrc/gather_plan.hpp) can reach:
 tests/test_gpu_gather_routes.py pins which kernel a call reaches, this file compares one call per reachable instantiation
-(tests/data/gather_numerics.json, generated from the plan: tools/gathernumerics.py; 247 of the 318 compiled names, the other 71 are
-in tests/data/gather_unreached.json with the condition that excludes them — tests/test_gather_plan_host.py keeps both lists
-complete) with an fp64 reference on the device: per offset index_select, then matmul.
+(tests/data/gather_numerics.json, generated from the plan: tools/gathernumerics.py; all 247 compiled names — the plan's predicates
+decide what is compiled, and tests/test_gather_plan_host.py holds admitted, compiled and probed names to one set) with an fp64
+reference on the device: per offset index_select, then matmul.
 
 Each probe is the smallest shape at which its kernel can still go wrong: a ragged last wave tile (37 rows, or a threshold
 16 (W - 1) + 1), a 300-voxel plane for the tile kernels (a full and a 44-row tile, six idle persistent workgroups), tables with

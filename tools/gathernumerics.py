@@ -4,8 +4,8 @@ each compared with an fp64 reference (tools/gatherroutes.py --numerics GROUP; te
 The probe list is GENERATED from the plan: `space()` walks the calls, the host planner (tests/host/gather_plan_main.cpp) names the
 route of each, `select()` keeps per route the call of fewest output rows and `shape()` moves it to the smallest shape at which the
 kernel can still go wrong (a ragged last wave tile, a second tile, idle persistent workgroups).  tests/data/gather_numerics.json is
-that list as recorded; tests/test_gather_plan_host.py regenerates it and asserts equality, and that the names it reaches plus
-tests/data/gather_unreached.json are exactly tests/data/gather_instantiations.json.
+that list as recorded; tests/test_gather_plan_host.py regenerates it and asserts equality, and that the names it reaches, the names
+the predicates of gather_plan.hpp admit and tests/data/gather_instantiations.json (what is compiled) are one set of 247.
 
 The checkers (`reference`, `check`) are plain torch on whatever device the tensors are on: tests/test_gather_numerics_host.py feeds
 them the rounded reference and corrupted copies of it on the CPU."""

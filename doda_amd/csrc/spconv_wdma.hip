@@ -407,37 +407,16 @@ __global__ __launch_bounds__(512) void wgrad_dma_reduce(const WdRJobs jobs) {
 // layer (8 layers per call).  The fp32 matrix rate (1/16 of bf16) puts 53 us of MFMA issue under a dense layer, 4-byte LDS
 // operand reads (one per lane and k-step: 4.6 k LDS instructions per tile) another ~45 us, and sixteen waves leaving a
 // barrier together run the two phases one after the other.  Removed)
-bool g_use_wdma = !(getenv("DODA_NO_WDMA") && getenv("DODA_NO_WDMA")[0] == '1');
+static_assert(WP_TILE_ROWS == TB_T && WP_TILE_K == TB_K, "wgrad_plan.hpp restates these constants");
 
 // One 16 x 16 channel block of a layer's weight gradient: x / dy point at the block's first channel (bf16), rows x_stride /
 // dy_stride bytes apart; the block's corner in the layer's dw [27][ca][cb] and its strides (ldo = ca * cb, ldc = cb).
 struct Block { const void *x, *dy; float *dw; int x_stride, dy_stride, ldo, ldc, accumulate; };
 struct WdArgs { WdJobs jobs; WdRJobs red; };      // the kernel arguments of one launch (at most WD_MAX_JOBS blocks)
 
-int groups_for(int n_rows) {
-    const int nt = (n_rows + TB_T - 1) / TB_T;
-    int groups = (nt + 7) / 8 * 8;
-    return groups > 256 ? 256 : groups;
-}
-// workspace per 16 x 16 channel block
-size_t block_partial_bytes(int n_rows) { return align_up((size_t)groups_for(n_rows) * TB_K * 256 * sizeof(float), 256); }
-int n_blocks(const doda_wgrad_job &j) { return (j.ca / 16) * (j.cb / 16); }
-
 }  // namespace
 
 namespace doda_wdma {
-
-bool enabled() { return g_use_wdma; }
-void set_enabled(bool on) { g_use_wdma = on; }
-
-// bf16, K = 27, a tilebook of the job's table; 16 -> 16, and — round 4 — 16 .. 64 channels on either side as 16 x 16 channel
-// blocks over row-strided slices
-bool eligible(const doda_wgrad_job &j) {
-    return j.tilebook && j.tbl && j.elem_bytes == 2 && j.ca % 16 == 0 && j.ca <= 64 && j.cb % 16 == 0 && j.cb <= 64 &&
-           j.K == 27 && j.n_rows > 0 && j.a && j.b && j.dw &&
-           j.n_a == j.n_rows && j.ld >= j.n_rows && (size_t)j.n_rows * 128 < 0x7ffffff0ull && (size_t)j.K * j.ld * 4 < 0xffffffffull &&
-           !(((uintptr_t)j.a | (uintptr_t)j.b | (uintptr_t)j.tilebook) & 15) && enabled();
-}
 
 // one launch sequence per rulebook (jobs sharing table + tilebook): their 16 x 16 channel blocks in queue order, the blocks'
 // partials contiguous
@@ -454,9 +433,9 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
             done[r] = 1;
             p.order.push_back(idx[r]);
             ++l.n_jobs;
-            l.n_blocks += n_blocks(j);
+            l.n_blocks += wdma_blocks(j);
         }
-        p.partial_bytes += (size_t)l.n_blocks * block_partial_bytes(j0.n_rows);
+        p.partial_bytes += (size_t)l.n_blocks * wdma_block_partial_bytes(j0.n_rows);
         p.launches.push_back(l);
     }
     return p;
@@ -476,7 +455,7 @@ void write_desc(Plan &p, const doda_wgrad_job *jobs, char *part) {
                     blocks.push_back(Block{(const char *)j.a + ci * es, (const char *)j.b + co * es, j.dw + (size_t)ci * j.cb + co,
                                            j.ca * es, j.cb * es, j.ca * j.cb, j.cb, (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0});
         }
-        const int groups = groups_for(j0.n_rows), nt = (j0.n_rows + TB_T - 1) / TB_T;
+        const int groups = wdma_groups(j0.n_rows), nt = (j0.n_rows + TB_T - 1) / TB_T;
         size_t used = l.part_off;      // partial slots handed out so far (bytes)
         for (int first = 0; first < l.n_blocks; first += WD_MAX_JOBS) {
             const int nj = l.n_blocks - first < WD_MAX_JOBS ? l.n_blocks - first : WD_MAX_JOBS;
@@ -518,7 +497,9 @@ int launch(const Plan &p, const doda_wgrad_job *jobs, hipStream_t s) {
         const doda_wgrad_job &j0 = jobs[p.order[l.first_job]];
         const TileBookView tb = tilebook_view(const_cast<void *>(j0.tilebook), j0.n_rows);
         for (int first = 0; first < l.n_blocks; first += WD_MAX_JOBS, ++a) {
-            hipLaunchKernelGGL(wgrad_dma16, dim3(groups_for(j0.n_rows)), dim3(1024), 0, s, a->jobs, j0.tbl, j0.ld, j0.n_rows, tb);
+            doda_wgrad::trace("wgrad_dma16", wdma_groups(j0.n_rows), 1024, a->jobs.n);
+            hipLaunchKernelGGL(wgrad_dma16, dim3(wdma_groups(j0.n_rows)), dim3(1024), 0, s, a->jobs, j0.tbl, j0.ld, j0.n_rows, tb);
+            doda_wgrad::trace("wgrad_dma_reduce", TB_K * 256 / 32 * a->jobs.n, 512, a->jobs.n);
             hipLaunchKernelGGL(wgrad_dma_reduce, dim3(TB_K * 256 / 32, a->jobs.n), dim3(512), 0, s, a->red);
         }
     }

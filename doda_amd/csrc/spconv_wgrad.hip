@@ -14,11 +14,10 @@
 // by a second kernel in fixed order (wgrad_common.hpp wgrad_fold): deterministic, no float atomics.
 //
 // This file also holds the entry point of every weight gradient, doda_spconv_wgrad_multi: ONE call plan (make_call_plan: the
-// class of every job, each class's plan, the workspace and descriptor layout) serves the size query and the call, and the
-// four kernel classes — this file's gather-table class (namespace doda_dense) and the three of wgrad_backends.hpp — are
+// class of every job and each class's geometry from the pure host functions of wgrad_plan.hpp, then the workspace and descriptor
+// layout) serves the size query and the call, and the four kernel classes — this file's gather-table class (namespace doda_dense) and the three of wgrad_backends.hpp — are
 // planned, described and launched through the same three steps.
 #include "wgrad_common.hpp"
-#include <stdlib.h>
 #include <string.h>
 #include <mutex>
 #include <vector>
@@ -52,7 +51,7 @@ struct F32 {
 // A = [a_hi | a_lo] against B = [b_hi | b_hi], then against [b_lo | b_lo]: all four partial products, fp32 accumulate.  The
 // fp32 matrix rate of this part is 1/16 of bf16 and four v_mfma_f32_16x16x4_f32 per 16 rows were the largest item of the
 // fp32 step (4.8 of 13.8 ms of kernels); same LDS reads (one float per lane, row and operand), same bytes.  Used for layers
-// of many rows (plan_job); small layers keep the exact chain.
+// of many rows (wgrad_plan.hpp plan_dense); small layers keep the exact chain.
 struct F32S : F32 {
     static constexpr int KSTEPS = RT / 16;
     struct kfrag { unsigned hi[2], lo[2]; };
@@ -353,104 +352,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float *__restrict__ pa
 }
 
 
-struct Plan {
-    int TA, TB, OGW, n_og, n_tag, n_tbg, R, rows_per_chunk;
-};
-static const int MULTI_MIN_ROWS = getenv("DODA_WGRAD_MIN_ROWS") ? atoi(getenv("DODA_WGRAD_MIN_ROWS")) : 512;
-
-// multi: the job is one of many in a doda_spconv_wgrad_multi launch — the other layers fill the chip,
-// so a layer needs far fewer row chunks (each chunk costs K*ca*cb*4 bytes of partials to write and reduce)
-Plan make_plan(int K, int ca, int cb, int n_rows, int elem_bytes, bool multi = false) {
-    Plan p;
-    const int ta = (ca + 15) / 16, tb = (cb + 15) / 16;
-    p.TA = (ta % 2 == 0) ? 2 : 1;
-    p.TB = (tb % 2 == 0) ? 2 : 1;
-    // 48-channel operands (level 3 of the U-Net): one 3 x 3 tile block gathers every row once instead of nine
-    // 1 x 1 blocks gathering a third of it each (and reading the table nine times)
-    static const bool no33 = getenv("DODA_WGRAD_NO33") && getenv("DODA_WGRAD_NO33")[0] == '1';
-    if (ta == 3 && tb == 3 && elem_bytes == 2 && K > 8 && !no33) { p.TA = 3; p.TB = 3; }
-    p.n_tag = ta / p.TA;
-    p.n_tbg = tb / p.TB;
-    // 2x2 accumulator tiles x 7 offsets would need 112 accumulator registers (1 wave/SIMD): give
-    // such blocks 4 offsets per wave and spread the offsets over several block groups instead
-    // offsets per wave for 1- and 2-tile blocks (rocprofv3, levels 1 / 3 / 5): bf16 7 -> 4 offsets
-    // 54.8 -> 52.2, 39.6 -> 35.3, 19.0 -> 14.3 us (fewer registers, half the partials); fp32 the other
-    // way round (91 vs 106 us at level 3): its 16 dY fragment reads per step amortise over more offsets
-    p.OGW = (p.TA * p.TB == 4 || elem_bytes == 2) ? 4 : MAX_OGW;
-    if (p.TA * p.TB == 9) p.OGW = 2;   // 72 accumulator registers
-    if (K <= 8) p.OGW = (p.TA * p.TB == 4) ? 2 : 2;
-    p.n_og = div_up(K, 4 * p.OGW);
-    const int gy = p.n_tag * p.n_tbg * p.n_og;
-    const int rows = n_rows > 0 ? n_rows : 1;
-    // measured at M = 600k / 183k (rocprofv3): 1x1 and 2x1 tiles 68 -> 50 us going from 512 to 1024
-    // blocks (+5 us of partial reduce); 2x2 tiles are fastest at 512
-    // multi (whole U-Net step, wgrad + reduce): 1024 -> 1.86 ms, 512 -> 1.67, 256 -> 1.67, 128 -> 1.99
-    // (3 x 3 blocks: a block does nine tiles' worth of work and its chunk writes all K*ca*cb partials)
-    static const int t33 = getenv("DODA_WGRAD_T33") ? atoi(getenv("DODA_WGRAD_T33")) : 128;
-    const int target = p.TA * p.TB == 9 ? t33 : (multi ? 512 : ((p.TA * p.TB == 4) ? 512 : 1024));
-    int R = div_up(target, gy);         // blocks over the whole grid
-    // multi: at least MULTI_MIN_ROWS rows per chunk.  Every chunk writes K*ca*cb*4 bytes of partials; with
-    // 512 blocks per job the coarse levels (64..112 channels, a few thousand rows) wrote and re-read
-    // 5-28 MB per layer for a few hundred rows per chunk, and the launch holds ~40 other jobs to fill the
-    // chip with anyway
-    const int max_r = multi ? (rows / MULTI_MIN_ROWS > 1 ? rows / MULTI_MIN_ROWS : 1) : div_up(rows, RT);
-    if (R > max_r) R = max_r;
-    if (R < 1) R = 1;
-    p.rows_per_chunk = div_up(div_up(rows, R), RT) * RT;
-    p.R = div_up(rows, p.rows_per_chunk);
-    (void)K;
-    return p;
-}
-
 // ---- host side of the many-layer launch -------------------------------------------------------
-struct JobPlan {
-    Plan p;
-    int esz, vok, key;
-    int split;         // fp32 job multiplied as bf16 head / tail splits (F32S)
-    size_t ws_off;     // partials of this job inside the class's workspace (unused when it writes dw itself)
-    long long n_elem;
-};
+static_assert(WP_RT == RT && WP_MAX_OGW == MAX_OGW, "wgrad_plan.hpp restates these constants");
 
-bool plan_job(const doda_wgrad_job &j, JobPlan *out) {
-    if (j.ca <= 0 || j.cb <= 0 || j.K <= 0 || j.K > 4 * MAX_OGW || j.n_rows <= 0 || j.ld < j.n_rows || !j.a ||
-        !j.b || !j.tbl || !j.dw || (j.elem_bytes != 2 && j.elem_bytes != 4))
-        return false;
-    out->esz = j.elem_bytes;
-    out->vok = ((size_t)j.ca * j.elem_bytes % 16 == 0) && ((size_t)j.cb * j.elem_bytes % 16 == 0) &&
-               ((uintptr_t)j.a % 16 == 0) && ((uintptr_t)j.b % 16 == 0);
-    out->p = make_plan(j.K, j.ca, j.cb, j.n_rows, j.elem_bytes, true);
-    {   // OPT-IN (see spconv_gather.hip run_gather): fp32 jobs of at least DODA_F32_WGRAD_SPLIT_ROWS rows (0: all of them — one
-        // instantiation for every fp32 job keeps the layers of a step in shared launches; unset / -1: none, the exact chain)
-        static const long long min_rows = [] { const char *e = getenv("DODA_F32_WGRAD_SPLIT_ROWS"); return e && *e ? atoll(e) : -1ll; }();
-        out->split = (j.elem_bytes == 4 && min_rows >= 0 && (long long)j.n_rows >= min_rows) ? 1 : 0;
-    }
-    out->key = ((((j.elem_bytes * 4 + out->p.TA) * 4 + out->p.TB) * 8 + out->p.OGW) * 2 + out->vok) * 2 + out->split;
-    out->n_elem = (long long)j.K * j.ca * j.cb;
-    return true;
-}
-
-template <class T>
-void launch_multi_variant(const Plan &p, int vok, int total_blocks, const WJob *jobs_dev, int n, hipStream_t s) {
-    const dim3 grid(total_blocks), block(256);
-#define GO(TA, TB, OG)                                                                             \
-    do {                                                                                           \
-        if (vok) hipLaunchKernelGGL((wgrad_multi_kernel<T, TA, TB, OG, true>), grid, block, 0, s, jobs_dev, n); \
-        else hipLaunchKernelGGL((wgrad_multi_kernel<T, TA, TB, OG, false>), grid, block, 0, s, jobs_dev, n); \
-    } while (0)
-    if (p.OGW == 2) {
-        if (p.TA == 3 && p.TB == 3) GO(3, 3, 2);
-        else if (p.TA == 1 && p.TB == 1) GO(1, 1, 2);
-        else if (p.TA == 2 && p.TB == 1) GO(2, 1, 2);
-        else if (p.TA == 1 && p.TB == 2) GO(1, 2, 2);
-        else GO(2, 2, 2);
-    } else if (p.OGW == 4 && p.TA == 1 && p.TB == 1) GO(1, 1, 4);
-    else if (p.OGW == 4 && p.TA == 2 && p.TB == 1) GO(2, 1, 4);
-    else if (p.OGW == 4 && p.TA == 1 && p.TB == 2) GO(1, 2, 4);
-    else if (p.TA == 1 && p.TB == 1) GO(1, 1, 7);
-    else if (p.TA == 2 && p.TB == 1) GO(2, 1, 7);
-    else if (p.TA == 1 && p.TB == 2) GO(1, 2, 7);
-    else GO(2, 2, 4);
-#undef GO
+// the plan's instantiation: a walk over the compiled set (wgrad_plan.hpp DenseTiles, dense_compiled), which holds every plan that
+// doda_dense::plan lets through
+template <class T, WgradPolicy P, class... Tile>
+void launch_multi_variant(WgradTiles<Tile...>, const DensePlan &p, int total_blocks, const WJob *jobs_dev, int n, hipStream_t s) {
+    const auto go = [&](auto tile) {
+        typedef decltype(tile) Tl;
+        if constexpr (dense_compiled(P, Tl::TA, Tl::TB, Tl::OGW))
+            if (p.TA == Tl::TA && p.TB == Tl::TB && p.OGW == Tl::OGW)
+                with_bool(p.vok, [&](auto vok) {
+                    hipLaunchKernelGGL((wgrad_multi_kernel<T, Tl::TA, Tl::TB, Tl::OGW, decltype(vok)::value>), dim3(total_blocks), dim3(256), 0, s, jobs_dev, n);
+                });
+    };
+    (go(Tile{}), ...);
 }
 
 // pinned staging for the descriptor upload (one per process, grow-only, reuse guarded by an event)
@@ -469,37 +386,36 @@ namespace doda_dense {
 
 struct Plan {
     std::vector<int> idx;
-    std::vector<JobPlan> jp;           // per job of idx
+    std::vector<DensePlan> jp;         // per job of idx
+    std::vector<size_t> ws_off;        // its partials inside the class's workspace
+    std::vector<char> red;             // 0: its one row chunk overwrites dw itself; 1: the shared fold; 2: the per-layer scalar reduce
     struct Group { int first, count, blocks, rep; };   // one launch per kernel variant; rep: a job of the variant
     std::vector<Group> groups;
     std::vector<int> order, blk_end;   // per descriptor: position in idx, inclusive block prefix inside its group
-    bool valid = true;                 // false: a job this kernel cannot run (DODA_ERR_INVALID)
+    int status = DODA_OK;              // DODA_ERR_INVALID: a job this kernel cannot run; DODA_ERR_UNSUPPORTED: a plan outside the compiled set
     size_t partial_bytes = 0, desc_bytes = 0;
     int n_reduce = 0;
 };
-
-// partials unless the job's one row chunk can overwrite dw itself
-bool needs_partial(const JobPlan &jp, const doda_wgrad_job &j) { return jp.p.R > 1 || (j.flags & DODA_WGRAD_ACCUMULATE); }
-// whole float quads: the shared fold; else the per-layer scalar reduce
-bool quads(const JobPlan &jp, const doda_wgrad_job &j) { return jp.n_elem % 4 == 0 && (uintptr_t)j.dw % 16 == 0; }
-
-// rows per chunk of the job's plan (the wide class sums over the same chunks)
-int rows_per_chunk(const doda_wgrad_job &j) { return make_plan(j.K, j.ca, j.cb, j.n_rows, j.elem_bytes, true).rows_per_chunk; }
 
 Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
     Plan p;
     p.idx = idx;
     p.jp.resize(idx.size());
+    p.ws_off.resize(idx.size());
+    p.red.resize(idx.size());
     std::vector<int> keys;
     for (size_t k = 0; k < idx.size(); ++k) {
-        JobPlan &jp = p.jp[k];
+        DensePlan &jp = p.jp[k];
         const doda_wgrad_job &j = jobs[idx[k]];
-        if (!plan_job(j, &jp)) { jp.key = -1; p.valid = false; continue; }
-        jp.ws_off = p.partial_bytes;
-        if (needs_partial(jp, j)) {
-            p.partial_bytes += align_up((size_t)jp.p.R * jp.n_elem * 4, 256);
-            p.n_reduce += quads(jp, j) ? 1 : 0;
-        }
+        jp.key = -1;
+        if (!dense_valid(j)) { p.status = DODA_ERR_INVALID; continue; }
+        jp = plan_dense(j, doda_wgrad::switches());
+        if (!dense_compiled(jp.policy, jp.TA, jp.TB, jp.OGW) && p.status == DODA_OK) p.status = DODA_ERR_UNSUPPORTED;
+        const bool quads = (long long)j.K * j.ca * j.cb % 4 == 0 && (uintptr_t)j.dw % 16 == 0;   // whole float quads
+        p.red[k] = !dense_needs_partial(jp, j) ? 0 : quads ? 1 : 2;
+        p.ws_off[k] = p.partial_bytes;
+        p.partial_bytes += dense_partial_bytes(jp, j);
+        p.n_reduce += p.red[k] == 1;
         bool seen = false;
         for (int key : keys) seen |= key == jp.key;
         if (!seen) keys.push_back(jp.key);
@@ -508,9 +424,8 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
         Plan::Group g{(int)p.order.size(), 0, 0, -1};
         for (size_t k = 0; k < idx.size(); ++k) {
             if (p.jp[k].key != key) continue;
-            const auto &q = p.jp[k].p;
             if (g.rep < 0) g.rep = (int)k;
-            g.blocks += q.R * q.n_tag * q.n_tbg * q.n_og;
+            g.blocks += p.jp[k].blocks;
             p.order.push_back((int)k);
             p.blk_end.push_back(g.blocks);
             ++g.count;
@@ -524,30 +439,31 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
 void write_desc(const Plan &p, const doda_wgrad_job *jobs, char *part, void *desc, std::vector<RJob> &reduce, int *reduce_blocks) {
     WJob *wj = (WJob *)desc;
     for (size_t q = 0; q < p.order.size(); ++q) {
-        const JobPlan &jp = p.jp[p.order[q]];
-        const doda_wgrad_job &j = jobs[p.idx[p.order[q]]];
+        const int k = p.order[q];
+        const DensePlan &jp = p.jp[k];
+        const doda_wgrad_job &j = jobs[p.idx[k]];
         WJob d;
         d.a = j.a; d.b = j.b; d.tbl = j.tbl;
-        d.out = needs_partial(jp, j) ? (float *)(part + jp.ws_off) : j.dw;
+        d.out = p.red[k] ? (float *)(part + p.ws_off[k]) : j.dw;
         d.ca = j.ca; d.cb = j.cb; d.ld = j.ld; d.K = j.K; d.n_rows = j.n_rows;
-        d.rows_per_chunk = jp.p.rows_per_chunk; d.n_tag = jp.p.n_tag; d.n_tbg = jp.p.n_tbg; d.n_og = jp.p.n_og;
+        d.rows_per_chunk = jp.rows_per_chunk; d.n_tag = jp.n_tag; d.n_tbg = jp.n_tbg; d.n_og = jp.n_og;
         d.blk_end = p.blk_end[q];
         wj[q] = d;
     }
-    for (size_t k = 0; k < p.idx.size(); ++k) {
-        const doda_wgrad_job &j = jobs[p.idx[k]];
-        if (needs_partial(p.jp[k], j) && quads(p.jp[k], j))
-            doda_wgrad::push_reduce(reduce, reduce_blocks, part + p.jp[k].ws_off, j, p.jp[k].p.R);
-    }
+    for (size_t k = 0; k < p.idx.size(); ++k)
+        if (p.red[k] == 1) doda_wgrad::push_reduce(reduce, reduce_blocks, part + p.ws_off[k], jobs[p.idx[k]], p.jp[k].R);
 }
 
 int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
     const WJob *wj_dev = (const WJob *)desc_dev;
     for (const Plan::Group &g : p.groups) {
-        const JobPlan &jp = p.jp[g.rep];
-        if (jp.esz == 4 && jp.split) launch_multi_variant<F32S>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
-        else if (jp.esz == 4) launch_multi_variant<F32>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
-        else launch_multi_variant<BF16>(jp.p, jp.vok, g.blocks, wj_dev + g.first, g.count, s);
+        const DensePlan &q = p.jp[g.rep];
+        char name[64];
+        dense_name(q, name, sizeof name);
+        doda_wgrad::trace(name, g.blocks, 256, g.count);
+        if (q.policy == WP_F32S) launch_multi_variant<F32S, WP_F32S>(DenseTiles{}, q, g.blocks, wj_dev + g.first, g.count, s);
+        else if (q.policy == WP_F32) launch_multi_variant<F32, WP_F32>(DenseTiles{}, q, g.blocks, wj_dev + g.first, g.count, s);
+        else launch_multi_variant<BF16, WP_BF16>(DenseTiles{}, q, g.blocks, wj_dev + g.first, g.count, s);
     }
     return doda_check_launch();
 }
@@ -555,45 +471,17 @@ int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
 // odd element counts: the per-layer scalar reduce
 int launch_scalar_reduce(const Plan &p, const doda_wgrad_job *jobs, char *part, hipStream_t s) {
     for (size_t k = 0; k < p.idx.size(); ++k) {
-        const JobPlan &jp = p.jp[k];
         const doda_wgrad_job &j = jobs[p.idx[k]];
-        if (!needs_partial(jp, j) || quads(jp, j)) continue;
-        hipLaunchKernelGGL(wgrad_reduce, dim3(div_up(jp.n_elem, 16)), dim3(256), 0, s, (const float *)(part + jp.ws_off), jp.p.R,
-                           jp.n_elem, j.dw, (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0);
+        const long long n_elem = (long long)j.K * j.ca * j.cb;
+        if (p.red[k] != 2) continue;
+        doda_wgrad::trace("wgrad_reduce", div_up(n_elem, 16), 256, 1);
+        hipLaunchKernelGGL(wgrad_reduce, dim3(div_up(n_elem, 16)), dim3(256), 0, s, (const float *)(part + p.ws_off[k]), p.jp[k].R,
+                           n_elem, j.dw, (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0);
     }
     return doda_check_launch();
 }
 
 }  // namespace doda_dense
-
-// job classes of a multi call
-enum { J_SKIP = 0, J_ZERO = 1, J_DENSE = 2, J_PAIRS = 3, J_TILE = 4, J_WIDE = 5 };
-
-// rows from which a rulebook's tile jobs take the LDS-staged kernel even when pair lists are at hand (measurement aid:
-// DODA_WDMA_MIN_ROWS)
-int wdma_min_rows() {
-    static const int v = getenv("DODA_WDMA_MIN_ROWS") ? atoi(getenv("DODA_WDMA_MIN_ROWS")) : 32768;
-    return v;
-}
-
-int classify(const doda_wgrad_job &j) {
-    if (j.n_rows == 0 && j.dw && j.K > 0 && j.ca > 0 && j.cb > 0)
-        return (j.flags & DODA_WGRAD_ACCUMULATE) ? J_SKIP : J_ZERO;
-    // a tilebook of the job's table and 48 .. 224 channels on both sides: the wide LDS-staged kernel (spconv_wwide.hip).  It
-    // takes 48 / 64-channel layers before wgrad_dma16, whose 16 x 16 blocks re-stage the tile once per block, and
-    // only jobs that would otherwise run the gather-table kernel, whose sums it reproduces (jobs with pair lists keep them)
-    if (doda_wwide::eligible(j) && !doda_pairs::eligible(j)) return J_WIDE;
-    // a tilebook of the job's table: the LDS-staged 16 x 16 tile kernel (spconv_wdma.hip).
-    // Round 4 (block-major chunks: one or two partials per workgroup whatever the number of layers): faster than the pair
-    // lists from ~40 k rows up — 8 layers per call: 601 k rows 21.3 / 43.3 us per layer, 152 k rows 7.2 / 13.0, level 2
-    // (154 k rows, 32 -> 32 as four blocks) 21.3 / 23.7, 37 k rows 10.3 / 10.1 (tools/wl2.py).  Round 3's schedule (every
-    // workgroup walked every layer: a flush per layer and workgroup) lost below 262 k rows.
-    if (doda_wdma::eligible(j) && (j.n_rows >= wdma_min_rows() || !doda_pairs::eligible(j))) return J_TILE;
-    // DODA_WGRAD_NO_PAIRS=1 keeps every job on the gather-table kernel (A/B measurements)
-    static const bool no_pairs = getenv("DODA_WGRAD_NO_PAIRS") && getenv("DODA_WGRAD_NO_PAIRS")[0] == '1';
-    if (doda_pairs::eligible(j) && (!no_pairs || !j.tbl)) return J_PAIRS;
-    return J_DENSE;
-}
 
 // Everything a call does, decided from the host-side job list alone (identical inputs give an identical plan): the class of
 // every job, each class's plan, and where its partials and descriptors lie.
@@ -614,15 +502,13 @@ CallPlan make_call_plan(const doda_wgrad_job *jobs, int n_jobs) {
     CallPlan cp;
     std::vector<int> of[J_WIDE + 1];
     for (int k = 0; k < n_jobs; ++k) {
-        cp.cls.push_back(classify(jobs[k]));
+        cp.cls.push_back(classify(jobs[k], doda_wgrad::switches()));
         of[cp.cls[k]].push_back(k);
     }
-    std::vector<int> rpc;
-    for (int k : of[J_WIDE]) rpc.push_back(doda_dense::rows_per_chunk(jobs[k]));
     cp.dense = doda_dense::plan(jobs, of[J_DENSE]);
     cp.pairs = doda_pairs::plan(jobs, of[J_PAIRS]);
     cp.tile = doda_wdma::plan(jobs, of[J_TILE]);
-    cp.wide = doda_wwide::plan(jobs, of[J_WIDE], rpc);
+    cp.wide = doda_wwide::plan(jobs, of[J_WIDE]);
     cp.pairs_part = cp.dense.partial_bytes;
     cp.tile_part = cp.pairs_part + cp.pairs.partial_bytes;
     cp.wide_part = cp.tile_part + cp.tile.partial_bytes;
@@ -635,6 +521,11 @@ CallPlan make_call_plan(const doda_wgrad_job *jobs, int n_jobs) {
     return cp;
 }
 }  // namespace
+
+WgradSwitches &doda_wgrad::switches() {
+    static WgradSwitches sw = wgrad_switches_from_env();
+    return sw;
+}
 
 extern "C" size_t doda_spconv_wgrad_multi_workspace_bytes(const doda_wgrad_job *jobs_h, int32_t n_jobs) {
     if (!jobs_h || n_jobs <= 0) return 0;
@@ -658,7 +549,7 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     // Every check comes before the first enqueue: a call that returns an error has left the stream and the caller's
     // gradients untouched.
     CallPlan cp = make_call_plan(jobs_h, n_jobs);
-    if (!cp.dense.valid) return DODA_ERR_INVALID;
+    if (cp.dense.status != DODA_OK) return cp.dense.status;
     if (ws_bytes < cp.part_bytes || desc_bytes < cp.desc_bytes) return DODA_ERR_WORKSPACE;
     char *part = (char *)ws;
     int r_blocks = 0;
@@ -701,6 +592,7 @@ extern "C" int doda_spconv_wgrad_multi(const doda_wgrad_job *jobs_h, int32_t n_j
     if (st == DODA_OK && cp.wide.n > 0) st = doda_wwide::launch(cp.wide, desc + cp.ww_off, s);
     if (st != DODA_OK) return st;
     if (cp.n_reduce > 0) {
+        doda_wgrad::trace("wgrad_reduce_multi", r_blocks, 256, cp.n_reduce);
         hipLaunchKernelGGL(wgrad_reduce_multi, dim3(r_blocks), dim3(256), 0, s, (const RJob *)(desc + cp.rj_off), cp.n_reduce);
         st = doda_check_launch();
         if (st != DODA_OK) return st;

@@ -25,12 +25,9 @@
 
 namespace {
 
-constexpr int SEG_TILE = 256;              // rows per tile of the export's segment prefix (rulebook.hip PAIR_TILE)
-constexpr int RANGE_TILES = 8;             // a block's row range: 2048 rows of the lists' `in` side
-constexpr int RANGE_ROWS = SEG_TILE * RANGE_TILES;
+constexpr int RANGE_TILES = WP_RANGE_TILES, RANGE_ROWS = WP_RANGE_ROWS;   // a block's row range (wgrad_plan.hpp pairs_geo)
 constexpr unsigned OOB = 0x80000000u;      // absent pair: beyond any buffer (operands are < 1 GB)
 constexpr unsigned CH_OOB = 0x40000000u;   // channel block past the channel count (OOB + CH_OOB does not wrap)
-constexpr int MAX_K = 28;
 
 // One layer inside a kernel-variant group.  Work item = (row range of the lists' `in` side, group of 4
 // offsets, channel tile); the block's four waves take one offset each and walk that offset's pairs
@@ -224,55 +221,17 @@ __global__ __launch_bounds__(256) void wgrad_pairs_kernel(const PJob *__restrict
         }
 }
 
-struct Geo {
-    int ta, tb, n_tag, n_tbg, n_og, n_range;
-    bool direct;   // one range and no accumulation: the waves write dw themselves
-};
-
-Geo make_geo(const doda_wgrad_job &j) {
-    Geo g;
-    const int na = j.ca / 16, nb = j.cb / 16;
-    g.ta = na >= 2 ? 2 : 1;
-    g.tb = nb >= 2 ? 2 : 1;
-    g.n_tag = div_up(na, g.ta);
-    g.n_tbg = div_up(nb, g.tb);
-    g.n_og = div_up(j.K, 4);
-    // rows of the lists' `in` side: the segment prefix covers pair_seg_nt tiles; identity lists: pair_ld pairs
-    const long long rows = j.pair_seg ? (long long)j.pair_seg_nt * SEG_TILE : (long long)j.pair_ld;
-    g.n_range = div_up(rows > 0 ? rows : 1, RANGE_ROWS);
-    g.direct = g.n_range == 1 && !(j.flags & DODA_WGRAD_ACCUMULATE);
-    return g;
-}
-
 template <int TA, int TB>
 void launch_variant(int blocks, const PJob *jobs_dev, const Ends &ends, hipStream_t s) {
+    char name[32];
+    snprintf(name, sizeof name, "wgrad_pairs_kernel<%d, %d>", TA, TB);
+    doda_wgrad::trace(name, blocks, 256, ends.n);
     hipLaunchKernelGGL((wgrad_pairs_kernel<TA, TB>), dim3(blocks), dim3(256), 0, s, jobs_dev, ends);
 }
 
 }  // namespace
 
 namespace doda_pairs {
-
-bool eligible(const doda_wgrad_job &j) {
-    if (j.elem_bytes != 2 || j.ca <= 0 || j.cb <= 0 || (j.ca % 16) || (j.cb % 16) || j.K <= 0 || j.n_rows <= 0)
-        return false;
-    if (!j.a || !j.b || !j.dw || j.K > MAX_K) return false;
-    if (!j.pair_in || !j.pair_out || j.pair_ld <= 0 || j.n_a <= 0) return false;
-    // real lists come with their counts and segment prefix; the identity lists of a 1x1 conv with neither
-    if (j.pair_num ? (!j.pair_seg || j.pair_seg_nt <= 0) : (j.pair_seg != nullptr || j.K != 1)) return false;
-    if ((unsigned long long)j.n_a * j.ca * 2ull >= 0x3fffffffull) return false;
-    if ((unsigned long long)j.n_rows * j.cb * 2ull >= 0x3fffffffull) return false;
-    if (((uintptr_t)j.a % 16) || ((uintptr_t)j.b % 16) || ((uintptr_t)j.dw % 16)) return false;
-    const Geo g = make_geo(j);
-    if ((long long)g.n_range * g.n_og * g.n_tag * g.n_tbg > 0x3fffffff) return false;
-    return true;
-}
-
-static size_t partial_bytes(const doda_wgrad_job &j) {
-    const Geo g = make_geo(j);
-    if (g.direct) return 0;
-    return align_up((size_t)g.n_range * j.K * j.ca * j.cb * 4, 256);
-}
 
 size_t desc_bytes_per_job() { return sizeof(PJob) + sizeof(doda_wgrad::RJob); }
 
@@ -283,8 +242,8 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
     const int n = (int)idx.size();
     for (int k = 0; k < n; ++k) {
         p.part_off.push_back(p.partial_bytes);
-        p.partial_bytes += partial_bytes(jobs[idx[k]]);
-        p.n_reduce += make_geo(jobs[idx[k]]).direct ? 0 : 1;
+        p.partial_bytes += pairs_geo(jobs[idx[k]]).partial_bytes;
+        p.n_reduce += pairs_geo(jobs[idx[k]]).direct ? 0 : 1;
     }
     for (int ta = 1; ta <= 2; ++ta)
         for (int tb = 1; tb <= 2; ++tb) {
@@ -294,10 +253,10 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
                 grp = Plan::Group{ta, tb, (int)p.order.size(), 0, 0};
             };
             for (int k = 0; k < n; ++k) {
-                const Geo g = make_geo(jobs[idx[k]]);
+                const PairsGeo g = pairs_geo(jobs[idx[k]]);
                 if (g.ta != ta || g.tb != tb) continue;
                 if (grp.count == MAX_GROUP) flush();
-                grp.blocks += g.n_range * g.n_og * g.n_tag * g.n_tbg;
+                grp.blocks += (int)g.blocks;
                 p.order.push_back(k);
                 p.blk_end.push_back(grp.blocks);
                 ++grp.count;
@@ -314,7 +273,7 @@ void write_desc(const Plan &p, const doda_wgrad_job *jobs, char *part, void *des
     for (size_t q = 0; q < p.order.size(); ++q) {
         const int k = p.order[q];
         const doda_wgrad_job &j = jobs[p.idx[k]];
-        const Geo g = make_geo(j);
+        const PairsGeo g = pairs_geo(j);
         PJob d;
         memset(&d, 0, sizeof(d));
         d.a = j.a; d.b = j.b;
@@ -330,7 +289,7 @@ void write_desc(const Plan &p, const doda_wgrad_job *jobs, char *part, void *des
     }
     for (size_t k = 0; k < p.idx.size(); ++k) {
         const doda_wgrad_job &j = jobs[p.idx[k]];
-        const Geo g = make_geo(j);
+        const PairsGeo g = pairs_geo(j);
         if (!g.direct) doda_wgrad::push_reduce(reduce, reduce_blocks, part + p.part_off[k], j, g.n_range);
     }
 }

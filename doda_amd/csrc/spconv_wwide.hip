@@ -22,7 +22,6 @@
 // of its dW.
 #include "wgrad_common.hpp"
 #include "tilebook.hpp"
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -31,8 +30,6 @@ namespace {
 
 constexpr int WW_WAVES = 16;
 constexpr int WW_MO = (TB_K + WW_WAVES - 1) / WW_WAVES;       // offsets per wave (2)
-constexpr int WW_MAX_BLOCKS = 9;                               // TA * TB
-constexpr int WW_MAX_TA = 3, WW_MAX_TB = 7;
 constexpr int WW_LIST_BYTES = TB_UMAX * 4;
 // dy slice (TB_T rows of 32 TB bytes) and behind it the x rows (slot 0 = the zero row, then up to TB_LMAX rows of 32 TA
 // bytes): at most 3 x 3 blocks -> 24 + 96 KB
@@ -198,9 +195,7 @@ __device__ void ww_body(const WwJob &d, int local, unsigned char *smem) {
     }
 }
 
-// the slice shapes the launch knows: (TA, TB) with TA * TB <= 9
-#define WW_SHAPES(X) X(3, 3) X(2, 4) X(2, 3) X(1, 5) X(1, 6) X(1, 7) X(1, 4) X(1, 3)
-
+// one case per slice shape the plan can name (wgrad_plan.hpp WW_SHAPES)
 __global__ __launch_bounds__(1024) void wgrad_wide(const WwJob *__restrict__ jobs, int n_jobs) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[WW_SMEM];
     const int j = find_job<WwJob, &WwJob::wg_end>(jobs, n_jobs, (int)blockIdx.x);
@@ -225,37 +220,13 @@ __global__ __launch_bounds__(256) void wgrad_wide_reduce(const WwJob *__restrict
     });
 }
 
-// slice shape of a job: TB = the widest output-channel slice of at most 7 blocks dividing cb / 16, TA = the widest input
-// slice of at most 3 blocks dividing ca / 16 with TA * TB <= 9
-bool ww_shape(int ca, int cb, int *ta, int *tb) {
-    const int A = ca / 16, B = cb / 16;
-    int b = B;
-    while (b > WW_MAX_TB || B % b) --b;
-    int a = WW_MAX_TA;
-    while (a > 1 && (A % a || a * b > WW_MAX_BLOCKS)) --a;
-    bool known = false;
-#define WW_KNOWN(X, Y) known |= (a == X && b == Y);
-    WW_SHAPES(WW_KNOWN)
-#undef WW_KNOWN
-    *ta = a; *tb = b;
-    return known;
-}
-
 }  // namespace
 
 namespace doda_wwide {
 
-bool eligible(const doda_wgrad_job &j) {
-    int ta, tb;
-    return j.tilebook && j.tbl && j.elem_bytes == 2 && j.K == TB_K && j.n_rows > 0 && j.a && j.b && j.dw &&
-           j.ca % 16 == 0 && j.cb % 16 == 0 && j.ca >= 48 && j.cb >= 48 && j.ca <= 224 && j.cb <= 224 &&
-           j.n_a == j.n_rows && j.ld >= j.n_rows && !(((uintptr_t)j.a | (uintptr_t)j.b | (uintptr_t)j.tilebook | (uintptr_t)j.dw) & 15) &&
-           ww_shape(j.ca, j.cb, &ta, &tb);
-}
-
 // The launch's plan: jobs longest first (most rows), one workgroup per (channel slice, row chunk of the gather-table
-// kernel's plan: rows_per_chunk[k] for job idx[k]).  Identical inputs give an identical plan.
-Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx, const std::vector<int> &rows_per_chunk) {
+// kernel's plan, plan_dense).  Identical inputs give an identical plan.
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx) {
     Plan pl;
     pl.n = (int)idx.size();
     std::vector<int> order;
@@ -268,15 +239,13 @@ Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx, const std::ve
         d.x = (const unsigned short *)j.a; d.dy = (const unsigned short *)j.b; d.tbl = j.tbl; d.tb = j.tilebook;
         d.dw = j.dw;
         d.ca = j.ca; d.cb = j.cb; d.ld = j.ld; d.n_rows = j.n_rows; d.nt = (j.n_rows + TB_T - 1) / TB_T;
-        ww_shape(j.ca, j.cb, &d.ta, &d.tb_);
+        const WideGeo g = wwide_geo(j, doda_wgrad::switches());
+        d.ta = g.ta; d.tb_ = g.tb; d.rpc = g.rpc; d.P = g.P;
         d.n_sb = j.cb / (16 * d.tb_);
-        d.rpc = rows_per_chunk[kk];
-        d.P = (j.n_rows + d.rpc - 1) / d.rpc;
         d.accumulate = (j.flags & DODA_WGRAD_ACCUMULATE) ? 1 : 0;
-        const int slices = (j.ca / (16 * d.ta)) * d.n_sb;
         d.part = (float *)(uintptr_t)pl.partial_bytes;      // offset until write_desc()
-        pl.partial_bytes += align_up((size_t)slices * d.P * TB_K * 256 * d.ta * d.tb_ * 4, 256);
-        pl.wgs += slices * d.P;
+        pl.partial_bytes += g.partial_bytes;
+        pl.wgs += g.blocks;
         d.wg_end = pl.wgs;
         pl.red_blocks += doda_wgrad::reduce_blocks((long long)TB_K * j.ca * j.cb / 4, d.P);
         d.red_end = pl.red_blocks;
@@ -298,7 +267,9 @@ void write_desc(const Plan &p, char *part, void *desc) {
 }
 
 int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
+    doda_wgrad::trace("wgrad_wide", p.wgs, 1024, p.n);
     hipLaunchKernelGGL(wgrad_wide, dim3(p.wgs), dim3(1024), 0, s, (const WwJob *)desc_dev, p.n);
+    doda_wgrad::trace("wgrad_wide_reduce", p.red_blocks, 256, p.n);
     hipLaunchKernelGGL(wgrad_wide_reduce, dim3(p.red_blocks), dim3(256), 0, s, (const WwJob *)desc_dev, p.n);
     return doda_check_launch();
 }

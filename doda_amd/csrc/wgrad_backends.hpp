@@ -9,12 +9,20 @@
 //      descriptors and n_reduce entries of the shared reduction list.  Identical inputs give an identical plan.
 //   2. write_desc(plan, ..., part, ...): the host copy of the descriptors, given the address of the class's partials.
 //   3. launch(plan, ..., s): the class's kernels, given the device address of its descriptors.
-// eligible(job) says whether a class can take a job; classify() in spconv_wgrad.hip decides which one does.
+// Which class takes a job, and every geometry a plan is made of, is decided in wgrad_plan.hpp (pure host functions of the job
+// and the switches: classify, the classes' *_eligible predicates, plan_dense); nothing here or in the classes' files chooses.
 #pragma once
 #include "common.hpp"
+#include "wgrad_plan.hpp"
 #include <vector>
 
 namespace doda_wgrad {
+// the process-wide switches: the environment once, at the first weight-gradient or option call, then doda_set_option
+WgradSwitches &switches();
+// DODA_TRACE_WGRAD=1: one line per kernel launch of the call on stderr; `name` as a kernel trace shows it, namespaces stripped
+inline void trace(const char *name, unsigned grid, unsigned block, int jobs) {
+    if (switches().trace) fprintf(stderr, "wgrad route=%s grid=%u block=%u jobs=%d\n", name, grid, block, jobs);
+}
 // One fixed-order reduction dw[q] (+)= sum_r partial[r][q] over float quads (wgrad_common.hpp wgrad_fold); every class
 // whose partials lie chunk-major appends its reductions to the call's one list, summed by one wgrad_reduce_multi launch.
 struct RJob {
@@ -46,7 +54,6 @@ inline void push_reduce(std::vector<RJob> &list, int *blocks, const void *partia
 
 // Pair-list kernels: bf16, 16-channel multiples, pair lists given or identity, operands inside the 4 GB hardware range check
 namespace doda_pairs {
-bool eligible(const doda_wgrad_job &j);
 struct Plan {
     std::vector<int> idx;
     std::vector<size_t> part_off;      // per job: its partials inside the class's workspace (unused when it writes dw itself)
@@ -67,9 +74,8 @@ size_t desc_bytes_per_job();           // descriptor + reduction entry
 // rulebook (jobs sharing tilebook, table, row count and leading dimension) and 16 channel blocks.  Its descriptors travel
 // in the kernel arguments (no device descriptors): write_desc keeps them in the plan.
 namespace doda_wdma {
-bool enabled();
-void set_enabled(bool on);
-bool eligible(const doda_wgrad_job &j);
+inline bool enabled() { return doda_wgrad::switches().wdma; }
+inline void set_enabled(bool on) { doda_wgrad::switches().wdma = on; }
 struct Plan {
     struct Launch { int first_job, n_jobs, n_blocks; size_t part_off; };   // first_job: position in `order`
     std::vector<Launch> launches;
@@ -83,16 +89,14 @@ int launch(const Plan &p, const doda_wgrad_job *jobs, hipStream_t s);
 }  // namespace doda_wdma
 
 // LDS-staged wide tile kernel over a tilebook (spconv_wwide.hip): bf16 K = 27 layers of 48 .. 224 channels, every such job
-// of a call in one launch.  rows_per_chunk: the gather-table plan's row chunks of each job, whose sums the kernel reproduces
-// bit for bit.
+// of a call in one launch, over the row chunks of the gather-table plan (plan_dense), whose sums the kernel reproduces bit for bit.
 namespace doda_wwide {
-bool eligible(const doda_wgrad_job &j);
 struct Plan {
     std::vector<unsigned char> desc;   // the descriptors, their partials as offsets into the class's workspace
     int n = 0, wgs = 0, red_blocks = 0;
     size_t partial_bytes = 0, desc_bytes = 0;
 };
-Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx, const std::vector<int> &rows_per_chunk);
+Plan plan(const doda_wgrad_job *jobs, const std::vector<int> &idx);
 void write_desc(const Plan &p, char *part, void *desc);
 int launch(const Plan &p, const void *desc_dev, hipStream_t s);
 size_t desc_bytes_per_job();

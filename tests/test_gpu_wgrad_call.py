@@ -1,4 +1,4 @@
-"""doda_spconv_wgrad_multi as ONE call (csrc/spconv_wgrad.hip make_call_plan): every kernel class — tile, wide, pair lists,
+"""doda_spconv_wgrad_multi as ONE call (csrc/spconv_wgrad.hip make_call_plan over csrc/wgrad_plan.hpp): every kernel class — tile, wide, pair lists,
 gather table — and every regime of the shared fixed-order reduction (csrc/wgrad_common.hpp wgrad_fold: 1, 2 .. 16 and more
 than 16 chunks, the scalar reduce of an element count that is no multiple of four) side by side, in overwrite and in
 accumulate mode, plus empty jobs; the workspace / descriptor contract of the call (an error return has enqueued nothing);

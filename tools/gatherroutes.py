@@ -15,6 +15,8 @@
       one call per kernel family at a small shape: the largest error against the fp64 reference, one JSON line per call.
   python tools/gatherroutes.py --instantiations doda_amd/csrc/_obj/spconv_gather.o .../spconv_tile.o .../spconv_wlds.o
       the conv_* kernel symbols of the gfx950 code objects: regenerates tests/data/gather_instantiations.json.
+  python tools/gatherroutes.py --instantiations --stem wgrad_multi_kernel doda_amd/csrc/_obj/spconv_wgrad.o
+      the same reader for the kernels whose name starts with another stem: regenerates tests/data/wgrad_instantiations.json.
   python tools/gatherroutes.py --fold TRACE.csv RESULTS.jsonl
       joins a rocprofv3 --kernel-trace CSV of such a run with its result lines: per call the normalised conv kernel with grid and
       workgroup size and those of the pack kernel, as JSON (the form of tests/data/gather_routes.json).
@@ -265,9 +267,10 @@ def families():
                               "err": float((y - ref).abs().max() / ref.abs().max())}), flush=True)
 
 
-def instantiations(objs):
-    """The conv_* kernel symbols of compiled objects (doda_amd/csrc/_obj/spconv_{gather,tile,wlds}.o), normalised and sorted:
-    the content of tests/data/gather_instantiations.json."""
+def instantiations(objs, stem="conv_"):
+    """The kernel symbols of compiled objects whose name starts with `stem`, normalised and sorted: conv_* of
+    doda_amd/csrc/_obj/spconv_{gather,tile,wlds}.o is the content of tests/data/gather_instantiations.json, wgrad_multi_kernel of
+    spconv_wgrad.o that of tests/data/wgrad_instantiations.json."""
     import glob
     import subprocess
     import tempfile
@@ -282,8 +285,8 @@ def instantiations(objs):
             for dev in glob.glob(os.path.join(tmp, "*gfx950*")):
                 out = subprocess.run([objdump, "-t", "-C", dev], capture_output=True, text=True, check=True).stdout
                 for l in out.splitlines():
-                    m = re.search(r"\sF \.text\s+\S+\s+(?:\.\w+ )?(.*conv_.*)$", l)
-                    if m:
+                    m = re.search(r"\sF \.text\s+\S+\s+(?:\.\w+ )?(.*)$", l)
+                    if m and normalise(m.group(1).strip()).startswith(stem):
                         names.add(normalise(m.group(1).strip()))
     return sorted(names)
 
@@ -332,6 +335,7 @@ if __name__ == "__main__":
     elif sys.argv[1] == "--families":
         families()
     elif sys.argv[1] == "--instantiations":
-        print(json.dumps(instantiations(sys.argv[2:]), indent=0))
+        stem, objs = (sys.argv[3], sys.argv[4:]) if sys.argv[2] == "--stem" else ("conv_", sys.argv[2:])
+        print(json.dumps(instantiations(objs, stem), indent=0))
     elif sys.argv[1] == "--fold":
         print(json.dumps(fold(sys.argv[2], sys.argv[3]), indent=0))

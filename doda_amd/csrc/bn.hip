@@ -48,6 +48,7 @@ __device__ __forceinline__ void st4(float *p, const f32x4 &v) { *reinterpret_cas
 struct F32 {
     typedef float elem;
     static constexpr int W = 1;   // 4-channel fragments per 16-byte access
+    static const char *name() { return "F32"; }   // (bn_trace)
     static __device__ __forceinline__ f32x4 load4(const elem *p) { return ld4(p); }
     static __device__ __forceinline__ void store4(elem *p, const f32x4 &v) { st4(p, v); }
     static __device__ __forceinline__ void loadw(const elem *p, f32x4 (&v)[1]) { v[0] = load4(p); }
@@ -66,6 +67,7 @@ struct BF16 {
         *reinterpret_cast<s16x4 *>(p) = o;
     }
     static constexpr int W = 2;   // two 4-channel fragments (8 channels) per 16-byte access
+    static const char *name() { return "BF16"; }
     typedef short s16x8_ __attribute__((ext_vector_type(8)));
     static __device__ __forceinline__ void loadw(const elem *p, f32x4 (&v)[2]) {
         const s16x8_ r = *reinterpret_cast<const s16x8_ *>(p);
@@ -428,6 +430,7 @@ int launch_apply(const void *x_, long long n_frag, int nf, const float *mean, co
     elem *y = (elem *)y_;
     bool fixed;
     const int grid = apply_grid(n_frag, nf, T::W, al16(x) && al16(y), TOT ? tot_grid_cap() : 4096, &fixed);
+    bn_trace(grid, BN_BLOCK, "bn_apply<%s, %s, %s>", T::name(), fixed ? "true" : "false", TOT ? "true" : "false");
     hipLaunchKernelGGL((fixed ? bn_apply<T, true, TOT> : bn_apply<T, false, TOT>), dim3(grid), dim3(BN_BLOCK), 0, s, x, n_frag, nf, mean,
                        invstd, gamma, beta, relu, y, tot);
     return doda_check_launch();
@@ -442,6 +445,7 @@ int launch_bwd_apply(const void *x_, const void *dy_, long long n_frag, int nf, 
     const bool aligned = al16(x) && al16(dy) && al16(dx) && (!add || (al16(add) && add_ld % (4 * T::W) == 0));
     bool fixed;
     const int grid = apply_grid(n_frag, nf, T::W, aligned, TOT ? tot_grid_cap() : 4096, &fixed);
+    bn_trace(grid, BN_BLOCK, "bn_bwd_apply<%s, %s, %s>", T::name(), fixed ? "true" : "false", TOT ? "true" : "false");
     hipLaunchKernelGGL((fixed ? bn_bwd_apply<T, true, TOT> : bn_bwd_apply<T, false, TOT>), dim3(grid), dim3(BN_BLOCK), 0, s, x, dy, n_frag,
                        nf, c, mean, invstd, gamma, beta, relu, coef, dx, add, add_ld, tot);
     return doda_check_launch();
@@ -871,6 +875,7 @@ int run_fwd(const void *x_, int m, int c, float eps, float momentum, const float
     const elem *x = (const elem *)x_;
     const Geo g = make_geo(c);
     if (training && m <= BN_SMALL_ROWS) {
+        bn_trace(c / 4, BN_BLOCK, "bn_small_fwd<%s>", T::name());
         hipLaunchKernelGGL((bn_small_fwd<T>), dim3(c / 4), dim3(BN_BLOCK), 0, s, x, m, c, eps, momentum,
                            gamma, beta, running_mean, running_var, nbt, relu, (elem *)y_, mean, invstd);
         return doda_check_launch();
@@ -879,6 +884,8 @@ int run_fwd(const void *x_, int m, int c, float eps, float momentum, const float
         const int nb = n_blocks_for(m, g);
         if (ws_bytes < (size_t)nb * 2 * c * 4) return DODA_ERR_WORKSPACE;
         float *partial = (float *)ws;
+        bn_trace(nb, BN_BLOCK, "bn_stats_partial<%s>", T::name());
+        bn_trace(c, 64, "bn_stats_final<%s>", T::name());
         hipLaunchKernelGGL((bn_stats_partial<T>), dim3(nb), dim3(BN_BLOCK), (size_t)g.rpb * 2 * c * 4, s,
                            x, m, c, g, partial);
         hipLaunchKernelGGL((bn_stats_final<T>), dim3(c), dim3(64), 0, s, x, partial, nb, m,
@@ -896,6 +903,7 @@ int run_bwd(const void *x_, const void *dy_, int m, int c, const float *mean, co
     const Geo g = make_geo(c);
     if (add_ld == c) add_ld = 0;   // dense
     if (m <= BN_SMALL_ROWS) {
+        bn_trace(c / 4, BN_BLOCK, "bn_small_bwd<%s>", T::name());
         hipLaunchKernelGGL((bn_small_bwd<T>), dim3(c / 4), dim3(BN_BLOCK), 0, s, x, dy, m, c, mean, invstd,
                            gamma, beta, relu, (elem *)dx_, dgamma, dbeta, (const elem *)add_, add_ld);
         return doda_check_launch();
@@ -904,6 +912,8 @@ int run_bwd(const void *x_, const void *dy_, int m, int c, const float *mean, co
     if (ws_bytes < (size_t)nb * 2 * c * 4 + (size_t)3 * c * 4) return DODA_ERR_WORKSPACE;
     float *partial = (float *)ws;
     float *coef = partial + (size_t)nb * 2 * c;
+    bn_trace(nb, BN_BLOCK, "bn_bwd_partial<%s>", T::name());
+    bn_trace(c, 64, "bn_bwd_final");
     hipLaunchKernelGGL((bn_bwd_partial<T>), dim3(nb), dim3(BN_BLOCK), (size_t)g.rpb * 2 * c * 4, s, x, dy,
                        m, c, g, mean, invstd, gamma, beta, relu, partial);
     hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(64), 0, s, partial, nb, m, c, invstd,
@@ -921,10 +931,12 @@ int run_fwd_stats(const void *x_, int m, int c, const float *stats, int rows, fl
     const Geo g = make_geo(c);
     const long long n_frag = (long long)m * g.nf;
     if (fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows
+        bn_trace(fused_grid(n_frag), BN_BLOCK, "bn_fused_fwd<%s>", T::name());
         hipLaunchKernelGGL((bn_fused_fwd<T>), dim3(fused_grid(n_frag)), dim3(BN_BLOCK), 0, s, (const elem *)x_, n_frag, g.nf, g.rpb,
                            stats, rows, m, eps, momentum, gamma, beta, mean, invstd, rm, rv, nbt, relu, (elem *)y_);
         return doda_check_launch();
     }
+    bn_trace(c / 4, BN_BLOCK, "bn_fwd_final_stats");
     hipLaunchKernelGGL(bn_fwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, eps, momentum, mean,
                        invstd, rm, rv, nbt);
     return launch_apply<T, false>(x_, n_frag, g.nf, mean, invstd, gamma, beta, relu, y_, TotArgs(), s);
@@ -939,11 +951,13 @@ int run_bwd_stats(const void *x_, const void *dy_, int m, int c, const float *st
     const long long n_frag = (long long)m * g.nf;
     if (add_ld == c || !add_) add_ld = 0;   // dense
     if (!add_ld && fused_ok(rows, c, m)) {      // final + apply in one launch: few partial rows (opt-in; dense `add` only)
+        bn_trace(fused_grid(n_frag), BN_BLOCK, "bn_fused_bwd<%s>", T::name());
         hipLaunchKernelGGL((bn_fused_bwd<T>), dim3(fused_grid(n_frag)), dim3(BN_BLOCK), 0, s, (const elem *)x_, (const elem *)dy_,
                            n_frag, g.nf, g.rpb, stats, rows, m, mean, invstd, gamma, beta, relu, dgamma, dbeta, (elem *)dx_,
                            (const elem *)add_);
         return doda_check_launch();
     }
+    bn_trace(c / 4, BN_BLOCK, "bn_bwd_final_stats");
     hipLaunchKernelGGL(bn_bwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, s, stats, rows, m, c, invstd, gamma, dgamma,
                        dbeta, coef);
     return launch_bwd_apply<T, false>(x_, dy_, n_frag, g.nf, c, mean, invstd, gamma, beta, relu, coef, dx_, add_, add_ld, TotArgs(), s);
@@ -1056,6 +1070,7 @@ extern "C" int doda_bn_fwd_final(const float *stats, int32_t stats_rows, int32_t
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, 2)) return DODA_ERR_UNSUPPORTED;
     if (any_null(stats, save_mean, save_invstd) || stats_rows <= 0 || (!running_mean != !running_var)) return DODA_ERR_INVALID;
+    bn_trace(c / 4, BN_BLOCK, "bn_fwd_final_stats");
     hipLaunchKernelGGL(bn_fwd_final_stats, dim3(c / 4), dim3(BN_BLOCK), 0, as_stream(stream), stats, stats_rows, m, c, eps,
                        momentum, save_mean, save_invstd, running_mean, running_var, (long long *)num_batches_tracked);
     return doda_check_launch();
@@ -1071,7 +1086,7 @@ extern "C" int doda_bn_relu_fwd_totals(const void *x, int32_t m, int32_t c, int3
     if (m == 0) return DODA_OK;
     if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
     if (any_null(x, y, totals, gamma, beta, save_mean, save_invstd) || (!running_mean != !running_var)) return DODA_ERR_INVALID;
-    if (totals_b && (c_a <= 0 || c_a >= c)) return DODA_ERR_INVALID;
+    if (totals_b && (c_a <= 0 || c_a >= c || c_a % 4)) return DODA_ERR_INVALID;   // (tot_sums indexes each producer's totals in groups of four channels)
     const TotArgs t = tot_fwd_args(totals, totals_b, totals_b ? c_a : c, m, eps, momentum, running_mean, running_var,
                                    (long long *)num_batches_tracked, save_mean, save_invstd);
     return BN_DISPATCH(elem_bytes, launch_apply<T, true>(x, (long long)m * (c / 4), c / 4, nullptr, nullptr, gamma, beta, relu, y, t,

@@ -4,6 +4,8 @@
 // same BatchNorm applied inside the consuming conv's gather give the same bits.  gfx950 only.
 #pragma once
 #include "common.hpp"
+#include <stdarg.h>
+#include <stdio.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -20,6 +22,19 @@ struct TotArgs {
     float *out_a = nullptr, *out_b = nullptr;     // forward: save_mean, save_invstd; backward: dgamma, dbeta
     int accum = 0;                                // backward: dgamma / dbeta are ADDED to (a second backward pass of one optimizer step)
 };
+
+// DODA_TRACE_BN=1 (read once): one stderr line per kernel launch of bn.hip and of the BatchNorm / statistics ops of layers.hip —
+// `bn route=<kernel> grid= block=`, the kernel's name as a kernel trace shows it, namespaces stripped (tools/bnnumerics.py)
+static inline void bn_trace(unsigned grid, unsigned block, const char *fmt, ...) {
+    static const bool on = getenv("DODA_TRACE_BN") && getenv("DODA_TRACE_BN")[0] == '1';
+    if (!on) return;
+    char name[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof(name), fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "bn route=%s grid=%u block=%u\n", name, grid, block);
+}
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ void tot_sums(const TotArgs &t, int c, int ch, double &s1, double &s2) {

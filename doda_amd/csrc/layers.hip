@@ -154,6 +154,7 @@ int launch_bn(const doda_cx_op &o, int esz, const PreArgs &p, hipStream_t s) {
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
     const int split = (o.kind == DODA_CX_BNBWD && o.c_split > 0 && o.c_split < c) ? o.c_split : c;
+    bn_trace((unsigned)grid, 256, "lay_bn<%d, %d>", esz, KIND);
     if (esz == 2)
         hipLaunchKernelGGL((lay_bn<2, KIND>), dim3((unsigned)grid), dim3(256), 0, s, o.x, (unsigned)o.x_ld, c, p, o.y, (unsigned)o.y_ld, o.y2,
                            (unsigned)o.y2_ld, split);
@@ -202,6 +203,7 @@ int run_stats(const doda_cx_op &o, int esz, hipStream_t s) {
     long long grid = ((long long)o.rows + (long long)rpb * 8 - 1) / ((long long)rpb * 8);   // ~8 rows per thread
     if (grid > 1024) grid = 1024;
     if (grid < 1) grid = 1;
+    bn_trace((unsigned)grid, 256, "lay_stats<%d>", esz);
     if (esz == 2) hipLaunchKernelGGL((lay_stats<2>), dim3((unsigned)grid), dim3(256), 0, s, o.x, (unsigned)o.x_ld, o.rows, o.c_in, (double *)o.stats);
     else hipLaunchKernelGGL((lay_stats<4>), dim3((unsigned)grid), dim3(256), 0, s, o.x, (unsigned)o.x_ld, o.rows, o.c_in, (double *)o.stats);
     return doda_check_launch();

@@ -354,7 +354,9 @@ def test_bn_relu_matches_torch(native_lib, c, relu, dtype):
     from doda_amd import nn as dnn
     torch.manual_seed(c)
     d = dev()
-    for m in (5000 + c, 40000 + c):   # single-launch small-M kernels and the multi-block path
+    # up to BN_SMALL_ROWS = 4096 rows: the single-launch bn_small_* kernels; above: partial sums, combine and apply sweep, with two
+    # grid sizes of the partial-sum kernels (tests/test_gpu_bn_numerics.py holds every route to derived bounds)
+    for m in (2000 + c, 5000 + c, 40000 + c):
         _check_bn(dnn, m, c, relu, dtype, d)
 
 

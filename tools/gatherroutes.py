@@ -17,6 +17,8 @@
       the conv_* kernel symbols of the gfx950 code objects: regenerates tests/data/gather_instantiations.json.
   python tools/gatherroutes.py --instantiations --stem wgrad_multi_kernel doda_amd/csrc/_obj/spconv_wgrad.o
       the same reader for the kernels whose name starts with another stem: regenerates tests/data/wgrad_instantiations.json.
+  python tools/gatherroutes.py --instantiations --stem bn_,lay_ doda_amd/csrc/_obj/bn.o doda_amd/csrc/_obj/layers.o
+      several stems, separated by commas: the BatchNorm kernels, tests/data/bn_instantiations.json (tools/bnnumerics.py).
   python tools/gatherroutes.py --fold TRACE.csv RESULTS.jsonl
       joins a rocprofv3 --kernel-trace CSV of such a run with its result lines: per call the normalised conv kernel with grid and
       workgroup size and those of the pack kernel, as JSON (the form of tests/data/gather_routes.json).
@@ -268,9 +270,10 @@ def families():
 
 
 def instantiations(objs, stem="conv_"):
-    """The kernel symbols of compiled objects whose name starts with `stem`, normalised and sorted: conv_* of
-    doda_amd/csrc/_obj/spconv_{gather,tile,wlds}.o is the content of tests/data/gather_instantiations.json, wgrad_multi_kernel of
-    spconv_wgrad.o that of tests/data/wgrad_instantiations.json."""
+    """The kernel symbols of compiled objects whose name starts with `stem` (a string or a tuple of them), normalised and sorted:
+    conv_* of doda_amd/csrc/_obj/spconv_{gather,tile,wlds}.o is the content of tests/data/gather_instantiations.json,
+    wgrad_multi_kernel of spconv_wgrad.o that of tests/data/wgrad_instantiations.json, bn_* and lay_* of bn.o and layers.o that of
+    tests/data/bn_instantiations.json."""
     import glob
     import subprocess
     import tempfile
@@ -335,7 +338,7 @@ if __name__ == "__main__":
     elif sys.argv[1] == "--families":
         families()
     elif sys.argv[1] == "--instantiations":
-        stem, objs = (sys.argv[3], sys.argv[4:]) if sys.argv[2] == "--stem" else ("conv_", sys.argv[2:])
+        stem, objs = (tuple(sys.argv[3].split(",")), sys.argv[4:]) if sys.argv[2] == "--stem" else ("conv_", sys.argv[2:])
         print(json.dumps(instantiations(objs, stem), indent=0))
     elif sys.argv[1] == "--fold":
         print(json.dumps(fold(sys.argv[2], sys.argv[3]), indent=0))

@@ -964,15 +964,7 @@ int run_bwd_stats(const void *x_, const void *dy_, int m, int c, const float *st
 }
 
 // ---- argument checks of the entry points ---------------------------------------------------------------------------
-bool bn_args_bad(int m, int c, int elem_bytes) {
-    return m <= 0 || c <= 0 || (c % 4) != 0 || c > 1024 || (elem_bytes != 2 && elem_bytes != 4);
-}
-template <class... P>
-bool any_null(const P *...p) { return (... || !p); }
-// the second-gradient operand: rows at least c elements apart, a multiple of one fragment, fragment-aligned
-bool add_bad(const void *add, int add_ld, int c, int elem_bytes) {
-    return add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes));
-}
+// (bn_args_bad, any_null, add_bad and the two totals entry points' checks: bn_totals.hpp, shared with the op list's host plan)
 // TotArgs of the forward / backward totals sweeps (backward: no running statistics; `accum` is the op list's alone, layers.hip)
 TotArgs tot_fwd_args(const double *ta, const double *tb, int ca, int m, float eps, float momentum, float *rm, float *rv,
                      long long *nbt, float *save_mean, float *save_invstd) {
@@ -1083,10 +1075,8 @@ extern "C" int doda_bn_relu_fwd_totals(const void *x, int32_t m, int32_t c, int3
                                        const float *beta, float *running_mean, float *running_var,
                                        int64_t *num_batches_tracked, int32_t relu, void *y, float *save_mean,
                                        float *save_invstd, doda_stream_t stream) {
-    if (m == 0) return DODA_OK;
-    if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
-    if (any_null(x, y, totals, gamma, beta, save_mean, save_invstd) || (!running_mean != !running_var)) return DODA_ERR_INVALID;
-    if (totals_b && (c_a <= 0 || c_a >= c || c_a % 4)) return DODA_ERR_INVALID;   // (tot_sums indexes each producer's totals in groups of four channels)
+    const int st = bn_fwd_totals_status(x, m, c, elem_bytes, totals, totals_b, c_a, gamma, beta, running_mean, running_var, y, save_mean, save_invstd);
+    if (st != DODA_OK || m == 0) return st;
     const TotArgs t = tot_fwd_args(totals, totals_b, totals_b ? c_a : c, m, eps, momentum, running_mean, running_var,
                                    (long long *)num_batches_tracked, save_mean, save_invstd);
     return BN_DISPATCH(elem_bytes, launch_apply<T, true>(x, (long long)m * (c / 4), c / 4, nullptr, nullptr, gamma, beta, relu, y, t,
@@ -1098,10 +1088,8 @@ extern "C" int doda_bn_relu_bwd_totals(const void *x, const void *dy, int32_t m,
                                        const double *totals, const float *save_mean, const float *save_invstd,
                                        const float *gamma, const float *beta, int32_t relu, const void *add, int32_t add_ld,
                                        void *dx, float *dgamma, float *dbeta, doda_stream_t stream) {
-    if (add && add_bad(add, add_ld, c, elem_bytes)) return DODA_ERR_INVALID;
-    if (m == 0) return DODA_OK;
-    if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
-    if (any_null(x, dy, dx, totals, gamma, beta, save_mean, save_invstd, dgamma, dbeta)) return DODA_ERR_INVALID;
+    const int st = bn_bwd_totals_status(x, dy, m, c, elem_bytes, totals, save_mean, save_invstd, gamma, beta, add, add_ld, dx, dgamma, dbeta);
+    if (st != DODA_OK || m == 0) return st;
     if (add_ld == c || !add) add_ld = 0;   // dense
     return BN_DISPATCH(elem_bytes, launch_bwd_apply<T, true>(x, dy, (long long)m * (c / 4), c / 4, c, save_mean, save_invstd, gamma, beta,
                                                              relu, nullptr, dx, add, add_ld, tot_bwd_args(totals, c, m, dgamma, dbeta),

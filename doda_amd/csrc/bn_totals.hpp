@@ -3,11 +3,19 @@
 // every conv sits behind BatchNorm1d -> ReLU).  One place for the arithmetic, so a BatchNorm applied by its own sweep and the
 // same BatchNorm applied inside the consuming conv's gather give the same bits.  gfx950 only.
 #pragma once
+// (the part above the kernels' arithmetic is plain C++ — constants, TotArgs, the trace line and the entry points' argument checks —
+// and is read by the host plan of the op list as well: layers_plan.hpp, built with g++)
+#if defined(__HIPCC__)
 #include "common.hpp"
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#else
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include "../../include/doda_hip.h"
+#endif
 #include <stdarg.h>
 #include <stdio.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BN_TOT_MAX_C = 256;
 constexpr int BN_TOT_SLOTS = 8;      // = DODA_STATS_SLOTS (spconv_common.hpp)
@@ -34,6 +42,37 @@ static inline void bn_trace(unsigned grid, unsigned block, const char *fmt, ...)
     vsnprintf(name, sizeof(name), fmt, ap);
     va_end(ap);
     fprintf(stderr, "bn route=%s grid=%u block=%u\n", name, grid, block);
+}
+
+// ---- argument checks of the entry points (bn.hip), pure: plan_layers (layers_plan.hpp) asks them before anything is launched ----
+inline bool bn_args_bad(int m, int c, int elem_bytes) {
+    return m <= 0 || c <= 0 || (c % 4) != 0 || c > 1024 || (elem_bytes != 2 && elem_bytes != 4);
+}
+template <class... P>
+inline bool any_null(const P *...p) { return (... || !p); }
+// the second-gradient operand: rows at least c elements apart, a multiple of one fragment, fragment-aligned
+inline bool add_bad(const void *add, int add_ld, int c, int elem_bytes) {
+    return add_ld < c || add_ld % 4 || ((uintptr_t)add % (4 * (size_t)elem_bytes));
+}
+// the status doda_bn_relu_fwd_totals / doda_bn_relu_bwd_totals return without a launch (DODA_OK: m == 0, or the sweep is launched)
+inline int bn_fwd_totals_status(const void *x, int m, int c, int elem_bytes, const double *totals, const double *totals_b, int c_a,
+                                const float *gamma, const float *beta, const float *running_mean, const float *running_var,
+                                const void *y, const float *save_mean, const float *save_invstd) {
+    if (m == 0) return DODA_OK;
+    if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
+    if (any_null(x, y, totals, gamma, beta, save_mean, save_invstd) || (!running_mean != !running_var)) return DODA_ERR_INVALID;
+    if (totals_b && (c_a <= 0 || c_a >= c || c_a % 4)) return DODA_ERR_INVALID;   // (tot_sums indexes each producer's totals in groups of four channels)
+    return DODA_OK;
+}
+// (the two entry points over a data-grad epilogue's statistics test `add` before m == 0)
+inline int bn_bwd_totals_status(const void *x, const void *dy, int m, int c, int elem_bytes, const double *totals,
+                                const float *save_mean, const float *save_invstd, const float *gamma, const float *beta,
+                                const void *add, int add_ld, const void *dx, const float *dgamma, const float *dbeta) {
+    if (add && add_bad(add, add_ld, c, elem_bytes)) return DODA_ERR_INVALID;
+    if (m == 0) return DODA_OK;
+    if (bn_args_bad(m, c, elem_bytes) || c > BN_TOT_MAX_C) return DODA_ERR_UNSUPPORTED;
+    if (any_null(x, dy, dx, totals, gamma, beta, save_mean, save_invstd, dgamma, dbeta)) return DODA_ERR_INVALID;
+    return DODA_OK;
 }
 
 #if defined(__HIPCC__)

@@ -1,5 +1,5 @@
 // Route plan of doda_spconv_gather_ex: which kernel instantiation a call reaches, with which grid, decided in ONE pure host
-// function.  run_gather (spconv_gather.hip) validates, plans, packs and launches what the route names; the launchers of the
+// function.  doda_spconv_gather_ex (spconv_gather.hip) describes, plans, packs and launches what the route names; the launchers of the
 // kernel families (spconv_gather.hip, spconv_tile.hip, spconv_wlds.hip) hold no decision of their own.  Plain C++17, no HIP
 // header: tests/host/gather_plan_main.cpp compiles it with g++ and tests/test_gather_plan_host.py sweeps it.
 #pragma once
@@ -31,6 +31,77 @@ struct GatherCall {
     bool tilebook;
     int tilebook_rows;                 // with `tilebook`: the rows it was built for
 };
+
+constexpr int GP_MAX_K = 27;           // spconv_gather.hip MAX_K: most kernel offsets of a table
+constexpr int GP_MAX_CHANNELS = 4096;
+
+// The call description of doda_spconv_gather_ex as a pure function of its arguments: every check of the entry point, in its
+// order and with its statuses, and the normalisations of the row strides (a stride equal to the channel count is dense: 0;
+// a broadcast residual has no stride).  Pointers are looked at for null-ness and their address mod 16 only; `epi` and its
+// prologue are read as plain structs.  status != DODA_OK: the call returns it; status == DODA_OK with call.n_out == 0: the
+// call has nothing to do; otherwise `call` is what plan_gather decides on.  (doda_layers_run asks the same question for a
+// whole op list before its first launch: layers_plan.hpp.)
+struct GatherDescription {
+    int status;
+    GatherCall call;
+};
+inline GatherDescription describe_gather(const void *x, int32_t n_in, int32_t kc, int32_t elem_bytes, const float *w, int32_t nc,
+                                         const int32_t *tbl, int32_t ld, int32_t K, int32_t n_out, const void *y, int32_t y_is_f32,
+                                         int32_t w_layout, const void *ws, size_t ws_bytes, const doda_conv_epilogue *epi) {
+    GatherDescription d{};
+    GatherCall &c = d.call;
+    const auto al = [](const void *p) { return (int)((uintptr_t)p & 15); };
+    d.status = DODA_ERR_INVALID;
+    if (elem_bytes != 2 && elem_bytes != 4) return d;
+    if (kc <= 0 || nc <= 0 || K <= 0 || n_out < 0 || ld < n_out || (w_layout & 3) > 2 || (w_layout & ~0x103)) return d;
+    if (n_out == 0) { d.status = DODA_OK; return d; }
+    if (!x || !w || !tbl || !y) return d;
+    if (K > GP_MAX_K || nc > GP_MAX_CHANNELS || kc > GP_MAX_CHANNELS) { d.status = DODA_ERR_UNSUPPORTED; return d; }
+    if (epi) {
+        const bool res = epi->residual != nullptr;
+        c.res_bcast = res && epi->residual_bcast;
+        bool bn_x = false;
+        if (epi->stats) {
+            if (!epi->stats_rows_h) return d;
+            c.stats = true;
+            if (epi->bn_x) {
+                if (!epi->bn_mean || !epi->bn_invstd || !epi->bn_gamma || !epi->bn_beta) return d;
+                bn_x = true;
+            }
+        }
+        if (epi->x_ld < 0 || epi->y_ld < 0 || epi->residual_ld < 0 || epi->bn_x_ld < 0) return d;
+        c.x_ld = (unsigned)epi->x_ld; c.y_ld = (unsigned)epi->y_ld;
+        c.res_ld = res ? (unsigned)epi->residual_ld : 0u; c.bnx_ld = bn_x ? (unsigned)epi->bn_x_ld : 0u;
+        if ((c.x_ld && c.x_ld < (unsigned)kc) || (c.y_ld && c.y_ld < (unsigned)nc) || (c.res_ld && c.res_ld < (unsigned)nc) ||
+            (c.bnx_ld && c.bnx_ld < (unsigned)nc))
+            return d;
+        if (c.x_ld == (unsigned)kc) c.x_ld = 0;      // dense
+        if (c.y_ld == (unsigned)nc) c.y_ld = 0;
+        if (c.res_ld == (unsigned)nc) c.res_ld = 0;
+        if (c.bnx_ld == (unsigned)nc) c.bnx_ld = 0;
+        if (c.res_bcast) c.res_ld = 0;
+        if (const doda_conv_prologue *q = epi->prologue) {
+            if (q->kind < 1 || q->kind > 3 || q->rows != n_in || q->side_ld < kc || (q->kind >= 2 && q->aux_ld < kc) ||
+                (q->kind >= 3 && q->add_ld < kc) || (q->kind >= 2 && (!q->dgamma || !q->dbeta || !q->totals)) ||
+                (q->kind == 1 && q->totals && (!q->mean || !q->invstd || (!q->running_mean != !q->running_var))) ||
+                (q->kind == 1 && q->totals_b && (q->c_a <= 0 || q->c_a >= kc || q->c_a % 4 || !q->totals)))
+                return d;
+            c.pre_kind = q->kind; c.pre_rows = q->rows;
+            c.side_ld = (unsigned)q->side_ld; c.aux_ld = (unsigned)q->aux_ld; c.add_ld = (unsigned)q->add_ld;
+            c.side = q->side && al(q->side) == 0; c.aux = q->aux && al(q->aux) == 0; c.add = q->add && al(q->add) == 0;
+            c.saved = q->mean && q->invstd; c.totals = q->totals != nullptr;
+            c.running = q->kind == 1 && q->running_mean && q->running_var;   // (a backward prologue carries no running statistics)
+            c.affine = q->gamma && q->beta;
+        }
+        c.tilebook = epi->tilebook != nullptr; c.tilebook_rows = epi->tilebook_rows;
+    }
+    c.K = K; c.kc = kc; c.nc = nc; c.n_out = n_out; c.ld = ld; c.esz = elem_bytes; c.n_in = n_in;
+    c.out32 = elem_bytes == 2 && y_is_f32 != 0;
+    c.layout = w_layout & 3; c.packed = (w_layout & 0x100) != 0; c.ws_bytes = ws ? ws_bytes : 0;
+    c.x_al = al(x); c.y_al = al(y);
+    d.status = DODA_OK;
+    return d;
+}
 
 // Every A/B switch and environment-derived threshold of the selection; one process-wide instance (spconv_gather.hip).
 struct GatherSwitches {

@@ -33,7 +33,7 @@ __device__ __forceinline__ void mma_bf16_k32(f32x4 &acc, const u32x4 &w, const u
 // (4 channels of the lane group) x (head, tail) — A = [w_hi | w_lo] against B = [x_hi | x_hi], then against [x_lo | x_lo]:
 // all four partial products, fp32 accumulate.  The gathered bytes do not change (fp32 rows, fp32 fragment buffer).  Error of a
 // product <= ~2^-16 relative (north_star: 1e-4 on fp32 features).  OPT-IN per launch (DODA_F32_SPLIT_ROWS /
-// DODA_F32_WGRAD_SPLIT_ROWS, see run_gather): measured -6 % on the fp32 step, but the U-Net's gradients move from ~1e-3 to
+// DODA_F32_WGRAD_SPLIT_ROWS, see plan_gather): measured -6 % on the fp32 step, but the U-Net's gradients move from ~1e-3 to
 // ~7e-3 (elementwise, relative) away from the fp64 golden, and fp32 is the parity precision here.  DODA_F32_EXACT_MFMA=1 at
 // build time removes the split instantiations altogether.
 #ifndef DODA_F32_EXACT_MFMA
@@ -100,7 +100,7 @@ struct EpiArgs {   // plain data, shared across translation units
     const float *bn_mean, *bn_invstd, *bn_gamma, *bn_beta;   // [nc] each
     int bn_relu;
     int res_bcast;           // ABI 6: `res` is ONE row [nc] added to every output row (a bias): conv_fast only
-    int f32_split;           // round 5: fp32 units as two bf16 MFMAs on head / tail splits (mma_f32_k16); set by run_gather from the route's policy
+    int f32_split;           // round 5: fp32 units as two bf16 MFMAs on head / tail splits (mma_f32_k16); set by launch_route from the route's policy
     double *stats_tot;       // ABI 9: [DODA_STATS_SLOTS][2][nc / 4][16] totals (4 of 16 used), accumulated with fp64 atomics INSTEAD of the rows, or null
     // ABI 11: row strides in ELEMENTS of x / y / res / bn_x (0: dense — kc, nc, nc, nc): a column slice of a wider matrix, e.g. one
     // half of a U-Net level's concatenation (reference model/unet_block.py:89-93), is read / written in place.  conv_fast only.
@@ -358,6 +358,14 @@ namespace doda_tile {
 // conv_up32 / conv_tile / conv_tile16 (spconv_tile.hip), as route.family says
 int launch(const GatherRoute &route, const GatherOperands &a, hipStream_t s);
 }  // namespace doda_tile
+
+namespace doda_gather {
+// doda_spconv_gather_ex behind describe_gather and plan_gather (gather_plan.hpp), for a caller that holds the description and the
+// route already (doda_layers_run plans its whole list first): the operands from the caller's structs, the trace line, the launch
+const GatherSwitches &switches();
+int launch(const GatherCall &call, const GatherRoute &route, const void *x, const float *w, const int32_t *tbl, void *y, void *ws,
+           const doda_conv_epilogue *epi, hipStream_t s);
+}  // namespace doda_gather
 
 namespace doda_layers {
 // doda_set_option(DODA_OPT_PRE_FWD_ROWS / DODA_OPT_PRE_BWD_ROWS): a BatchNorm op of doda_layers_run with at most this many rows is

@@ -396,7 +396,7 @@ struct PF32 {
     static __device__ __forceinline__ void mma(f32x4 &acc, const raw &w, const raw &x) { mma_f32_k16<false>(acc, w, x); }
 };
 // PF32S: the same kernel with every unit as two bf16 MFMAs on bf16 head / tail splits of both operands (spconv_common.hpp
-// mma_f32_k16<true>): fp32 layers of many rows (run_gather: EpiArgs::f32_split)
+// mma_f32_k16<true>): fp32 layers of many rows (launch_route: EpiArgs::f32_split)
 struct PF32S : PF32 {
     static __device__ __forceinline__ void mma(f32x4 &acc, const raw &w, const raw &x) { mma_f32_k16<true>(acc, w, x); }
 };
@@ -1002,11 +1002,10 @@ GatherSwitches &gather_switches() {
     static GatherSwitches sw = switches_from_env();
     return sw;
 }
-static_assert(GP_TILE_ROWS == TB_T && GP_TILE_K == TB_K && GP_PRE_MAX_C == PRE_MAX_C, "gather_plan.hpp restates these constants");
+static_assert(GP_TILE_ROWS == TB_T && GP_TILE_K == TB_K && GP_PRE_MAX_C == PRE_MAX_C && GP_MAX_K == MAX_K, "gather_plan.hpp restates these constants");
 
-// validate (doda_spconv_gather_ex), plan, pack, launch: an error return has enqueued nothing
-int run_gather(const GatherCall &c, GatherOperands &a, const float *w, void *ws, int *n_part, hipStream_t s) {
-    const GatherRoute r = plan_gather(c, gather_switches());
+// pack, launch what the route names.  The caller has validated (describe_gather) and planned: an error route has enqueued nothing
+int launch_route(const GatherCall &c, const GatherRoute &r, GatherOperands &a, const float *w, void *ws, int *n_part, hipStream_t s) {
     {   // DODA_TRACE_GATHER=1: one line per call on stderr (which layer shapes reach which kernel: tools/gathermap.py)
         static const bool trace = getenv("DODA_TRACE_GATHER") && getenv("DODA_TRACE_GATHER")[0] == '1';
         if (trace) {
@@ -1037,18 +1036,6 @@ int run_gather(const GatherCall &c, GatherOperands &a, const float *w, void *ws,
     case GF_WLDS48: return doda_wlds::launch(r, a, s);
     default: return doda_tile::launch(r, a, s);
     }
-}
-
-bool bad_args(const void *x, int kc, const float *w, int nc, const int32_t *tbl, int ld, int K,
-              int n_out, const void *y, int wl, int *status) {
-    if (kc <= 0 || nc <= 0 || K <= 0 || n_out < 0 || ld < n_out || (wl & 3) > 2 || (wl & ~0x103)) {
-        *status = DODA_ERR_INVALID;
-        return true;
-    }
-    if (n_out == 0) { *status = DODA_OK; return true; }
-    if (!x || !w || !tbl || !y) { *status = DODA_ERR_INVALID; return true; }
-    if (K > MAX_K || nc > 4096 || kc > 4096) { *status = DODA_ERR_UNSUPPORTED; return true; }
-    return false;
 }
 }  // namespace
 
@@ -1125,88 +1112,66 @@ extern "C" int32_t doda_get_option(int32_t option) {
 
 extern "C" size_t doda_spconv_stats_capacity(int32_t n_out) { return n_out > 0 ? (size_t)div_up(n_out, 16) : 1; }
 
-extern "C" int doda_spconv_gather_ex(const void *x, int32_t n_in, int32_t kc, int32_t elem_bytes, const float *w,
-                                     int32_t nc, const int32_t *tbl, int32_t ld, int32_t K, int32_t n_out, void *y,
-                                     int32_t y_is_f32, int32_t w_layout, void *ws, size_t ws_bytes,
-                                     const doda_conv_epilogue *epi, doda_stream_t stream) {
-    int st;
-    if (elem_bytes != 2 && elem_bytes != 4) return DODA_ERR_INVALID;
-    if (bad_args(x, kc, w, nc, tbl, ld, K, n_out, y, w_layout, &st)) {
-        if (st == DODA_OK && epi && epi->stats_rows_h) *epi->stats_rows_h = 0;
-        return st;
-    }
+namespace doda_gather {
+const GatherSwitches &switches() { return gather_switches(); }
+
+// The operands of a described call (EpiArgs / PreArgs from the caller's structs), then the launch of its route
+int launch(const GatherCall &c, const GatherRoute &r, const void *x, const float *w, const int32_t *tbl, void *y, void *ws,
+           const doda_conv_epilogue *epi, hipStream_t s) {
     GatherOperands a{};
     EpiArgs &ep = a.ep;
-    const void *res = nullptr;
-    int n_part = 0;
-    GatherCall c{};
+    PreArgs pre{};
     if (epi) {
-        res = epi->residual;
-        ep.res_bcast = (res && epi->residual_bcast) ? 1 : 0;
-        if (epi->stats) {
-            if (!epi->stats_rows_h) return DODA_ERR_INVALID;
+        a.res = epi->residual;
+        if (c.stats) {
             ep.stats = epi->stats;
             ep.stats_tot = epi->stats_totals;
             if (epi->bn_x) {
-                if (!epi->bn_mean || !epi->bn_invstd || !epi->bn_gamma || !epi->bn_beta) return DODA_ERR_INVALID;
                 ep.bn_x = epi->bn_x;
                 ep.bn_mean = epi->bn_mean; ep.bn_invstd = epi->bn_invstd;
                 ep.bn_gamma = epi->bn_gamma; ep.bn_beta = epi->bn_beta;
                 ep.bn_relu = epi->bn_relu;
             }
         }
-    }
-    PreArgs pre{};
-    if (epi) {
-        if (epi->x_ld < 0 || epi->y_ld < 0 || epi->residual_ld < 0 || epi->bn_x_ld < 0) return DODA_ERR_INVALID;
-        ep.x_ld = (unsigned)epi->x_ld; ep.y_ld = (unsigned)epi->y_ld;
-        ep.res_ld = res ? (unsigned)epi->residual_ld : 0u; ep.bnx_ld = ep.bn_x ? (unsigned)epi->bn_x_ld : 0u;
-        if ((ep.x_ld && ep.x_ld < (unsigned)kc) || (ep.y_ld && ep.y_ld < (unsigned)nc) || (ep.res_ld && ep.res_ld < (unsigned)nc) ||
-            (ep.bnx_ld && ep.bnx_ld < (unsigned)nc))
-            return DODA_ERR_INVALID;
-        if (ep.x_ld == (unsigned)kc) ep.x_ld = 0;      // dense
-        if (ep.y_ld == (unsigned)nc) ep.y_ld = 0;
-        if (ep.res_ld == (unsigned)nc) ep.res_ld = 0;
-        if (ep.bnx_ld == (unsigned)nc) ep.bnx_ld = 0;
-        if (ep.res_bcast) ep.res_ld = 0;
         if (const doda_conv_prologue *q = epi->prologue) {
-            if (q->kind < 1 || q->kind > 3 || q->rows != n_in || q->side_ld < kc || (q->kind >= 2 && q->aux_ld < kc) ||
-                (q->kind >= 3 && q->add_ld < kc) || (q->kind >= 2 && (!q->dgamma || !q->dbeta || !q->totals)) ||
-                (q->kind == 1 && q->totals && (!q->mean || !q->invstd || (!q->running_mean != !q->running_var))) ||
-                (q->kind == 1 && q->totals_b && (q->c_a <= 0 || q->c_a >= kc || q->c_a % 4 || !q->totals)))
-                return DODA_ERR_INVALID;
             pre.kind = q->kind; pre.relu = q->relu ? 1 : 0; pre.rows = q->rows;
 #ifdef DODA_PRE_ABLATE
             { static const int ab = getenv("DODA_PRE_ABLATE") ? atoi(getenv("DODA_PRE_ABLATE")) : 0; pre.kind |= ab << 8; }
 #endif
             pre.tot.ta = q->totals; pre.tot.tb = q->kind == 1 ? q->totals_b : nullptr;
-            pre.tot.ca = (q->kind == 1 && q->totals_b) ? q->c_a : kc;
+            pre.tot.ca = (q->kind == 1 && q->totals_b) ? q->c_a : c.kc;
             pre.tot.m = q->rows; pre.tot.eps = q->eps; pre.tot.momentum = q->momentum;
-            pre.tot.rm = q->running_mean; pre.tot.rv = q->running_var; pre.tot.nbt = (long long *)q->num_batches_tracked;
-            if (q->kind == 1) { pre.tot.out_a = q->mean; pre.tot.out_b = q->invstd; }
-            else { pre.tot.out_a = q->dgamma; pre.tot.out_b = q->dbeta; pre.tot.accum = q->accumulate ? 1 : 0; pre.tot.rm = nullptr; pre.tot.rv = nullptr; pre.tot.nbt = nullptr; }
+            if (q->kind == 1) {
+                pre.tot.rm = q->running_mean; pre.tot.rv = q->running_var; pre.tot.nbt = (long long *)q->num_batches_tracked;
+                pre.tot.out_a = q->mean; pre.tot.out_b = q->invstd;
+            } else { pre.tot.out_a = q->dgamma; pre.tot.out_b = q->dbeta; pre.tot.accum = q->accumulate ? 1 : 0; }
             pre.gamma = q->gamma; pre.beta = q->beta; pre.mean = q->mean; pre.invstd = q->invstd;
             pre.side = q->side; pre.side_ld = (unsigned)q->side_ld;
             pre.aux = q->aux; pre.add = q->add; pre.aux_ld = (unsigned)q->aux_ld; pre.add_ld = (unsigned)q->add_ld;
             a.pre = &pre;
-            c.pre_kind = q->kind; c.pre_rows = q->rows;
-            c.side_ld = pre.side_ld; c.aux_ld = pre.aux_ld; c.add_ld = pre.add_ld;
-            c.side = pre.side && al16(pre.side); c.aux = pre.aux && al16(pre.aux); c.add = pre.add && al16(pre.add);
-            c.saved = pre.mean && pre.invstd; c.totals = pre.tot.ta != nullptr; c.running = pre.tot.rm && pre.tot.rv;
-            c.affine = pre.gamma && pre.beta;
         }
-        c.tilebook = epi->tilebook != nullptr; c.tilebook_rows = epi->tilebook_rows;
         a.tilebook = epi->tilebook;
     }
-    c.K = K; c.kc = kc; c.nc = nc; c.n_out = n_out; c.ld = ld; c.esz = elem_bytes; c.n_in = n_in;
-    c.out32 = elem_bytes == 2 && y_is_f32 != 0;
-    c.layout = w_layout & 3; c.packed = (w_layout & 0x100) != 0; c.ws_bytes = ws ? ws_bytes : 0;
-    c.x_al = (int)((uintptr_t)x & 15); c.y_al = (int)((uintptr_t)y & 15);
-    c.x_ld = ep.x_ld; c.y_ld = ep.y_ld; c.res_ld = ep.res_ld; c.bnx_ld = ep.bnx_ld;
-    c.res_bcast = ep.res_bcast != 0; c.stats = ep.stats != nullptr;
-    a.x = x; a.tbl = tbl; a.y = y; a.res = res;
-    a.kc = kc; a.nc = nc; a.K = K; a.ld = ld; a.n_out = n_out;
-    st = run_gather(c, a, w, ws, &n_part, as_stream(stream));
+    ep.res_bcast = c.res_bcast ? 1 : 0;
+    ep.x_ld = c.x_ld; ep.y_ld = c.y_ld; ep.res_ld = c.res_ld; ep.bnx_ld = c.bnx_ld;
+    a.x = x; a.tbl = tbl; a.y = y;
+    a.kc = c.kc; a.nc = c.nc; a.K = c.K; a.ld = c.ld; a.n_out = c.n_out;
+    int n_part = 0;
+    const int st = launch_route(c, r, a, w, ws, &n_part, s);
     if (st == DODA_OK && epi && epi->stats_rows_h) *epi->stats_rows_h = n_part;
     return st;
+}
+}  // namespace doda_gather
+
+// validate (describe_gather), plan, pack, launch: an error return has enqueued nothing
+extern "C" int doda_spconv_gather_ex(const void *x, int32_t n_in, int32_t kc, int32_t elem_bytes, const float *w,
+                                     int32_t nc, const int32_t *tbl, int32_t ld, int32_t K, int32_t n_out, void *y,
+                                     int32_t y_is_f32, int32_t w_layout, void *ws, size_t ws_bytes,
+                                     const doda_conv_epilogue *epi, doda_stream_t stream) {
+    const GatherDescription d = describe_gather(x, n_in, kc, elem_bytes, w, nc, tbl, ld, K, n_out, y, y_is_f32, w_layout, ws, ws_bytes, epi);
+    if (d.status != DODA_OK || d.call.n_out == 0) {
+        if (d.status == DODA_OK && epi && epi->stats_rows_h) *epi->stats_rows_h = 0;
+        return d.status;
+    }
+    return doda_gather::launch(d.call, plan_gather(d.call, gather_switches()), x, w, tbl, y, ws, epi, as_stream(stream));
 }

@@ -1,6 +1,6 @@
 // LDS-staged sparse-convolution kernel over a tilebook (tilebook.hpp / tilebook.hip): conv_tile (forward and data
 // gradient of the bf16 16- / 32-channel and fp32 16-channel SubM layers).  Dispatched from spconv_gather.hip
-// (run_gather) through doda_tile::launch, on the route gather_plan.hpp chose;
+// (launch_route) through doda_tile::launch, on the route gather_plan.hpp chose;
 // replaces spconv v1.2's indice_conv / indice_conv_backward data path (reference call sites
 // model/unet_block.py:26,29,48) for the layers whose rulebook carries a tilebook.
 #include "common.hpp"

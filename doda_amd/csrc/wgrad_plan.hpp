@@ -33,7 +33,7 @@ struct WgradSwitches {
     // gathering a third of it each (and reading the table nine times)
     bool no33 = false;                 // DODA_WGRAD_NO33
     int t33 = 128;                     // DODA_WGRAD_T33: blocks a 3 x 3 job aims at (a block does nine tiles' worth of work and its chunk writes all K*ca*cb partials)
-    // OPT-IN (see spconv_gather.hip run_gather): fp32 jobs of at least this many rows multiply bf16 head / tail splits (0: all of
+    // OPT-IN (see gather_plan.hpp plan_gather): fp32 jobs of at least this many rows multiply bf16 head / tail splits (0: all of
     // them — one instantiation for every fp32 job keeps the layers of a step in shared launches; -1: none, the exact chain)
     long long f32_split_rows = -1;     // DODA_F32_WGRAD_SPLIT_ROWS
     // Rows from which a rulebook's tile jobs take the LDS-staged kernel even when pair lists are at hand.  Round 4 (block-major

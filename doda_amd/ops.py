@@ -1271,7 +1271,7 @@ def sgd_multi(params, grads, bufs, first, lr, momentum=0.0, dampening=0.0, weigh
 # ---- coarse-level op lists (ABI 11, csrc/layers.hip: doda_layers_run) --------------------------------------
 CX_GEMM, CX_BNFWD, CX_BNBWD, CX_STATS = 1, 2, 3, 4
 # widest BatchNorm op the list takes (csrc/bn_totals.hpp BN_TOT_MAX_C = PRE_MAX_C: the LDS channel vectors of lay_bn / bn_apply and
-# of the folded gather prologue); a wider one returns DODA_ERR_UNSUPPORTED after the ops before it have launched
+# of the folded gather prologue); a list with a wider one is refused with DODA_ERR_UNSUPPORTED before anything launches
 CX_BN_MAX_C = 256
 CX_F_BARRIER, CX_F_IDENTITY, CX_F_RELU, CX_F_TRAINING, CX_F_ACCUM = 1, 2, 4, 8, 16
 

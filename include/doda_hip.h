@@ -666,7 +666,8 @@ typedef struct doda_cx_op {
     float *dgamma, *dbeta;
     const void *tilebook;    /* ABI 12, GEMM: the tilebook of `tbl` (doda_tilebook_build over rows == this op's `rows`), or NULL */
 } doda_cx_op;
-/* *n_launches_h (optional, HOST) receives the number of kernel launches issued. */
+/* The whole list is validated and planned on the host before the first launch: an error return has enqueued nothing (but for
+ * DODA_ERR_LAUNCH).  *n_launches_h (optional, HOST) receives the number of kernel launches issued. */
 int doda_layers_run(const doda_cx_op *ops_h, int32_t n_ops, int32_t elem_bytes, int32_t *n_launches_h, doda_stream_t stream);
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 """tools/bnnumerics.py on the CPU: the probe table of tests/test_gpu_bn_numerics.py reaches every compiled BatchNorm kernel
 (tests/data/bn_instantiations.json, regenerated from the built objects when they are there) and nothing else, has a probe on each
-side of every threshold of the route selection (the constants are parsed from bn.hip / layers.hip), keeps the undecided ReLU
+side of every threshold of the route selection (the constants are parsed from bn.hip / layers_plan.hpp), keeps the undecided ReLU
 masks of every backward probe below 1e-4 of its elements — and its bounds do their work: the fp64 reference rounded once and the
 kernels' expressions in numpy float32 pass them, twelve subtly wrong results (applied to the reference's own outputs) do not."""
 import importlib.util

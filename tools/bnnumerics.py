@@ -77,20 +77,19 @@ PAD = 12345.0       # the unused doubles of a totals line
 
 # ------------------------------------------------------------------------------------------------------ the code's own constants
 def constants():
-    """The thresholds of the route selection, parsed from bn.hip, bn_totals.hpp and layers.hip."""
+    """The thresholds of the route selection: the named constants of bn.hip, bn_totals.hpp and layers_plan.hpp, and three
+    literals of bn.hip's launchers."""
     K = {}
-    src = {f: open(os.path.join(CSRC, f)).read() for f in ("bn.hip", "bn_totals.hpp", "layers.hip")}
+    src = {f: open(os.path.join(CSRC, f)).read() for f in ("bn.hip", "bn_totals.hpp", "layers_plan.hpp")}
     for text in src.values():
-        for m in re.finditer(r"constexpr (?:int|long long) (BN_\w+) = ([0-9* ]+);", text):
+        for m in re.finditer(r"constexpr (?:int|long long) ((?:BN|LAY)_\w+) = ([0-9* ]+);", text):
             K[m[1]] = eval(m[2])
     one = lambda f, pat: int(re.search(pat, src[f])[1])
     K["ROWS_PER_LANE"] = one("bn.hip", r"div_up\(m, g\.rpb \* (\d+)\)")
     K["APPLY_CAP"] = one("bn.hip", r"TOT \? tot_grid_cap\(\) : (\d+), &fixed")
     K["TOT_GRID"] = one("bn.hip", r'env_ll\("DODA_BN_TOT_GRID", (\d+)\)')
-    K["LAY_BN_GRID"] = one("layers.hip", r'env_ll\("DODA_LAY_BN_GRID", (\d+)\)')
-    K["TUNED_ROWS"] = {4: one("layers.hip", r"return esz == 4 \? (\d+) : bf;"), 2: one("layers.hip", r'env_ll\("DODA_LAY_TUNED_ROWS", (\d+)\)')}
-    K["STATS_ROWS_PER_LANE"] = one("layers.hip", r"\(long long\)rpb \* (\d+) - 1\)")
-    K["STATS_GRID"] = one("layers.hip", r"if \(grid > (\d+)\) grid = \1;")
+    K["TUNED_ROWS"] = {4: K["LAY_TUNED_ROWS_F32"], 2: K["LAY_TUNED_ROWS_BF16"]}
+    K["STATS_ROWS_PER_LANE"], K["STATS_GRID"] = K["LAY_STATS_ROWS_PER_LANE"], K["LAY_STATS_GRID"]
     return K
 
 

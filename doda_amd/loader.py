@@ -12,7 +12,8 @@ issuing thread:
      size read-backs of both block this thread only;
   3. the training loop takes a finished (batch, rulebooks) pair with one stream wait.
 
-Data: there is no dataset in this environment.  `SyntheticScenes` stands in for dataset/scannet.py: a pool of procedural
+Data: `dataset_for` picks a split's pool of base scenes by its dataset config's DATASET — the reference's ScanNet / S3DIS /
+3D-FRONT files converted once (doda_amd.datasets), or `SyntheticScenes`, which stands in for dataset/scannet.py: a pool of procedural
 base scenes (doda_amd.scene, generated once into a cache directory, as the reference preprocesses its scans into
 SharedArray, dataset/scannet.py:22-28) and, per sample, what the reference's loader does per sample — a rigid augmentation
 (z-rotation, x-flip, jitter; dataset/augmentor_utils.py:85-104) and the integer voxel coordinates `xyz * voxel_scale - min`
@@ -383,8 +384,11 @@ class DeviceScenes:
     SUBSAMPLE_NATIVE = False
 
     def __init__(self, paths, length, voxel_scale, seed, batch_size, rank, world, device, augment=True, shuffle=True,
-                 full_scale0=128, aug_cfg=None, downsampling_scale=1, subsample_seed=0):
+                 full_scale0=128, aug_cfg=None, downsampling_scale=1, subsample_seed=0, min_extent=0):
         self.device = torch.device(device)
+        # a training sample whose voxel coordinates span fewer than `min_extent` voxels on an axis is drawn again (reference
+        # dataset/front3d.py:80-81, there 64); 0: no such rule
+        self.min_extent = int(min_extent) if augment else 0
         self.length, self.voxel_scale, self.seed, self.bs, self.augment = int(length), float(voxel_scale), int(seed), batch_size, augment
         self.full_scale0 = full_scale0
         # DATA_AUG.aug_list of the dataset config (doda_amd.aug.AugConfig; None or disabled: the rigid augmentation below).  As in
@@ -426,12 +430,29 @@ class DeviceScenes:
 
     @torch.no_grad()
     def _batch(self, ids):
+        if self.min_extent:
+            return self._redrawn(self._wide_enough, ids)
         if self.aug_cfg is not None:
             return self._redrawn(self._augmented, ids)
         m, labels, offsets, bidx = self._rigid(ids)
         out = self._finish(m, labels, offsets, bidx, ids)
         if self.eval_sub is not None:
             out.update(self._full_clouds(ids))
+        return out
+
+    def _wide_enough(self, ids):
+        """The training batch of `ids` under the min_extent rule: EmptySample for the first sample whose largest voxel coordinate on
+        some axis is below min_extent (reference dataset/front3d.py:80: (xyz.max(0) // 64).min() < 1, after the augmentation)."""
+        from . import aug
+        if self.aug_cfg is not None:
+            out = self._augmented(ids)
+        else:
+            out = self._finish(*self._rigid(ids), ids)
+        q, offsets = out["locs32"][:, 1:], out["offsets"].tolist()
+        top = torch.stack([q[offsets[b]:offsets[b + 1]].amax(0) for b in range(len(ids))]).cpu().numpy()      # (read-back: 12 B per sample)
+        for b in range(len(ids)):
+            if (top[b] // self.min_extent).min() < 1:
+                raise aug.EmptySample(b)
         return out
 
     def _redrawn(self, make, ids):
@@ -577,6 +598,13 @@ class MixedDeviceScenes(DeviceScenes):
         return out
 
 
+class FileScenes(SyntheticScenes):
+    """SyntheticScenes over a pool that doda_amd.datasets filled from scannet / s3dis / front3d files: the same items from the same
+    pool format, `length` = the number of scenes (an epoch is one pass).  doda_amd.datasets.file_dataset adds `kind`, `class_names`,
+    `sources` (the files the pool was converted from) and `min_extent`."""
+    kind, class_names, sources, min_extent = None, (), (), 0
+
+
 _OWN_CACHES = []      # cache directories this PROCESS created privately (DODA_PRIVATE_SCENES=1): the only ones it may delete
 
 
@@ -600,6 +628,18 @@ def synthetic_dataset(cfg, args, split):
         cache = _OWN_CACHES[0]
     cache_dir, paths = prepare_cache(n_base, args.synthetic_voxels, voxel_scale, base_seed, cache)
     return SyntheticScenes(paths, args.synthetic_scenes, voxel_scale, seed=base_seed, augment=split != "val")
+
+
+def dataset_for(cfg, args, split, log=None):
+    """The dataset object of a split (`train`, `target`, `val`; `test`: doda_amd.test's) as its dataset config's DATASET says —
+    the fields the loaders use: paths, length, voxel_scale, seed, augment, set_labels.  `synthetic` (or no DATASET key): exactly
+    synthetic_dataset's; `scannet`, `s3dis`, `front3d`: the files under DATA_ROOT, converted once into a pool of base scenes
+    (doda_amd.datasets).  Call it on rank 0 first, then behind a barrier on the others, as for synthetic_dataset."""
+    from . import datasets
+    dataset_cfg = datasets.dataset_config(cfg, split, eval_src=getattr(args, "eval_src", False))
+    if datasets.kind_of(dataset_cfg) == "synthetic":
+        return synthetic_dataset(cfg, args, "val" if split == "test" else split)
+    return datasets.file_dataset(cfg, dataset_cfg, args, split, log)
 
 
 @atexit.register

@@ -102,7 +102,7 @@ def main(argv=None):
     from .collate import collate_device
     from .dsnorm import DSNorm, set_ds_source, set_ds_target
     from .evaluate import score_batch
-    from .loader import EvalScenes, synthetic_dataset
+    from .loader import EvalScenes, dataset_for
     from .model import SparseConvNet
     args, cfg = parse_config(argv)
     check_supported(args)
@@ -140,10 +140,10 @@ def main(argv=None):
 
     # dataset: the split's base scenes, unaugmented, in order
     if rank == 0:
-        ds = synthetic_dataset(cfg, args, "val")      # (generates missing base scenes)
+        ds = dataset_for(cfg, args, "test", log=log)      # (generates / converts missing base scenes)
     ddist.barrier()
     if rank != 0:
-        ds = synthetic_dataset(cfg, args, "val")
+        ds = dataset_for(cfg, args, "test")
     dp = dataset_cfg.DATA_PROCESSOR
     source = EvalScenes(ds.paths, dp.voxel_scale, dp.get("downsampling_scale", 1), seed=args.manual_seed or 0)
     split, epoch = split_name(dataset_cfg), args.start_epoch
@@ -165,7 +165,8 @@ def main(argv=None):
             l, _, _, allacc, _ = meters.read()
             log("Test: [%d/%d] Loss %.4f Accuracy %.4f." % (i + 1, len(groups), l, allacc))
     meters.all_reduce()
-    names = cfg.COMMON_CLASSES.get("class_names", None) or [str(c) for c in range(cfg.COMMON_CLASSES.n_classes)]
+    names = cfg.COMMON_CLASSES.get("class_names", None) or list(getattr(ds, "class_names", None) or []) or \
+        [str(c) for c in range(cfg.COMMON_CLASSES.n_classes)]
     res = results_of(meters, names)
     log("Val result: mIoU/mAcc/allAcc {:.4f}/{:.4f}/{:.4f}.".format(res["mIoU"], res["mAcc"], res["allAcc"]))
     for c, name in enumerate(names):

@@ -19,9 +19,9 @@ target histograms accumulate ON THE DEVICE and are read back every `--print_freq
 are collated on the GPU (doda_amd.collate), the rulebooks of the next batch are built during the
 current step (PyramidPrefetcher), gradients are averaged by doda_amd.dist.GradAllReduce.
 
-Data: there is no dataset in this environment, so the loader here draws seeded synthetic ScanNet-shaped
-scenes (doda_amd.scene); `make_loader` is the one function to replace for real data — it must yield
-the collate dictionary of reference dataset/dataset.py:121-187."""
+Data: the dataset config's DATASET decides (doda_amd.loader.dataset_for): `synthetic` draws seeded
+ScanNet-shaped scenes (doda_amd.scene); `scannet`, `s3dis` and `front3d` read the reference's prepared files
+under DATA_ROOT, converted once into the same pool of base scenes (doda_amd.datasets, cfgs/files/)."""
 import argparse
 import glob
 import math
@@ -317,6 +317,12 @@ def downsampling_scale_of(cfg, split):
     return scale if scale else 1
 
 
+def file_splits(cfg, args):
+    """The splits of this run whose dataset config names a file dataset (DATASET: scannet | s3dis | front3d)."""
+    from . import datasets
+    return [split for split in used_splits(args) if datasets.kind_of(datasets.dataset_config(cfg, split)) != "synthetic"]
+
+
 def used_splits(args):
     return ("train", "target", "val") if getattr(args, "self_train", False) else ("train", "val")
 
@@ -372,6 +378,9 @@ class Trainer:
                              "(drop --host_loader / --inline_loader, or disable tacm)")
         check_aug_loader(cfg, args)
         check_subsample_loader(cfg, args)
+        if args.inline_loader and file_splits(cfg, args):
+            raise ValueError("DATASET of split %s is a file dataset: --inline_loader generates synthetic scenes in the training loop "
+                             "(drop --inline_loader)" % file_splits(cfg, args)[0])
         self.subsampled = any(downsampling_scale_of(cfg, split) > 1 for split in used_splits(args))
         self.step_times = []      # (iterations, seconds) of the steady part of every epoch (see train_epoch)
 
@@ -398,14 +407,18 @@ class Trainer:
         """(iterable of host / device batches, object with set_epoch) per split, made once: the dataset resident in HBM
         (default) or a persistent DataLoader with worker processes (--host_loader; reference dataset/__init__.py:62-75)."""
         from . import dist as ddist
-        from .loader import DeviceScenes, host_loader, synthetic_dataset
+        from .loader import DeviceScenes, dataset_for, host_loader
         if split not in self._loaders:
             if self.rank == 0:
-                ds = synthetic_dataset(self.cfg, self.args, split)      # (generates missing base scenes)
+                ds = dataset_for(self.cfg, self.args, split, log=self.log)      # (generates / converts missing base scenes)
             ddist.barrier()
             if self.rank != 0:
-                ds = synthetic_dataset(self.cfg, self.args, split)
+                ds = dataset_for(self.cfg, self.args, split)
             self._datasets[split] = ds
+            min_extent = getattr(ds, "min_extent", 0)
+            if min_extent and self.args.host_loader:
+                raise ValueError("DATASET front3d: a training sample narrower than %d voxels is drawn again on the device-resident "
+                                 "loader only (drop --host_loader)" % min_extent)
             seed = self.args.manual_seed or 0
             fs0 = self.cfg.DATA_CONFIG.DATA_PROCESSOR.get("full_scale", [128, 512])[0]
             if self.args.host_loader:   # (same sampler seed and the same spatial-shape clip as the HBM-resident loader below)
@@ -426,11 +439,18 @@ class Trainer:
                 dsc = DeviceScenes(ds.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank, self.world,
                                    self.device, augment=ds.augment, shuffle=split != "val",
                                    full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split),
-                                   downsampling_scale=downsampling_scale_of(self.cfg, split), subsample_seed=seed)
+                                   downsampling_scale=downsampling_scale_of(self.cfg, split), subsample_seed=seed, min_extent=min_extent)
                 self._loaders[split] = (dsc, dsc)
             if split in self._labels:
                 self._apply_labels(split)
         return self._loaders[split]
+
+    def epoch_items(self):
+        """Items of a training epoch: --synthetic_scenes, or the scenes of a file dataset's source split (one pass)."""
+        if self.args.inline_loader or self.device.type != "cuda":
+            return int(self.args.synthetic_scenes)
+        self._loader("train")
+        return int(self._datasets["train"].length)
 
     def split_paths(self, split):
         """The base scene files of a split (made on first use, as the split's loader is)."""
@@ -511,8 +531,9 @@ class Trainer:
         args, cfg = self.args, self.cfg
         self.model.train()
         meters = DeviceMeters(cfg.COMMON_CLASSES.n_classes, cfg.DATA_CONFIG.DATA_CLASS.ignore_label, self.device)
-        n_iter = max(1, args.synthetic_scenes // (args.batch_size * self.world))
+        n_iter = max(1, self.epoch_items() // (args.batch_size * self.world))
         target = self._batches(epoch, "target") if args.self_train else None
+        target_passes = 0
         t0 = time.time()
         warm = min(getattr(args, "timing_warmup", 10), max(0, n_iter - 2))
         t_steady = None
@@ -530,7 +551,14 @@ class Trainer:
                 st = cfg.get("SELF_TRAIN", Config())
                 loss, preds, labels = self._pass(batch, pyramid, "source",
                                                  st.get("SRC", Config()).get("loss_weight", 1.0))
-                tb, tp = next(target)
+                nxt = next(target, None)
+                if nxt is None:
+                    # a target split with fewer batches than the source split starts over under another shuffle (the reference's
+                    # DataReader.read_data does this for the shorter side, util/common_utils.py:31-38)
+                    target_passes += 1
+                    target = self._batches(epoch + target_passes * total_epochs, "target")
+                    nxt = next(target)
+                tb, tp = nxt
                 if self.subsampled:      # (host sizes: no read-back)
                     self.log("Subsampled batch: source %d points, target %d points" % (labels.shape[0], tb["labels"].shape[0]))
                 if self.reducer is not None:

@@ -301,10 +301,10 @@ int launch(const Plan &p, const void *desc_dev, hipStream_t s) {
         memset(&ends, 0, sizeof(ends));
         ends.n = g.count;
         for (int k = 0; k < g.count; ++k) ends.end[k] = p.blk_end[g.first + k];
-        if (g.ta == 1 && g.tb == 1) launch_variant<1, 1>(g.blocks, pj + g.first, ends, s);
-        else if (g.ta == 2 && g.tb == 1) launch_variant<2, 1>(g.blocks, pj + g.first, ends, s);
-        else if (g.ta == 1 && g.tb == 2) launch_variant<1, 2>(g.blocks, pj + g.first, ends, s);
-        else launch_variant<2, 2>(g.blocks, pj + g.first, ends, s);
+        // one case per shape pairs_geo can name (wgrad_plan.hpp WP_PAIR_SHAPES)
+#define WP_CASE(A, B) if (g.ta == A && g.tb == B) launch_variant<A, B>(g.blocks, pj + g.first, ends, s);
+        WP_PAIR_SHAPES(WP_CASE)
+#undef WP_CASE
     }
     return doda_check_launch();
 }

@@ -55,6 +55,9 @@ inline WgradSwitches wgrad_switches_from_env() {
             on(getenv("DODA_WGRAD_NO_PAIRS")), !on(getenv("DODA_NO_WDMA")), on(getenv("DODA_TRACE_WGRAD"))};
 }
 
+// wgrad_pairs_kernel's shapes TA x TB: blocks of 16 channels of (a, b) per wave (pairs_geo: two where the operand has two or more)
+#define WP_PAIR_SHAPES(X) X(1, 1) X(2, 1) X(1, 2) X(2, 2)
+
 constexpr size_t wp_align256(size_t x) { return (x + 255) / 256 * 256; }
 constexpr int wp_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline bool wp_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }

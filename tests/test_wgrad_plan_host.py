@@ -6,7 +6,13 @@ doda_spconv_wgrad_multi_workspace_bytes returned for them on the commit before t
 this tree is held to the same record).  Both sides of every threshold are named; the instantiations dense_compiled admits (the
 program's `--compiled` mode; launch_multi_variant instantiates nothing else), the wgrad_multi_kernel symbols of the built object
 (tests/data/wgrad_instantiations.json), the routes of the sweep and the routes of the numerics probes of
-tests/test_gpu_wgrad_numerics.py (tests/data/wgrad_numerics.json, regenerated here from the plan) are one set of 50 names."""
+tests/test_gpu_wgrad_numerics.py (tests/data/wgrad_numerics.json, regenerated here from the plan) are one set of 50 names: the
+gather-table class.  The other three classes have their own set: the program names what it chose for a wide, pair or tile job
+(slice shape and counts, PairsGeo, channel blocks and workgroups) and lists the compiled wide and pair shapes (`--shapes`); listed =
+walked = probed holds for the eight wgrad_wide slice shapes and the four wgrad_pairs_kernel shapes, and
+tests/data/wgrad_class_numerics.json — the pair, tile and wide probes of tests/test_gpu_wgrad_numerics.py, with wgrad_dma16's
+chunking regimes asserted from its formula — is regenerated here byte for byte.  The 1e-4 bound of those probes is shown to reject
+a missing row and local indices that are off by one list position."""
 import importlib.util
 import json
 import os
@@ -37,6 +43,7 @@ def planner(request, tmp_path_factory):
     def ask(lines):
         return wn.ask_planner(exe, lines)
     ask.compiled = lambda: subprocess.run([exe, "--compiled"], capture_output=True, text=True, check=True, timeout=300).stdout.splitlines()
+    ask.shapes = lambda: subprocess.run([exe, "--shapes"], capture_output=True, text=True, check=True, timeout=300).stdout.splitlines()
     return ask
 
 
@@ -158,6 +165,79 @@ def test_one_set_of_names(planner, swept):
         assert p["n_rows"] in wn.SHAPES and p["ld"] == p["n_rows"] + 3 and p["n_a"] != p["n_rows"], p
         assert (p["R"], p["rows_per_chunk"]) == ((1, 64) if p["n_rows"] == 37 else (2, 576)), p
     assert all(len([p for p in recorded if p["route"] == n]) == 2 for n in admitted)
+
+
+def test_one_set_of_names_for_the_wide_and_pair_classes(planner):
+    """Listed = walked = probed: the eight slice shapes of WW_SHAPES are the shapes ww_shape produces over every channel pair of
+    48 .. 224 channels, and the shapes of the recorded wide probes; the four shapes of WP_PAIR_SHAPES are the ones pairs_geo
+    produces and the recorded pair probes run.  cb = 176 and 208 (11 and 13 blocks: no slice of at most 7 blocks but 1 divides
+    them) stay with the gather-table class.  The recorded list is the one the plan generates."""
+    listed = [tuple(l.split()) for l in planner.shapes()]
+    wide = {(int(a), int(b)) for k, a, b in listed if k == "wide"}
+    pair = {"wgrad_pairs_kernel<%s, %s>" % (a, b) for k, a, b in listed if k == "pairs"}
+    assert len(listed) == 12 and len(wide) == 8 and len(pair) == 4
+    first, refused = wn.wide_walk(planner)
+    assert refused and {cb for _, cb in refused} == {176, 208} and len(refused) == 2 * len(wn.WIDE_CHANNELS), refused
+    rec = wn.generate_class(planner)
+    assert wn.dump_class(rec) == open(wn.CLASS_PROBES).read()       # regenerate: python tools/wgradnumerics.py --class-probes PLANNER
+    rec = wn.load_class_probes()
+    assert wide == set(first) == {(p["ta"], p["tb"]) for p in rec["wide"]} == set(wn.WIDE_SHAPE_PAIRS)
+    channels = (16, 32, 48, 64)
+    got = planner([wn.job(n_rows=3000, ca=ca, cb=cb, pairs=1) for ca in channels for cb in channels])
+    assert all(g["cls"] == "pairs" for g in got)
+    assert pair == {g["route"] for g in got} == {p["route"] for p in rec["pairs"]}
+    # the tile group: all twelve channel pairs, every regime of the chunking in some composition, every composition at every shape
+    assert {tuple(j) for c in rec["tile"] for j in c["jobs"]} == set(wn.TILE_PAIRS) and len(wn.TILE_PAIRS) == 12
+    assert {r for c in rec["tile"] for v in c["regimes"].values() for r in v} == set(wn.TILE_REGIMES)
+    assert all(set(c["regimes"]) == set(wn.SHAPE_ROWS) for c in rec["tile"])
+    # what the device run reports and what it must trace are functions of the record
+    assert [len(wn.class_results(g, rec)) for g in wn.CLASS_GROUPS] == [86, 180, 60]
+    assert len(set(wn.class_results("wide", rec))) == 60 and len(set(wn.class_results("tile", rec))) == 180
+
+
+def test_the_designed_tables_hold_what_their_recipes_say():
+    """tools/wgradnumerics.py design_table: the distinct rows of every tile (numpy.unique) — 1023 for the full list, 1024 just over
+    it, more for the scattered tile; the chunk boundary of the gather-table plan (row 576) lies in tile 2, once unlisted, once
+    listed — for the tile group's tables and for every wide probe's."""
+    rec = wn.load_class_probes()
+    for name in ["tile"] + [p["name"] for p in rec["wide"]]:
+        for shape, n in wn.SHAPE_ROWS.items():
+            t, distinct = wn.design_table(name, shape)
+            assert t.shape == (27, n + 3) and t.min() == -1 and t.max() < n
+            unlisted = tuple(k for k, d in enumerate(distinct) if d > wn.TILE_LMAX)
+            assert unlisted == wn.UNLISTED[shape]
+            if n == 1100:
+                assert wn.CHUNKS[n] == (2, 576) and 576 // wn.TILE_ROWS == 2 and 576 % wn.TILE_ROWS == 64
+                assert sorted(distinct[1:3]) == [1023, 1024] and len(distinct) == 5
+    assert (2 in wn.UNLISTED["1100A"]) != (2 in wn.UNLISTED["1100B"])
+
+
+def test_the_class_bound_rejects_a_missing_row_and_shifted_local_indices():
+    """tools/wgradnumerics.py check() on the CPU, for the smallest and the largest probe of each class group: the fp64 reference
+    rounded to fp32 passes in both modes; the same sum without one row's contribution, and with the local indices of one tile moved
+    one list position on, misses the 1e-4 bound."""
+    import torch
+    rec = wn.load_class_probes()
+    cases = [(wn.tile_probe(48, 48, "37", "wide"), "37", 0), (wn.tile_probe(224, 224, "1100A", "wide"), "1100A", 1),
+             (wn.tile_probe(16, 16, "37"), "37", 0), (wn.tile_probe(64, 32, "1100B"), "1100B", 2)]
+    pairs = {p["name"]: p for p in rec["pairs"]}
+    cases += [(pairs["pairs identity 37 rows 16->16"], "identity", 0), (pairs["pairs two ranges 48->48"], "two ranges", 9)]
+    for p, shape, tile in cases:
+        tbl = wn.class_table(p, shape)
+        I = wn.class_inputs(p, shape, tbl, torch.device("cpu"))
+        R = wn.class_reference(p, I)
+        side = "a" if "table" in p else "b"        # the operand the table's columns count
+        col = tile * wn.TILE_ROWS + int((tbl[:, tile * wn.TILE_ROWS:I[side].shape[0]] >= 0).any(0).nonzero()[0])
+        less = I[side].clone()
+        less[col] = 0
+        no_row = wn.class_reference(p, dict(I, **{side: less}))[0]
+        shifted = wn.class_reference(p, dict(I, tbl=wn.shift_tile(tbl, tile)))[0]
+        for acc in (0, 1):
+            base = I["base"].double() if acc else 0.0
+            err, fails = wn.check(p, I, (R[0] + base).float(), acc, R)
+            assert fails == [] and err["max_rel"] < 1e-6, (p["name"], acc, err)
+            for bad in (no_row, shifted):
+                assert wn.check(p, I, (bad + base).float(), acc, R)[1], (p["name"], acc)
 
 
 def test_the_split_bound_rejects_a_dropped_partial_product():

@@ -17,14 +17,15 @@ __device__ unsigned g_tb_dbg[8 + 2 * 2048];   // [0] hits, [1] tile, [2] U, [3] 
 #endif
 namespace {
 
-constexpr int HCAP = 4096;   // hash slots: the insert loop stops adding once TB_UMAX + 256 keys are in
+constexpr int HCAP = TB_HCAP;   // hash slots: the insert loop stops adding once TB_UMAX + 256 keys are in
 constexpr unsigned EMPTY = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(256) void tilebook_build(const int32_t *__restrict__ tbl, int ld, int n,
                                                       TileBookView v) {
-    constexpr int UQ = 2048;          // sort buffer: the power of two above TB_UMAX
-    // hash slots and sort buffer back to back: the bitmap form uses both as ONE array of BMW words (196608 bits)
+    constexpr int UQ = TB_UQ;         // sort buffer: the power of two above TB_UMAX
+    // hash slots and sort buffer back to back: the bitmap form uses both as ONE array of BMW words (TB_BITMAP_BITS = 196608 bits)
     constexpr int BMW = HCAP + UQ;
+    static_assert(BMW * 32 == TB_BITMAP_BITS, "the bitmap is the hash slots and the sort buffer");
     __shared__ unsigned hq[BMW];
     unsigned *const htab = hq, *const uq = hq + HCAP;
     static_assert(TB_UMAX <= UQ, "sort buffer");
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void tilebook_build(const int32_t *__restrict_
         doda_sync();
         const int lo = min(min(wmn[0], wmn[1]), min(wmn[2], wmn[3])), hi = max(max(wmx[0], wmx[1]), max(wmx[2], wmx[3]));
         const long long span = (long long)hi - lo + 1;
-        if (hi >= 0 && span <= (long long)BMW * 32) {
+        if (hi >= 0 && span <= (long long)TB_BITMAP_BITS) {
             const int W = (int)((span + 31) >> 5);              // words in use
             const int wpt = (W + 255) / 256;                    // consecutive words per thread (<= 24)
             for (int k = 0; k < wpt; ++k) { const int w = tid * wpt + k; if (w < W) htab[w] = 0u; }

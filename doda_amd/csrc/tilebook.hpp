@@ -34,6 +34,12 @@ constexpr int TB_CAP64 = 960;    // kernel capacity for 64-byte rows (2 workgrou
 constexpr int TB_K = 27;
 constexpr int TB_LW = 10;        // planes of local indices (32-bit words per output row, three 10-bit indices each)
 constexpr int TB_LIDX_BYTES = TB_T * TB_LW * 4;   // 10240 per tile
+// The builder's LDS arrays (tilebook.hip): TB_HCAP hash slots and a sort buffer of TB_UQ keys, back to back.  Its bitmap form uses
+// both as ONE array of bits, one per row number between a tile's smallest and largest referenced row: a tile whose rows span
+// at most TB_BITMAP_BITS row numbers takes the bitmap form, a wider one the hash + sort form.
+constexpr int TB_HCAP = 4096;
+constexpr int TB_UQ = 2048;      // the power of two above TB_UMAX
+constexpr int TB_BITMAP_BITS = (TB_HCAP + TB_UQ) * 32;   // 196608
 
 struct TileBookView {
     int32_t *ulist;     // [nt][TB_UMAX]

@@ -5,10 +5,13 @@
 // operands all present, aligned and dense.
 // With the argument `--compiled`: no stdin; one line per instantiation that the predicates of gather_plan.hpp admit, as route_name
 // writes it, from a walk over the whole parameter grid.
+// With the argument `--constants`: no stdin; the tilebook's constants (tilebook.hpp) as `name=value` lines, TB_BITMAP_BITS — the
+// widest span of row numbers a tile may have and still take the builder's bitmap form — among them.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../doda_amd/csrc/gather_plan.hpp"
+#include "../../doda_amd/csrc/tilebook.hpp"
 
 static void admit(bool yes, GatherRoute r) {
     if (!yes) return;
@@ -54,6 +57,12 @@ static void print_compiled() {
 
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "--compiled")) { print_compiled(); return 0; }
+    if (argc > 1 && !strcmp(argv[1], "--constants")) {
+        printf("TB_T=%d\nTB_UMAX=%d\nTB_LMAX=%d\nTB_CAP64=%d\nTB_K=%d\nTB_LW=%d\nTB_BITMAP_BITS=%d\n", TB_T, TB_UMAX, TB_LMAX, TB_CAP64, TB_K, TB_LW,
+               TB_BITMAP_BITS);
+        printf("GP_TILE_MAX_GROUPS=%d\nGP_TILE16_GROUPS=%d\n", GP_TILE_MAX_GROUPS, GP_TILE16_GROUPS);
+        return 0;
+    }
     char line[4096];
     while (fgets(line, sizeof line, stdin)) {
         GatherCall c{};

@@ -49,6 +49,8 @@ def planner(request, tmp_path_factory):
         return [dict(status=int(m[1]), route=m[2], grid=int(m[3]), block=int(m[4]), parts=int(m[5]), frags=int(m[6]))
                 for m in out]
     ask.compiled = lambda: subprocess.run([exe, "--compiled"], capture_output=True, text=True, check=True, timeout=300).stdout.splitlines()
+    ask.constants = lambda: {k: int(v) for k, v in (l.split("=") for l in subprocess.run(
+        [exe, "--constants"], capture_output=True, text=True, check=True, timeout=300).stdout.splitlines())}
     return ask
 
 
@@ -160,3 +162,38 @@ def test_extended_sweep_settles_every_instantiation(planner):
         assert (g["status"], g["route"], g["grid"], g["parts"]) == (0, p["route"], p["grid"], p["parts"]), (p, g)
         assert p["n_out"] % 16 != 0 and p["n_out"] >= 37 and p["ld"] == p["n_out"] + 3 and p["n_in"] != p["n_out"], p
         assert not p["res_bcast"] or p["group"].startswith("fast")
+
+
+def test_tile_class_probes_regenerate_and_cover_every_tile_kernel(planner):
+    """tests/data/gather_tile_class.json (the probes of the LDS-staged kernels over designed tilebooks, tools/gathernumerics.py) is
+    the list the plan generates; the names it probes, the tile-kernel names the predicates admit and the compiled ones are one
+    set of 27; the tilebook constants the generator restates are those of tilebook.hpp and gather_plan.hpp."""
+    gn = _numerics()
+    k = planner.constants()
+    assert (k["TB_T"], k["TB_UMAX"], k["TB_LMAX"], k["TB_CAP64"], k["TB_K"], k["TB_LW"], k["TB_BITMAP_BITS"]) == (
+        gn.TB_T, gn.TB_UMAX, gn.TB_LMAX, gn.TB_CAP64, gn.TB_K, gn.TB_LW, gn.TB_BITMAP_BITS) and k["TB_BITMAP_BITS"] == 196608
+    widths = {w for _, _, w in gn.TILE_TABLES.values()}
+    assert widths == {k["GP_TILE_MAX_GROUPS"], k["GP_TILE16_GROUPS"]} == {768, 512}
+    tile = lambda names: {n for n in names if re.match(r"conv_(tile|tile16|wlds48)<", n)}
+    compiled = tile(json.load(open(os.path.join(ROOT, "tests", "data", "gather_instantiations.json"))))
+    admitted = planner.compiled()
+    recorded = gn.load_tile_class()
+    assert gn.generate_tile_class(planner, admitted) == recorded
+    assert gn.dump_tile_class(recorded) == open(gn.TILE_CLASS).read()
+    probed = {p["route"] for p in recorded}
+    assert tile(admitted) == compiled == probed and len(probed) == 27
+    families = [re.match(r"\w+", n).group(0) for n in probed]
+    assert {f: families.count(f) for f in families} == {"conv_tile": 21, "conv_tile16": 4, "conv_wlds48": 2}
+    for name in probed:         # both arrangements of the launch width; the 1031-tile table for six names
+        tables = sorted(p["table"] for p in recorded if p["route"] == name)
+        w = "w768" if name.startswith("conv_tile<0") else "w512"
+        assert tables == [w + "A", w + "B"] + (["w512C"] if name in gn.ON_1031 else []), (name, tables)
+    on_1031 = [n for n in gn.ON_1031 if not n.startswith("conv_tile16")]
+    assert len(on_1031) == 2 and on_1031[0].endswith("true>") and on_1031[1].startswith("conv_tile<2")
+    for p, g in zip(recorded, planner([gn.plan_line(p) for p in recorded])):
+        assert (g["status"], g["route"], g["grid"], g["parts"]) == (0, p["route"], p["grid"], p["parts"]), (p, g)
+        assert p["ld"] == p["n_out"] + 3 and p["n_in"] == p["n_out"] + 5 and p["layouts"] == [0, 2] and not p["res_bcast"]
+        assert (p["n_out"], p["n_in"], p["ld"]) == gn.table_rows(p["table"]) and p["n_out"] <= 264000
+        assert p["group"] in gn.TILE_GROUPS
+        # conv_tile<0, ., ., 1, false> at 769 tiles or more: only with the pipeline option off
+        assert (p["off"] == ["tile_pipeline"]) == bool(re.match(r"conv_tile<0, \w+, \w+, 1, false>", p["route"])), p

@@ -46,17 +46,38 @@ def _scene_table(m, seed=0, batch=2, shape=(80, 70, 60)):
     return idx, ops.rulebook_subm(idx, list(shape), batch, 3)
 
 
-def _far_apart_table(n=300000, second_div=1):
-    """Every tile references two clusters of rows ~200k rows apart (span above the builder's 131072-bit bitmap: the hash +
-    sort form), ~570 distinct rows per tile; some entries absent."""
+def _far_apart_table(n=400000, second_div=1):
+    """Every tile references two clusters of rows 200 000 rows apart (modulo n = 400 000, so from either side) — a span above the
+    196 608 bits of the builder's bitmap (tilebook.hpp TB_BITMAP_BITS): the hash + sort form, for EVERY tile (asserted; with
+    300 000 rows the second cluster of two tiles in three wrapped around to 100 000 rows from the first, and those tiles took the
+    bitmap form) —, up to ~540 distinct rows per tile; some entries absent."""
     t = torch.arange(n, dtype=torch.int64)
+    t0 = t // 256 * 256
     tbl = torch.empty(27, n, dtype=torch.int64)
     for o in range(27):
-        tbl[o] = (t + o) % n if o < 13 else (t // second_div + 200000 + o) % n   # (second_div = 2: ~410 distinct rows per tile)
+        # (second_div = 2: the second cluster of a tile has half as many rows, ~410 distinct rows per tile)
+        tbl[o] = (t + o) % n if o < 13 else (t0 + (t - t0) // second_div + 200000 + o) % n
     g = torch.Generator().manual_seed(3)
     tbl[torch.rand(27, n, generator=g) < 0.3] = -1
     tbl[13] = t   # the centre tap is always present
+    nt = -(-n // 256)
+    ent = torch.full((27, nt * 256), -1, dtype=torch.int64)
+    ent[:, :n] = tbl
+    ent = ent.view(27, nt, 256)
+    span = ent.amax((0, 2)) - torch.where(ent >= 0, ent, torch.full_like(ent, n)).amin((0, 2)) + 1
+    assert int(span.min()) > _bitmap_bits(), int(span.min())      # every tile takes the hash + sort form
     return tbl.int().to(dev())
+
+
+def _bitmap_bits():
+    """tilebook.hpp TB_BITMAP_BITS as tools/gathernumerics.py restates it (tests/test_gather_plan_host.py holds the two together)"""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("gathernumerics", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                                                 "tools", "gathernumerics.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.TB_BITMAP_BITS
 
 
 @pytest.mark.parametrize("m", [40000, 1000, 256, 255, -1, -2])

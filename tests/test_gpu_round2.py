@@ -91,7 +91,8 @@ def test_packed_weights_follow_every_update_style(native_lib, style):
             done[(device, esz)] = orig(device, esz)
         plan = done[(device, esz)]
         plan.gen = dconv._GEN[0]
-        plan.versions = tuple(m().weight._version for m in plan.refs)
+        # (the plan also lists the modules of the two networks above until the collector takes them: a dead one has no version to follow)
+        plan.versions = tuple(-1 if (mod := m()) is None else mod.weight._version for m in plan.refs)
         return plan
     dconv._repack_all = frozen
     try:

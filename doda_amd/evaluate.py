@@ -25,7 +25,7 @@ def score_batch(cfg, model, batch, meters, device, feature_dtype, want_preds=Fal
     where the batch has one; uint8 there, int64 otherwise) when want_preds, else None.  cell_side: metres, default
     default_cell_side(DATA_CONFIG.DATA_PROCESSOR.voxel_scale)."""
     from . import ops
-    from .model import criterion_of, sparse_input, voxelize_and_run
+    from .model import criterion_of, sparse_input, unwrap, voxelize_and_run
     ignore = cfg.DATA_CONFIG.DATA_CLASS.ignore_label
     if not has_full_cloud(batch):
         scores = voxelize_and_run(cfg, model, batch, device, feature_dtype=feature_dtype, inputs_ready=True, pyramid=pyramid)
@@ -33,7 +33,7 @@ def score_batch(cfg, model, batch, meters, device, feature_dtype, want_preds=Fal
         preds = scores.argmax(1)
         meters.update(loss, preds, batch["labels"])
         return preds if want_preds else None
-    net = model.module if hasattr(model, "module") else model
+    net = unwrap(model)
     inp, p2v, _ = sparse_input(cfg, model, batch, device, feature_dtype, inputs_ready=True, pyramid=pyramid)
     feats = net._trunk(inp).features.contiguous()
     if cell_side is None:

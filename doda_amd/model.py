@@ -12,20 +12,25 @@ tests/test_oracle_unet.py and tests/test_gpu_unet.py check that equivalence thro
 tests/golden/unet_golden.npz / unet_state_keys.json, which the reference's own model files produced.
 """
 import functools
+import os as _os
+import threading
 from collections import OrderedDict
+from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 
 import torch
 from torch import nn
 from torch.autograd import Function
+from torch.nn.modules.module import register_module_module_registration_hook
 
-from torch.nn.modules import module as _torch_module
-
+from . import nn as _dnn
 from . import ops as _ops
 from . import pointgroup_ops, spconv
+from .lovasz import _VoxelHeadLovasz, lovasz_softmax
 from .spconv import conv as _cv
 from .spconv import functional as Fsp
-from .spconv.modules import SparseModule
+from .spconv.modules import SparseModule, _run, any_hooks
+from .streams import independent_stream
 
 
 def default_cfg(n_classes=20, in_channel=3, mid_channel=16, block_reps=2, block_residual=True,
@@ -40,17 +45,12 @@ def default_cfg(n_classes=20, in_channel=3, mid_channel=16, block_reps=2, block_
                                DATA_CLASS=SimpleNamespace(n_classes=n_classes, ignore_label=255)))
 
 
-def _shallow(t):
-    """A second SparseConvTensor header over the same features / rulebooks: SparseSequential
-    re-binds `.features` on the object it is given, so a branch that must keep the incoming
-    features takes its own header (reference unet_block.py:33,89)."""
-    c = spconv.SparseConvTensor(t.features, t.indices, t.spatial_shape, t.batch_size)
-    c.indice_dict = t.indice_dict   # same forward pass: rulebooks and weight-pack generation are shared
-    return c
+def unwrap(model):
+    """The network itself behind a DistributedDataParallel-style wrapper."""
+    return model.module if hasattr(model, "module") else model
 
 
 # One extension call per residual block instead of one per BatchNorm / convolution (DODA_FAST_BLOCKS=0: module by module)
-import os as _os
 FAST_BLOCKS = _os.environ.get("DODA_FAST_BLOCKS", "1") == "1"
 # Skip connections through the BatchNorm's pass-through output (round 3): a tensor that feeds a fused BatchNorm AND a skip
 # (the U-Net level's concatenation, reference model/unet_block.py:89-93; the 1x1 skip of a channel-changing block) hands
@@ -60,6 +60,164 @@ FAST_BLOCKS = _os.environ.get("DODA_FAST_BLOCKS", "1") == "1"
 SKIP_IN_BLOCK = SKIP_VIA_BN = _os.environ.get("DODA_SKIP_FUSION", "1") == "1"
 # The concatenation's BatchNorm takes the statistics rows of its two halves (conv epilogues) instead of sweeping the new tensor
 CAT_STATS = _os.environ.get("DODA_CAT_STATS", "1") == "1"
+
+
+# ---- one description per block, cached until the module tree changes ----
+# The generation counts submodule registrations anywhere in the process: setattr / add_module of a submodule (so also
+# SyncBatchNorm.convert_sync_batchnorm and DSNorm.convert_dsnorm); train(), eval() and .float() register nothing.  A direct write
+# into `_modules[...]` bypasses the hook.  What no registration reports — a replaced Parameter, its dtype, requires_grad, training —
+# is looked at per call, where the operands are gathered.
+_STRUCTURE = [0]
+
+
+def _structure_changed(module, name, submodule):
+    _STRUCTURE[0] += 1
+
+
+register_module_module_registration_hook(_structure_changed)
+
+
+def _described(module, describe):
+    """describe(module), kept on the module (its one cache entry) until the next registration of a submodule."""
+    entry = module.__dict__.get("_doda_desc")
+    if entry is None or entry[0] != _STRUCTURE[0]:
+        entry = module.__dict__["_doda_desc"] = (_STRUCTURE[0], describe(module))
+    return entry[1]
+
+
+def _plain_bn(m):
+    return type(m) is nn.BatchNorm1d and m.affine and m.track_running_stats and m.momentum is not None
+
+
+def _plain_conv(m, cls, ksize):
+    return type(m) is cls and m.bias is None and m.kernel_size == ksize
+
+
+def _op_list_bn(m):   # (the kernels' widest BatchNorm; width 32 carries 320 / 384 / 448 channels at levels 5-7)
+    return m._parameters["weight"].dtype == torch.float32 and m.num_features <= _ops.CX_BN_MAX_C
+
+
+def _op_list_conv(m):
+    return (m._parameters["weight"].dtype == torch.float32 and m.in_channels % 16 == 0 and m.out_channels % 16 == 0
+            and m.in_channels >= 16)
+
+
+class _Block:
+    """The plain residual block of the reference (model/unet_block.py:9-37): [BN, ReLU, SubM3, BN, ReLU, SubM3] + skip.
+    skip: the bias-free 1x1 SubM convolution that can run inside an extension call, or None (`identity`, or any other i_branch,
+    which then runs as a module); modules: what the hook sweep of a route looks at; per_block / op_list: does the block meet what
+    ext.residual_block (channels in fours) / the op list (channels in sixteens, fp32 weights, BatchNorm width) asks of it."""
+    __slots__ = ("bn1", "bn2", "conv1", "conv2", "skip", "identity", "modules", "per_block", "op_list")
+
+
+def _describe_block(block):
+    mods = tuple(block.conv_branch._modules.values())
+    if not (len(mods) == 6 and _plain_bn(mods[0]) and type(mods[1]) is nn.ReLU and _plain_conv(mods[2], spconv.SubMConv3d, [3, 3, 3])
+            and _plain_bn(mods[3]) and type(mods[4]) is nn.ReLU and _plain_conv(mods[5], spconv.SubMConv3d, [3, 3, 3])
+            and mods[2].indice_key is not None and mods[2].indice_key == mods[5].indice_key):
+        return None
+    d = _Block()
+    d.bn1, d.conv1, d.bn2, d.conv2 = mods[0], mods[2], mods[3], mods[5]
+    sk = tuple(block.i_branch._modules.values())
+    d.identity = len(sk) == 1 and type(sk[0]) is nn.Identity
+    d.skip = sk[0] if (len(sk) == 1 and _plain_conv(sk[0], spconv.SubMConv3d, [1, 1, 1]) and sk[0].in_channels % 4 == 0
+                       and sk[0].out_channels % 4 == 0) else None
+    d.modules = (block.conv_branch, block.i_branch) + mods + sk
+    convs = (d.conv1, d.conv2) if d.skip is None else (d.conv1, d.conv2, d.skip)
+    d.per_block = all(c.in_channels % 4 == 0 and c.out_channels % 4 == 0 for c in convs)
+    d.op_list = ((d.identity or d.skip is not None) and all(_op_list_conv(c) for c in convs)
+                 and _op_list_bn(d.bn1) and _op_list_bn(d.bn2))
+    return d
+
+
+class _Triple:
+    """[norm, ReLU, sparse convolution]: a level's `conv` (down) and `deconv` (up) sequences (model/unet_block.py:62-85).
+    op_list: "down" / "up" when the op list takes it as that step (plain BatchNorm, bias-free k2 convolution, strided for down,
+    inverse for up, channels in sixteens, fp32), else None."""
+    __slots__ = ("bn", "conv", "modules", "op_list")
+
+
+def _describe_triple(seq):
+    mods = tuple(seq._modules.values())
+    if not (len(mods) == 3 and type(mods[1]) is nn.ReLU and isinstance(mods[2], spconv.SparseConvolution)):
+        return None
+    d = _Triple()
+    d.bn, d.conv, d.modules = mods[0], mods[2], (seq,) + mods
+    kind = ("down" if type(d.conv) is spconv.SparseConv3d and d.conv.stride == [2, 2, 2] else
+            "up" if type(d.conv) is spconv.SparseInverseConv3d else None)
+    d.op_list = kind if (kind and _plain_bn(d.bn) and _op_list_bn(d.bn) and d.conv.bias is None and d.conv.kernel_size == [2, 2, 2]
+                         and _op_list_conv(d.conv)) else None
+    return d
+
+
+def _bn_operands(bn):
+    """bn x5 of both extension calls: gamma, beta, running_mean, running_var, num_batches_tracked — the objects of THIS call."""
+    par, buf = bn._parameters, bn._buffers
+    return [par["weight"], par["bias"], buf["running_mean"], buf["running_var"], buf["num_batches_tracked"]]
+
+
+def _block_operands(d, feats, idict, rows, training, skip_in_call, pairs):
+    """What either route hands the extension for one block — (rulebook, bn1 x5, conv1 x3, bn2 x5, conv2 x3, skip conv x5 | None) —
+    or None where a precondition fails.  conv x3 = weight, packed forward, packed data-grad.  skip conv x5 (when skip_in_call) =
+    conv x3, the identity table of `rows` rows, and that table again as both pair lists of the skip's weight gradient where
+    `pairs` and the level is large enough for lists, else None."""
+    bn1, bn2, c1, c2 = d.bn1, d.bn2, d.conv1, d.conv2
+    data = idict.get(c1.indice_key)
+    if (data is None or data.kind != "subm" or data.tbl.shape[1] != rows or bn1.training != training or bn2.training != training
+            or c1.training != training or c2.training != training):
+        return None
+    b1, b2 = _bn_operands(bn1), _bn_operands(bn2)
+    pk1, pk2 = c1._packed(feats, idict), c2._packed(feats, idict)
+    if pk1 is None or pk2 is None or b1[0].dtype != torch.float32 or b2[0].dtype != torch.float32:
+        return None
+    sc = None
+    if skip_in_call:
+        w = d.skip._parameters["weight"]
+        pks = d.skip._packed(feats, idict)
+        if pks is None:
+            return None
+        ident = _cv._identity_table(rows, feats.device)
+        sc = [w, pks[0], pks[1], ident, ident if (pairs and Fsp._want_pairs(feats, w, rows)) else None]
+    return (data, b1, [c1._parameters["weight"], pk1[0], pk1[1]], b2, [c2._parameters["weight"], pk2[0], pk2[1]], sc)
+
+
+def _triple_operands(d, feats, idict, rows, training):
+    """(strided rulebook, bn x5, conv x3) of a down or up step at the level with `rows` rows, or None where a precondition fails."""
+    data = idict.get(d.conv.indice_key)
+    if data is None or data.kind != "down2" or d.bn.training != training or data.tbl_rev.shape[1] != rows:
+        return None
+    pk = d.conv._packed(feats, idict)
+    bn = _bn_operands(d.bn)
+    if pk is None or bn[0].dtype != torch.float32:
+        return None
+    return data, bn, [d.conv._parameters["weight"], pk[0], pk[1]]
+
+
+def _residual_block_args(d, feats, stats, operands, rb, skip, want_stats):
+    """ext.residual_block's positional arguments (csrc_ext/doda_torch.cpp, the comment above residual_block and its signature:
+    x, stats_in, bn1, bn2, training, momentum1, eps1, momentum2, eps2, cv1, cv2, rb, n_out, skip, want_stats, sc, stats_in_b)."""
+    data, bn1, cv1, bn2, cv2, sc = operands
+    stats_b = None
+    if isinstance(stats, tuple):   # the input is a channel concatenation: statistics rows of its two halves
+        stats, stats_b = stats
+    return (feats, stats, bn1, bn2, d.bn1.training, d.bn1.momentum, d.bn1.eps, d.bn2.momentum, d.bn2.eps, cv1, cv2, rb,
+            data.outids.shape[0], skip, want_stats, sc or [], stats_b)
+
+
+def _block_step(d, operands):
+    """(tensors, scalars) of an op-list RB step (csrc_ext/doda_torch.cpp, `step RB (kind 0)` above namespace coarse): t[0] subm
+    table, t[1:6] bn1, t[6:9] conv1, t[9:14] bn2, t[14:17] conv2, t[17:20] skip conv or None x3, t[20] identity table or None,
+    t[21] that table as the skip's pair lists or None; scalars eps1, momentum1, eps2, momentum2."""
+    data, bn1, cv1, bn2, cv2, sc = operands
+    return ([data.tbl] + bn1 + cv1 + bn2 + cv2 + (sc or [None, None, None, None, None]),
+            [d.bn1.eps, d.bn1.momentum, d.bn2.eps, d.bn2.momentum])
+
+
+def _updown_step(d, operands, down, rows_out):
+    """(tensors, scalars) of an op-list DOWN / UP step (csrc_ext/doda_torch.cpp, `step DOWN (kind 1)` / `step UP (kind 2)`):
+    child and par_off tables (UP: swapped), bn x5, conv x3; scalars eps, momentum, rows of the step's output."""
+    data, bn, cv = operands
+    return (([data.tbl, data.tbl_rev] if down else [data.tbl_rev, data.tbl]) + bn + cv, [d.bn.eps, d.bn.momentum, rows_out])
 
 
 def _subm3(cin, cout, key):
@@ -78,123 +236,54 @@ class ResidualBlock(SparseModule):
             norm_fn(in_channels), nn.ReLU(), _subm3(in_channels, out_channels, indice_key),
             norm_fn(out_channels), nn.ReLU(), _subm3(out_channels, out_channels, indice_key))
 
+    def _description(self):
+        """The block's _Block, or None when it is not the plain block of the reference."""
+        return _described(self, _describe_block)
+
     def forward(self, input):
         # reference: output = conv_branch(input); output.features += i_branch(identity).features
         # (model/unet_block.py:33-37).  Here the add rides in the last convolution's store and, for an
         # identity skip, the skip's gradient in the first BatchNorm's backward kernel.
-        identity = type(self.i_branch[0]) is nn.Identity and len(self.i_branch) == 1
         if FAST_BLOCKS:
-            out = self._forward_one_call(input, identity)
+            out = self._forward_one_call(input)
             if out is not None:
                 return out
-        if identity:
+        if type(self.i_branch[0]) is nn.Identity and len(self.i_branch) == 1:
             return self.conv_branch(input, residual="input")
-        skip = self.i_branch(_shallow(input))
+        skip = self.i_branch(input.header(input.features))
         return self.conv_branch(input, residual=skip.features)
 
-    def _plan(self):
-        """The block's static operands for ext.residual_block — (generation, bn1 list, bn2 list, bn1, bn2, conv1, conv2, the six modules) —
-        or False when the block is not the plain [BN, ReLU, SubM3, BN, ReLU, SubM3] of the reference."""
-        plan = self.__dict__.get("_doda_plan")
-        if plan is not None and (plan is False or plan[0] == _cv._GEN[0]):
-            return plan
-        mods = list(self.conv_branch._modules.values())
-        ok = (len(mods) == 6 and type(mods[0]) is nn.BatchNorm1d and type(mods[1]) is nn.ReLU
-              and type(mods[3]) is nn.BatchNorm1d and type(mods[4]) is nn.ReLU
-              and all(type(m) is spconv.SubMConv3d and m.bias is None and m.kernel_size == [3, 3, 3] and not m.inverse
-                      and m.in_channels % 4 == 0 and m.out_channels % 4 == 0 for m in (mods[2], mods[5]))
-              and mods[2].indice_key is not None and mods[2].indice_key == mods[5].indice_key
-              and all(m.affine and m.track_running_stats and m.momentum is not None and not m._forward_hooks
-                      and not m._forward_pre_hooks for m in (mods[0], mods[3]))
-              and not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks for m in mods))
-        if not ok:
-            plan = False
-        else:
-            def bn_list(bn):
-                return [bn._parameters["weight"], bn._parameters["bias"], bn._buffers["running_mean"],
-                        bn._buffers["running_var"], bn._buffers["num_batches_tracked"]]
-            plan = (_cv._GEN[0], bn_list(mods[0]), bn_list(mods[3]), mods[0], mods[3], mods[2], mods[5], tuple(mods))
-        self.__dict__["_doda_plan"] = plan
-        return plan
-
-    def _forward_one_call(self, input, identity):
+    def _forward_one_call(self, input):
         """The whole block as ONE extension call (csrc_ext residual_block: the same native ops and autograd nodes the
         module-by-module path issues, without the interpreter between them), or None when any precondition of that
         path does not hold — then the modules run one by one as before."""
-        ext = Fsp._ext
-        if ext is None or not Fsp._SERIAL or not hasattr(ext, "residual_block"):
+        ext, d, feats = Fsp._ext, self._description(), input.features
+        # (hooks — feature taps, profilers — must fire: module by module then)
+        if (ext is None or not Fsp._SERIAL or not hasattr(ext, "residual_block") or d is None or not d.per_block or any_hooks(d.modules)
+                or not feats.is_cuda or feats.dim() != 2 or feats.shape[0] < 2 or feats.dtype not in (torch.float32, torch.bfloat16)):
             return None
-        plan = self._plan()
-        if plan is False:
+        training = d.bn1.training
+        # the 1x1 skip convolution (reference model/unet_block.py:18-21) runs inside the extension call, on the first
+        # BatchNorm's pass-through alias of the input: its data gradient is then summed inside that BatchNorm's
+        # backward kernel instead of by an autograd accumulation kernel (SKIP_IN_BLOCK; the input has two consumers)
+        in_call = SKIP_IN_BLOCK and training and d.skip is not None and d.skip.training
+        operands = _block_operands(d, feats, input.indice_dict, feats.shape[0], training, in_call, True)
+        if operands is None:
             return None
-        _, l1, l2, bn1, bn2, c1, c2, all_mods = plan
-        # hooks registered since the plan was made (feature taps, profilers) must fire: module by module then
-        _mod = _torch_module   # (imported at module level: the function-level imports were ~5 us per block and step)
-        if (_mod._global_forward_hooks or _mod._global_forward_pre_hooks or _mod._global_backward_hooks
-                or _mod._global_backward_pre_hooks or self.conv_branch._forward_hooks or self.conv_branch._forward_pre_hooks):
-            return None
-        for m in all_mods:
-            if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
+        data, skip = operands[0], None
+        if not (d.identity or in_call):
+            skip = self.i_branch(input.header(feats)).features
+            if skip.dtype != feats.dtype:
                 return None
-        feats = input.features
-        training = bn1.training
-        if (not feats.is_cuda or feats.dim() != 2 or feats.shape[0] < 2 or feats.dtype not in (torch.float32, torch.bfloat16)
-                or bn2.training != training or c1.training != training or c2.training != training
-                or l1[0] is not bn1._parameters["weight"] or l2[0] is not bn2._parameters["weight"]
-                or l1[2] is not bn1._buffers["running_mean"] or l2[2] is not bn2._buffers["running_mean"]
-                or l1[0].dtype != torch.float32 or l2[0].dtype != torch.float32):
+        p1, p2 = Fsp._lists(data, feats, operands[2][0]), Fsp._lists(data, feats, operands[4][0])
+        if (p1 is None) != (p2 is None):
             return None
-        data = input.find_indice_pair(c1.indice_key)
-        if data is None or data.kind != "subm":
-            return None
-        pk1 = c1._packed(feats, input.indice_dict)
-        pk2 = c2._packed(feats, input.indice_dict)
-        if pk1 is None or pk2 is None:
-            return None
-        skip, sc = None, []
-        if not identity:
-            # the 1x1 skip convolution (reference model/unet_block.py:18-21) runs inside the extension call, on the first
-            # BatchNorm's pass-through alias of the input: its data gradient is then summed inside that BatchNorm's
-            # backward kernel instead of by an autograd accumulation kernel (SKIP_IN_BLOCK; the input has two consumers)
-            sk = self.i_branch[0] if len(self.i_branch) == 1 else None
-            if (SKIP_IN_BLOCK and training and type(sk) is spconv.SubMConv3d and sk.conv1x1 and sk.bias is None
-                    and sk.training and sk.in_channels % 4 == 0 and sk.out_channels % 4 == 0
-                    and sk._parameters["weight"].dtype == torch.float32 and not (sk._forward_hooks or sk._forward_pre_hooks
-                                                                              or sk._backward_hooks or sk._backward_pre_hooks)
-                    and not (self.i_branch._forward_hooks or self.i_branch._forward_pre_hooks)):
-                pks = sk._packed(feats, input.indice_dict)
-                if pks is not None:
-                    from .spconv.conv import _identity_table
-                    ident = _identity_table(feats.shape[0], feats.device)
-                    wsk = sk._parameters["weight"]
-                    sc = [wsk, pks[0], pks[1], ident, ident if Fsp._want_pairs(feats, wsk) else None]
-            if not sc:
-                skip = self.i_branch(_shallow(input)).features
-                if skip.dtype != feats.dtype:
-                    return None
-        n_out = data.outids.shape[0]
-        w1, w2 = c1._parameters["weight"], c2._parameters["weight"]
-        p1, p2 = Fsp._lists(data, feats, w1), Fsp._lists(data, feats, w2)
-        if p1 is not None and p2 is not None:
-            p = p1
-            rb = [data.tbl, p[0], p[1], p[2], p[3] if len(p) > 3 else None]
-        elif p1 is not None or p2 is not None:
-            return None
-        else:
-            rb = [data.tbl, None, None, None, None]
-        st = input.__dict__.get("_doda_stats")
-        stats_in = st[1] if (st is not None and st[0] is feats and st[2] == feats._version) else None
-        stats_in_b = None
-        if isinstance(stats_in, tuple):   # the input is a channel concatenation: statistics rows of its two halves
-            stats_in, stats_in_b = stats_in
-        want_stats = training and Fsp.BN_FUSION and n_out > Fsp.STATS_MIN_ROWS
-        y, stats = ext.residual_block(feats, stats_in, l1, l2, training, bn1.momentum, bn1.eps, bn2.momentum, bn2.eps,
-                                      [w1, pk1[0], pk1[1]], [w2, pk2[0], pk2[1]], rb, n_out, skip, want_stats, sc, stats_in_b)
-        out = spconv.SparseConvTensor(y, data.outids, data.out_spatial_shape, input.batch_size)
-        out.indice_dict = input.indice_dict
-        out.grid = input.grid
+        rb = [data.tbl, None, None, None, None] if p1 is None else [data.tbl, p1[0], p1[1], p1[2], p1[3] if len(p1) > 3 else None]
+        want_stats = training and Fsp.BN_FUSION and data.outids.shape[0] > Fsp.STATS_MIN_ROWS
+        y, stats = ext.residual_block(*_residual_block_args(d, feats, input.stats(), operands, rb, skip, want_stats))
+        out = input.header(y, data.outids, data.out_spatial_shape)
         if stats is not None:
-            out._doda_stats = (y, stats, y._version)
+            out.set_stats(stats)
         return out
 
 
@@ -243,31 +332,8 @@ def choose_coarse_backend(rows, dtype):
 
 
 def _coarse_entry_level():
-    """The level whose UBlock becomes one call: COARSE_EXEC_LEVEL, but not above the levels whose inputs carry tensor hooks (the early
-    gradient exchange at EARLY_LEVEL, the side-stream weight gradients at WGRAD_SIDE_LEVEL: both opt-in)."""
-    lvl = COARSE_EXEC_LEVEL
-    if _early_exchange[0] is not None:
-        lvl = max(lvl, EARLY_LEVEL + 1)
-    if WGRAD_SIDE_LEVEL:
-        lvl = max(lvl, WGRAD_SIDE_LEVEL + 1)
-    return lvl
-
-
-def _bn_list(bn):
-    return [bn._parameters["weight"], bn._parameters["bias"], bn._buffers["running_mean"], bn._buffers["running_var"],
-            bn._buffers["num_batches_tracked"]]
-
-
-def _plain_bn(m):
-    return (type(m) is nn.BatchNorm1d and m.affine and m.track_running_stats and m.momentum is not None
-            and not (m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks)
-            and m._parameters["weight"].dtype == torch.float32)
-
-
-def _plain_conv(m, cls, ksize):
-    return (type(m) is cls and m.bias is None and m.kernel_size == ksize and m._parameters["weight"].dtype == torch.float32
-            and m.in_channels % 16 == 0 and m.out_channels % 16 == 0 and m.in_channels >= 16
-            and not (m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks))
+    """The level whose UBlock becomes one call: COARSE_EXEC_LEVEL, or below the tensor hook at EARLY_LEVEL's input when the exchange is armed."""
+    return COARSE_EXEC_LEVEL if _early_exchange[0] is None else max(COARSE_EXEC_LEVEL, EARLY_LEVEL + 1)
 
 
 # Early gradient exchange (doda_amd.dist.GradAllReduce.arm): a callback fired from a tensor hook when the backward pass has
@@ -283,19 +349,34 @@ def set_early_exchange(fn):
 # Level at which the forward pass turns launch-floor bound (a few thousand rows and fewer): PyramidPrefetcher starts the
 # NEXT batch's rulebook kernels there instead of next to the level-1 convolutions (see PyramidPrefetcher.submit).
 COARSE_LEVEL = 4
-# Weight gradients under the coarse levels (round 5): when the backward pass produces the gradient of level WGRAD_SIDE_LEVEL's
-# OUTPUT — the decoder of every finer level is done, the coarse levels' chain of small kernels starts — the weight gradients
-# queued so far are issued on a second stream (extension: flush_wgrads_side) and run under that chain; the flush at the end of
-# backward joins them.  Measured (tools/side_ab.sh, side_ab2.sh: 4 and 8 scenes, levels 2-5): no change of the step in either
-# regime — the second queue's workgroups do not run under the chain, they delay it —, so 0 = off is the default.
-WGRAD_SIDE_LEVEL = int(_os.environ.get("DODA_WGRAD_SIDE_LEVEL", "0"))
-
-
-def _side_flush_hook(g):
-    if Fsp._ext is not None:
-        Fsp._ext.flush_wgrads_side()
-    return g
 _coarse_hooks = []
+_STEP_KINDS = {"rb": 0, "down": 1, "up": 2}
+
+
+def _walk(ub):
+    steps = [("rb", blk, ub.level) for blk in ub.blocks._modules.values()]
+    if len(ub.nPlanes) > 1:
+        steps += [("down", ub.conv, ub.level)] + _walk(ub.u) + [("up", ub.deconv, ub.level)]
+        steps += [("rb", blk, ub.level) for blk in ub.blocks_tail._modules.values()]
+    return steps
+
+
+def _describe_subtree(ub):
+    """The UBlock subtree as op-list steps — ([("rb", block, level) | ("down", seq, level) | ("up", seq, level)] in execution order,
+    their descriptions, every module and every parameter of the subtree for the per-call sweeps) — or False when a module of it is
+    not the plain reference form (model/unet_block.py:9-37,55-100) or does not meet what the op list asks (_Block, _Triple)."""
+    steps, descs = _walk(ub), []
+    for kind, m, _ in steps:
+        if kind == "rb":
+            d = m._description() if type(m) is ResidualBlock else None
+            good = d is not None and d.op_list
+        else:
+            d = _described(m, _describe_triple)
+            good = d is not None and d.op_list == kind
+        if not good:
+            return False
+        descs.append(d)
+    return steps, descs, list(ub.modules()), list(ub.parameters())
 
 
 class UBlock(nn.Module):
@@ -324,130 +405,60 @@ class UBlock(nn.Module):
 
     # ---- the subtree as executor steps (csrc_ext coarse_ublock) ----
     def _coarse_modules(self):
-        """Static part: [("rb", block) | ("down", seq, level) | ("up", seq, level)] in execution order, or False when a
-        module of the subtree is not the plain reference form (model/unet_block.py:9-37,55-100) or a BatchNorm of it is wider
-        than the op list takes (ops.CX_BN_MAX_C: width 32 carries 320 / 384 / 448 channels at levels 5-7)."""
-        plan = self.__dict__.get("_doda_coarse")
-        if plan is not None:
-            return plan
-        steps, ok = [], [True]
-
-        def walk(ub):
-            for blk in ub.blocks._modules.values():
-                steps.append(("rb", blk, ub.level))
-            if len(ub.nPlanes) > 1:
-                steps.append(("down", ub.conv, ub.level))
-                walk(ub.u)
-                steps.append(("up", ub.deconv, ub.level))
-                for blk in ub.blocks_tail._modules.values():
-                    steps.append(("rb", blk, ub.level))
-
-        walk(self)
-        for kind, m, _ in steps:
-            if kind == "rb":
-                mods = list(m.conv_branch._modules.values()) if type(m) is ResidualBlock else []
-                sk = list(m.i_branch._modules.values()) if type(m) is ResidualBlock else []
-                good = (len(mods) == 6 and _plain_bn(mods[0]) and type(mods[1]) is nn.ReLU and _plain_conv(mods[2], spconv.SubMConv3d, [3, 3, 3])
-                        and _plain_bn(mods[3]) and type(mods[4]) is nn.ReLU and _plain_conv(mods[5], spconv.SubMConv3d, [3, 3, 3])
-                        and mods[2].indice_key == mods[5].indice_key and len(sk) == 1
-                        and (type(sk[0]) is nn.Identity or _plain_conv(sk[0], spconv.SubMConv3d, [1, 1, 1]))
-                        and not (m._forward_hooks or m._forward_pre_hooks or m.conv_branch._forward_hooks or m.i_branch._forward_hooks))
-                good = good and max(mods[0].num_features, mods[3].num_features) <= _ops.CX_BN_MAX_C
-            else:
-                mods = list(m._modules.values())
-                cls = spconv.SparseConv3d if kind == "down" else spconv.SparseInverseConv3d
-                good = (len(mods) == 3 and _plain_bn(mods[0]) and type(mods[1]) is nn.ReLU and _plain_conv(mods[2], cls, [2, 2, 2])
-                        and (kind == "up" or mods[2].stride == [2, 2, 2]) and not (m._forward_hooks or m._forward_pre_hooks)
-                        and mods[0].num_features <= _ops.CX_BN_MAX_C)
-            ok[0] = ok[0] and good
-        plan = self.__dict__["_doda_coarse"] = steps if ok[0] else False
-        return plan
+        """The steps of _describe_subtree, or False."""
+        plan = _described(self, _describe_subtree)
+        return plan and plan[0]
 
     def _forward_coarse(self, input):
         """The whole subtree in one executor call, or None when a precondition fails (then the modules run one by one)."""
         ext = Fsp._ext
         feats = input.features
-        if (ext is None or not Fsp._SERIAL or not hasattr(ext, "coarse_ublock") or not feats.is_cuda
-                or feats.dtype not in (torch.bfloat16, torch.float32) or feats.dim() != 2
-                or _torch_module._global_forward_hooks or _torch_module._global_forward_pre_hooks
-                or _torch_module._global_backward_hooks or _torch_module._global_backward_pre_hooks):
+        if (ext is None or not Fsp._SERIAL or not hasattr(ext, "coarse_ublock") or not feats.is_cuda or feats.dim() != 2
+                or choose_coarse_backend(feats.shape[0], feats.dtype) is None):
             return None
-        backend = choose_coarse_backend(feats.shape[0], feats.dtype)
-        if backend is None:
-            return None
-        plan = self._coarse_modules()
+        plan = _described(self, _describe_subtree)
         if plan is False:
             return None
+        steps, descs, modules, params = plan
         training = self.training
         grad = torch.is_grad_enabled() and feats.requires_grad
-        # per call (the plan is cached): a hook registered on ANY module of the subtree since then (feature taps, profilers) must
-        # fire, and a frozen parameter must not receive a gradient — both mean module by module
-        flat = self.__dict__.get("_doda_coarse_flat")
-        if flat is None:
-            flat = self.__dict__["_doda_coarse_flat"] = (list(self.modules()), list(self.parameters()))
-        for m in flat[0]:
-            if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
-                return None
+        # per call (the plan is cached): a hook on ANY module of the subtree (feature taps, profilers) must fire, and a frozen
+        # parameter must not receive a gradient — both mean module by module
+        if any_hooks(modules):
+            return None
         if grad:
-            for q in flat[1]:
+            for q in params:
                 if not q.requires_grad:
                     return None
-        if grad and not (training and ext.get_defer_wgrad() and ext.get_direct_grads()):
-            return None
+            if not (training and ext.get_defer_wgrad() and ext.get_direct_grads()):
+                return None
         idict = input.indice_dict
         kinds, tensors, scalars = [], [], []
         gate_step = -1          # first step of level COARSE_LEVEL: where the rulebook prefetcher's gate opens (see forward)
         rows = {self.level: feats.shape[0]}
-        for kind, m, lvl in plan:
+        for (kind, _, lvl), d in zip(steps, descs):
             if kind == "rb":
-                mods = list(m.conv_branch._modules.values())
-                bn1, c1, bn2, c2 = mods[0], mods[2], mods[3], mods[5]
-                data = idict.get(c1.indice_key)
-                if (data is None or data.kind != "subm" or data.tbl.shape[1] != rows.get(lvl) or bn1.training != training
-                        or bn2.training != training):
+                operands = _block_operands(d, feats, idict, rows.get(lvl), training, not d.identity, grad)
+                if operands is None:
                     return None
-                pk1, pk2 = c1._packed(feats, idict), c2._packed(feats, idict)
-                if pk1 is None or pk2 is None:
-                    return None
-                sk = m.i_branch[0]
-                if type(sk) is nn.Identity:
-                    skt = [None, None, None, None, None]
-                else:
-                    pks = sk._packed(feats, idict)
-                    if pks is None:
-                        return None
-                    ident = _cv._identity_table(rows[lvl], feats.device)
-                    # (t[21]: the identity table doubles as both pair lists of the skip conv's weight gradient at the large levels)
-                    skt = [sk._parameters["weight"], pks[0], pks[1], ident,
-                           ident if (grad and Fsp._want_pairs(feats, sk._parameters["weight"], rows[lvl])) else None]
-                if kind == "rb" and lvl == COARSE_LEVEL and gate_step < 0:
+                if lvl == COARSE_LEVEL and gate_step < 0:
                     gate_step = len(kinds)
-                kinds.append(0)
-                tensors.append([data.tbl] + _bn_list(bn1) + [c1._parameters["weight"], pk1[0], pk1[1]] + _bn_list(bn2)
-                               + [c2._parameters["weight"], pk2[0], pk2[1]] + skt)
-                scalars.append([bn1.eps, bn1.momentum, bn2.eps, bn2.momentum])
+                step = _block_step(d, operands)
             else:
-                mods = list(m._modules.values())
-                bn, cv = mods[0], mods[2]
-                data = idict.get(cv.indice_key)
-                if data is None or data.kind != "down2" or bn.training != training or data.tbl_rev.shape[1] != rows.get(lvl):
-                    return None
-                pk = cv._packed(feats, idict)
-                if pk is None:
+                operands = _triple_operands(d, feats, idict, rows.get(lvl), training)
+                if operands is None:
                     return None
                 if kind == "down":
-                    rows[lvl + 1] = data.outids.shape[0]
+                    rows[lvl + 1] = operands[0].outids.shape[0]
                     if rows[lvl + 1] < 2:
                         return None
-                    kinds.append(1)
-                    tensors.append([data.tbl, data.tbl_rev] + _bn_list(bn) + [cv._parameters["weight"], pk[0], pk[1]])
-                    scalars.append([bn.eps, bn.momentum, rows[lvl + 1]])
-                else:
-                    kinds.append(2)
-                    tensors.append([data.tbl_rev, data.tbl] + _bn_list(bn) + [cv._parameters["weight"], pk[0], pk[1]])
-                    scalars.append([bn.eps, bn.momentum, rows[lvl]])
-        st = input.__dict__.get("_doda_stats")
-        stats_in = st[1] if (st is not None and st[0] is feats and st[2] == feats._version and torch.is_tensor(st[1])) else None
+                step = _updown_step(d, operands, kind == "down", rows[lvl + 1] if kind == "down" else rows[lvl])
+            kinds.append(_STEP_KINDS[kind])
+            tensors.append(step[0])
+            scalars.append(step[1])
+        stats_in = input.stats()
+        if not torch.is_tensor(stats_in):   # (the op list's first BatchNorm takes one statistics tensor, not a concatenation's pair)
+            stats_in = None
         gate = None
         if self.level < COARSE_LEVEL and gate_step >= 0 and _coarse_hooks and training and torch.is_grad_enabled():
             hooks = list(_coarse_hooks)
@@ -456,11 +467,9 @@ class UBlock(nn.Module):
                 for hook in hooks:
                     hook()
         y, stats = ext.coarse_ublock(feats, stats_in, kinds, tensors, scalars, training, gate_step if gate is not None else -1, gate)
-        out = spconv.SparseConvTensor(y, input.indices, input.spatial_shape, input.batch_size)
-        out.indice_dict = idict
-        out.grid = input.grid
+        out = input.header(y)
         if stats is not None:
-            out._doda_stats = (y, stats, y._version)
+            out.set_stats(stats)
         return out
 
     def forward(self, input):
@@ -479,28 +488,21 @@ class UBlock(nn.Module):
                 return out
         out = self.blocks(input)
         if len(self.nPlanes) > 1:
-            st_a = out.__dict__.get("_doda_stats")
-            src = out.features                        # (what the level's statistics rows belong to)
+            skip_feats, st_a = out.features, out.stats()
             down = self._down_with_skip(out) if SKIP_VIA_BN else None
             if down is not None:
                 skip_feats, down = down
             else:
-                skip_feats = _shallow(out).features
                 down = self.conv(out)                 # (re-binds out.features)
             dec = self.deconv(self.u(down))
+            st_b = dec.stats()
             out.features = torch.cat((skip_feats, dec.features), dim=1)
             # BatchNorm statistics are per channel: the concatenation's are its halves' — the rows the two producing convs
             # accumulated in their epilogues — so the first BatchNorm of blocks_tail needs no sweep over the new tensor
-            st_b = dec.__dict__.get("_doda_stats")
-            out.__dict__.pop("_doda_stats", None)
-            if (CAT_STATS and st_a is not None and st_b is not None and st_a[0] is src and st_a[2] == src._version
-                    and st_b[0] is dec.features and st_b[2] == dec.features._version
-                    and torch.is_tensor(st_a[1]) and torch.is_tensor(st_b[1])):
-                out._doda_stats = (out.features, (st_a[1], st_b[1]), out.features._version)
+            out.clear_stats()
+            if CAT_STATS and torch.is_tensor(st_a) and torch.is_tensor(st_b):   # (a half that is itself a concatenation: no pair of pairs)
+                out.set_stats((st_a, st_b))
             out = self.blocks_tail(out)
-        if (self.level == WGRAD_SIDE_LEVEL and self.training and torch.is_grad_enabled() and out.features.requires_grad
-                and out.features.is_cuda):
-            out.features.register_hook(_side_flush_hook)
         return out
 
     def _down_with_skip(self, out):
@@ -508,25 +510,13 @@ class UBlock(nn.Module):
         out.features for the skip connection, the strided conv's output), or None when the sequence is not that plain
         triple in training mode on the fused path.  The concatenation's gradient for the skip — a column slice of a
         twice as wide matrix — then reaches the BatchNorm's backward kernel as its strided `add` operand."""
-        from . import nn as _dnn
-        from .spconv.modules import _run
-        seq = self.conv
-        mods = list(seq._modules.values())
+        d = _described(self.conv, _describe_triple)
         feats = out.features
-        if (len(mods) != 3 or type(mods[1]) is not nn.ReLU or not isinstance(mods[2], spconv.SparseConvolution)
-                or not mods[0].training or not torch.is_grad_enabled() or not feats.requires_grad
-                or out.indices.shape[0] < 2 or not _dnn.fusable(mods[0], feats) or _dnn._ext is None
-                or seq._forward_hooks or seq._forward_pre_hooks or seq._backward_hooks or seq._backward_pre_hooks
-                or mods[0]._forward_hooks or mods[0]._forward_pre_hooks or mods[0]._backward_hooks
-                or mods[1]._forward_hooks or mods[1]._forward_pre_hooks or mods[1]._backward_hooks):
+        if (d is None or not d.bn.training or not torch.is_grad_enabled() or not feats.requires_grad or out.indices.shape[0] < 2
+                or _dnn._ext is None or not _dnn.fusable(d.bn, feats) or any_hooks(d.modules)):
             return None
-        st = out.__dict__.get("_doda_stats")
-        stats = st[1] if (st is not None and st[0] is feats and st[2] == feats._version) else None
-        y, alias = _dnn.batch_norm_relu(feats, mods[0], True, True, stats)
-        t = spconv.SparseConvTensor(y, out.indices, out.spatial_shape, out.batch_size)
-        t.indice_dict = out.indice_dict
-        t.grid = out.grid
-        return alias, _run(mods[2], t)
+        y, alias = _dnn.batch_norm_relu(feats, d.bn, True, True, out.stats())
+        return alias, _run(d.conv, out.header(y))
 
 
 class _PointLinear(Function):
@@ -652,8 +642,14 @@ def loss_kind_of(cfg):
 
 def criterion_of(model):
     """The point-level criterion(scores, labels, ignore_index) of a (possibly wrapped) network; cross_entropy for one without a choice."""
-    net = model.module if hasattr(model, "module") else model
-    return getattr(net, "criterion", cross_entropy)
+    return getattr(unwrap(model), "criterion", cross_entropy)
+
+
+def matrix_loss(net, scores, labels, ignore_index):
+    """The tail of the matrix path: the network's criterion on the point-level scores, which stay behind for point_predictions."""
+    net.voxel_pred = None                 # (point_predictions: this batch's scores, not an earlier call's voxel argmax)
+    net.point_scores = scores.detach()    # (no reference to the score matrix's graph)
+    return criterion_of(net)(scores, labels, ignore_index)
 
 
 class SparseConvNet(nn.Module):
@@ -662,7 +658,6 @@ class SparseConvNet(nn.Module):
         # the configured loss: the point-level criterion of the matrix path and the voxel-level autograd function of head_loss
         self.loss_kind = loss_kind_of(cfg)
         if self.loss_kind == "lovasz":
-            from .lovasz import _VoxelHeadLovasz, lovasz_softmax
             self.criterion, self.voxel_head = lovasz_softmax, _VoxelHeadLovasz
         else:
             self.criterion, self.voxel_head = cross_entropy, _VoxelHeadCE
@@ -691,8 +686,7 @@ class SparseConvNet(nn.Module):
                 and feats.dtype in (torch.float32, torch.bfloat16) and self.linear.out_features <= 32
                 and self.linear.weight.dtype == torch.float32 and v2p_map is not None and v2p_map.is_cuda
                 and v2p_map.dtype == torch.int32 and v2p_map.dim() == 2 and v2p_map.shape[0] == feats.shape[0]
-                and labels.is_cuda and labels.dtype == torch.int64
-                and not (self.linear._forward_hooks or self.linear._forward_pre_hooks or self.linear._backward_hooks)):
+                and labels.is_cuda and labels.dtype == torch.int64 and not any_hooks((self.linear,))):
             return None
         if self.loss_kind == "lovasz" and not (self.linear.out_features >= 2 and v2p_map.shape[1] - 1 <= _ops.LOVASZ_MAX_POINTS_PER_VOXEL
                                                 and 2 * feats.shape[0] * self.linear.out_features < 2 ** 31):
@@ -704,10 +698,8 @@ class SparseConvNet(nn.Module):
     def _trunk(self, input):
         if input.features.is_cuda and input.indices.shape[0] > 0:
             # all 13 rulebooks up front (+ their pair lists when a bf16 backward pass will follow)
-            spconv.ops.build_pyramid(input, len(self.unet.nPlanes), with_pairs=(
-                spconv.functional.WGRAD_PAIRS and torch.is_grad_enabled() and self.training
-                and input.features.dtype == torch.bfloat16),
-                with_tiles=tile_levels_for(input.features.dtype))   # tilebooks serve inference as well
+            spconv.ops.build_pyramid(input, len(self.unet.nPlanes), with_pairs=_with_pairs(self, input.features.dtype),
+                                     with_tiles=tile_levels_for(input.features.dtype))   # tilebooks serve inference as well
         return self.output_layer(self.unet(self.input_conv(input)))
 
     @torch.no_grad()
@@ -734,21 +726,12 @@ class SparseConvNet(nn.Module):
             v2p_t = v2p_map_t if (v2p_map_t is not None and v2p_map_t.shape == (v2p_map.shape[1] - 1, v2p_map.shape[0])
                                   and v2p_map_t.is_contiguous()) else v2p_map[:, 1:].t().contiguous()
             scores = _PointLinear.apply(feats, self.linear.weight, self.linear.bias, input_map, v2p_t)
-            if labels is not None:
-                self.voxel_pred = None
-                self.point_scores = scores.detach()   # (for point_predictions: no reference to the score matrix's graph)
-                return self.criterion(scores, labels, ignore_index)
-            return scores
-        point_feats = feats[input_map.long()]  # voxel -> point
-        scores = self.linear(point_feats.to(self.linear.weight.dtype))
+        else:
+            point_feats = feats[input_map.long()]  # voxel -> point
+            scores = self.linear(point_feats.to(self.linear.weight.dtype))
         if labels is not None and not return_mid_feat:
-            self.voxel_pred = None
-            self.point_scores = scores.detach()
-            return self.criterion(scores, labels, ignore_index)
+            return matrix_loss(self, scores, labels, ignore_index)
         return (point_feats, scores) if return_mid_feat else scores
-
-
-_PYR_STREAMS = {}
 
 
 F32_TILES = _os.environ.get("DODA_F32_TILES", "0") == "1"
@@ -769,6 +752,41 @@ def tile_levels_for(dtype):
     return 1 if (dtype == torch.float32 and F32_TILES) else 0
 
 
+def _with_pairs(net, dtype):
+    """Do this pass's rulebooks get their pair lists: only when a bf16 backward pass will follow."""
+    return Fsp.WGRAD_PAIRS and torch.is_grad_enabled() and net.training and dtype == torch.bfloat16
+
+
+def _build_pyramid_on(stream, coords, shape, batch_size, n_levels, with_pairs, with_tiles, after=()):
+    """int32 indices and all rulebooks of one batch on `stream`, behind the events `after`.  -> (indices, indice_dict, event that
+    the build has finished); _hand_over gives them to the consuming stream."""
+    with torch.cuda.stream(stream):
+        for event in after:
+            stream.wait_event(event)
+        idx32 = coords.int()
+        probe = spconv.SparseConvTensor(None, idx32, shape, batch_size)
+        spconv.ops.build_pyramid(probe, n_levels, with_pairs=with_pairs, with_tiles=with_tiles)
+        done = torch.cuda.Event()
+        done.record(stream)
+    return idx32, probe.indice_dict, done
+
+
+def _hand_over(idx32, book, done, device):
+    """A pyramid built on a side stream, handed to the current stream: -> (indices int32, indice_dict)."""
+    main = torch.cuda.current_stream(device)
+    main.wait_event(done)
+    idx32.record_stream(main)
+    for data in book.values():
+        for t in vars(data).values():
+            for u in (t if isinstance(t, tuple) else (t,)):
+                if torch.is_tensor(u) and u.is_cuda:
+                    u.record_stream(main)
+    return idx32, book
+
+
+_PYR_STREAMS = {}
+
+
 def _prebuild_pyramid(voxel_coords, spatial_shape, batch_size, n_levels, device, with_pairs=False, with_tiles=None):
     """Build the int32 indices and all rulebooks on a side stream that does NOT wait for the main
     stream.  Rulebooks depend only on the voxel coordinates; built at the head of the forward pass on
@@ -777,23 +795,10 @@ def _prebuild_pyramid(voxel_coords, spatial_shape, batch_size, n_levels, device,
     wall time per step for 0.55 ms of kernels).  Only valid when `voxel_coords` has no producer work
     pending on any stream (a resident batch) — the caller opts in.
     Returns (indices int32, indice_dict); every tensor is handed over to the main stream."""
-    main = torch.cuda.current_stream(device)
     side = _PYR_STREAMS.get(device)
     if side is None:
-        from .streams import independent_stream
         side = _PYR_STREAMS[device] = independent_stream(device, tag="rulebooks")
-    with torch.cuda.stream(side):
-        idx32 = voxel_coords.int()
-        probe = spconv.SparseConvTensor(None, idx32, spatial_shape, batch_size)
-        spconv.ops.build_pyramid(probe, n_levels, with_pairs=with_pairs, with_tiles=with_tiles)
-    main.wait_stream(side)
-    idx32.record_stream(main)
-    for data in probe.indice_dict.values():
-        for t in vars(data).values():
-            for u in (t if isinstance(t, tuple) else (t,)):
-                if torch.is_tensor(u) and u.is_cuda:
-                    u.record_stream(main)
-    return idx32, probe.indice_dict
+    return _hand_over(*_build_pyramid_on(side, voxel_coords, spatial_shape, batch_size, n_levels, with_pairs, with_tiles), device)
 
 
 class PyramidPrefetcher:
@@ -813,11 +818,8 @@ class PyramidPrefetcher:
         levels (COARSE_LEVEL).  Measured: the same step with a re-used pyramid runs at 5.7 ms, with the next pyramid
         built from the start of the step at 6.5 ms — 0.9 ms of rulebook kernels next to the level-1 convolutions cost
         0.8 ms; next to the coarse levels' launch-floor-bound kernels they are nearly free."""
-        import threading
-        from concurrent.futures import ThreadPoolExecutor
         self.device, self.n_levels = device, n_levels
         self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="doda-rulebooks")
-        from .streams import independent_stream
         self.stream = independent_stream(device, tag="rulebooks")   # (not on the main stream's hardware queue)
         self.gated = bool(gated)
         self._gate = None            # (threading.Event, torch.cuda.Event) of the build waiting for this step's coarse phase
@@ -840,7 +842,6 @@ class PyramidPrefetcher:
         current stream that produces it (collate_device returns with doda_voxelize_idx_fill pending) is ordered
         before the build through an event recorded here; resident=True (a batch that was complete before the
         call, e.g. bench.py's reused one) skips that event, so the build does not queue behind the step in flight."""
-        import threading
         coords, shape = batch["voxel_locs"], batch["spatial_shape"]
         bs = batch["offsets"].numel() - 1
         ready = None
@@ -858,11 +859,13 @@ class PyramidPrefetcher:
 
     def _build(self, coords, shape, bs, with_pairs, with_tiles=None, ready=None, gate=None):
         torch.cuda.set_device(self.device)
+        after = []
         if gate is not None:
             # wait (host side) until the main thread has recorded the coarse-phase event of the step in flight; a step
             # that never gets there (evaluation of a shallow model, an exception) must not hold the pipeline: time out
-            opened = gate[0].wait(timeout=0.05)
-            if not opened:
+            if gate[0].wait(timeout=0.05):
+                after.append(gate[1])
+            else:
                 # the step in flight did not reach its coarse levels in time (first iterations, evaluation, a profiler
                 # run): this build goes ungated; the stale gate is withdrawn so that nobody records an event for it, and
                 # the count tells an A/B reader how many of its steps were NOT gated
@@ -870,32 +873,15 @@ class PyramidPrefetcher:
                     if self._gate is gate:
                         self._gate = None
                     self.gate_timeouts += 1
-        with torch.cuda.stream(self.stream):
-            if gate is not None and opened:
-                self.stream.wait_event(gate[1])
-            if ready is not None:
-                self.stream.wait_event(ready)
-                coords.record_stream(self.stream)   # read here; the allocator must not recycle it under the build
-            idx32 = coords.int()
-            probe = spconv.SparseConvTensor(None, idx32, shape, bs)
-            spconv.ops.build_pyramid(probe, self.n_levels, with_pairs=with_pairs, with_tiles=with_tiles)
-            done = torch.cuda.Event()
-            done.record(self.stream)
-        return idx32, probe.indice_dict, done
+        if ready is not None:
+            after.append(ready)
+            coords.record_stream(self.stream)   # read there; the allocator must not recycle it under the build
+        return _build_pyramid_on(self.stream, coords, shape, bs, self.n_levels, with_pairs, with_tiles, after)
 
     @staticmethod
     def take(future, device):
         """(indices int32, indice_dict) of a submitted batch, handed over to the current stream."""
-        idx32, book, done = future.result()
-        main = torch.cuda.current_stream(device)
-        main.wait_event(done)
-        idx32.record_stream(main)
-        for data in book.values():
-            for t in vars(data).values():
-                for u in (t if isinstance(t, tuple) else (t,)):
-                    if torch.is_tensor(u) and u.is_cuda:
-                        u.record_stream(main)
-        return idx32, book
+        return _hand_over(*future.result(), device)
 
     def shutdown(self):
         with self._lock:
@@ -935,7 +921,7 @@ def _input_rows(net, feats, xyz, v2p, mode, feature_dtype):
 def point_predictions(model, p2v):
     """argmax class per POINT after a `labels=` call of voxelize_and_run: the per-voxel argmax of the fused head gathered through
     p2v, or the argmax of the score matrix when the matrix path ran."""
-    net = model.module if hasattr(model, "module") else model
+    net = unwrap(model)
     vp = getattr(net, "voxel_pred", None)
     if vp is not None:
         return vp[p2v.long()].long()
@@ -952,19 +938,16 @@ def voxelize_and_run(cfg, model, batch, device, feature_dtype=torch.float32, fus
     rulebooks may be built on a side stream ahead of the main stream's queue (_prebuild_pyramid).
     pyramid: (indices int32, indice_dict) of this batch from PyramidPrefetcher.take."""
     inp, p2v, v2p = sparse_input(cfg, model, batch, device, feature_dtype, inputs_ready, pyramid)
+    kwargs = {}
     if fused_head:
         v2p_t = batch.get("v2p_map_t")
+        kwargs = dict(v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None)
         if labels is not None:   # -> the LOSS (head + CrossEntropyLoss at voxel level when the fused form applies)
-            return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None,
-                         labels=labels, ignore_index=ignore_index)
-        return model(inp, p2v, v2p_map=v2p, v2p_map_t=v2p_t.to(device, non_blocking=True) if v2p_t is not None else None)
-    if labels is not None:
-        scores = model(inp, p2v)
-        net = model.module if hasattr(model, "module") else model
-        net.voxel_pred = None                 # (point_predictions: this batch's scores, not an earlier call's voxel argmax)
-        net.point_scores = scores.detach()
-        return criterion_of(model)(scores, labels, ignore_index)
-    return model(inp, p2v)
+            kwargs.update(labels=labels, ignore_index=ignore_index)
+    out = model(inp, p2v, **kwargs)
+    if labels is not None and not fused_head:
+        return matrix_loss(unwrap(model), out, labels, ignore_index)
+    return out
 
 
 def sparse_input(cfg, model, batch, device, feature_dtype=torch.float32, inputs_ready=False, pyramid=None):
@@ -976,26 +959,18 @@ def sparse_input(cfg, model, batch, device, feature_dtype=torch.float32, inputs_
     feats = batch["feats"].to(device, non_blocking=True)
     xyz = batch["locs_float"].to(device, non_blocking=True) if cfg.MODEL.BACKBONE.use_xyz else None
     batch_size = batch["offsets"].numel() - 1
-    net = model.module if hasattr(model, "module") else model
+    net = unwrap(model)
     voxel_feats = _input_rows(net, feats, xyz, v2p, cfg.DATA_CONFIG.DATA_PROCESSOR.voxel_mode, feature_dtype)
     if voxel_feats is None:
         if xyz is not None:
             feats = torch.cat((feats, xyz), 1)
         voxel_feats = pointgroup_ops.voxelization(feats, v2p, cfg.DATA_CONFIG.DATA_PROCESSOR.voxel_mode)
-    if pyramid is not None:
-        idx32, book = pyramid
-        inp = spconv.SparseConvTensor(voxel_feats.to(feature_dtype), idx32, batch["spatial_shape"], batch_size)
+    if pyramid is None and (inputs_ready and batch["voxel_locs"].is_cuda and voxel_coords.shape[0] > 0
+                            and hasattr(net, "unet") and device.type == "cuda"):
+        pyramid = _prebuild_pyramid(voxel_coords, batch["spatial_shape"], batch_size, len(net.unet.nPlanes), device,
+                                    with_pairs=_with_pairs(net, feature_dtype), with_tiles=tile_levels_for(feature_dtype))
+    idx32, book = pyramid if pyramid is not None else (voxel_coords.int(), None)
+    inp = spconv.SparseConvTensor(voxel_feats.to(feature_dtype), idx32, batch["spatial_shape"], batch_size)
+    if book is not None:
         inp.indice_dict.update(book)
-    elif (inputs_ready and batch["voxel_locs"].is_cuda and voxel_coords.shape[0] > 0
-            and hasattr(net, "unet") and device.type == "cuda"):
-        idx32, pyramid = _prebuild_pyramid(voxel_coords, batch["spatial_shape"], batch_size,
-                                           len(net.unet.nPlanes), device,
-                                           with_pairs=(spconv.functional.WGRAD_PAIRS and torch.is_grad_enabled()
-                                                       and net.training and feature_dtype == torch.bfloat16),
-                                           with_tiles=tile_levels_for(feature_dtype))
-        inp = spconv.SparseConvTensor(voxel_feats.to(feature_dtype), idx32, batch["spatial_shape"], batch_size)
-        inp.indice_dict.update(pyramid)
-    else:
-        inp = spconv.SparseConvTensor(voxel_feats.to(feature_dtype), voxel_coords.int(),
-                                      batch["spatial_shape"], batch_size)
     return inp, p2v, v2p

@@ -165,10 +165,10 @@ def generate(model, cfg, paths, pseudo_dir, device, rank=0, world=1, feature_dty
     from . import ops
     from .collate import collate_device
     from .dsnorm import set_ds_target
-    from .model import sparse_input
+    from .model import sparse_input, unwrap
     if is_done(pseudo_dir):
         return None
-    net = model.module if hasattr(model, "module") else model
+    net = unwrap(model)
     n_cls = int(net.linear.out_features)
     ignore = int(cfg.DATA_CONFIG.DATA_CLASS.ignore_label)
     st = cfg.SELF_TRAIN

@@ -288,11 +288,9 @@ class SparseConvolution(SparseModule):
             if residual is not None:
                 out_features = out_features + residual
                 stats = None
-            out = SparseConvTensor(out_features, indices, spatial_shape, batch_size)
-            out.indice_dict = input.indice_dict
-            out.grid = input.grid
+            out = input.header(out_features)
             if stats is not None:
-                out._doda_stats = (out_features, stats, out_features._version)
+                out.set_stats(stats)
             return out
 
         weight, packed = self.weight, None
@@ -353,13 +351,9 @@ class SparseConvolution(SparseModule):
         if self.bias is not None:
             out_features = out_features + self.bias.to(out_features.dtype)
             stats = None
-        out = SparseConvTensor(out_features, outids, out_spatial_shape, batch_size)
-        out.indice_dict = input.indice_dict
-        out.grid = input.grid
+        out = input.header(out_features, outids, out_spatial_shape)
         if stats is not None:   # (sum y, sum y^2) partials for a fused BatchNorm applied to exactly these features
-            # (... and to exactly this VERSION of them: `output.features += skip` of the reference's residual
-            # block, model/unet_block.py:36, edits the same tensor object in place)
-            out._doda_stats = (out_features, stats, out_features._version)
+            out.set_stats(stats)
         return out
 
 

@@ -112,6 +112,33 @@ class SparseConvTensor:
         self.indice_dict = IndiceDict()
         self.grid = grid
 
+    def header(self, features, indices=None, spatial_shape=None):
+        """A tensor of the same forward pass over other features (behind a strided layer: other indices and shape) that shares the
+        rulebooks, their weight-pack generation and the grid; also what a branch that must keep the incoming features takes, since
+        SparseSequential re-binds `.features` on the object it is given (reference unet_block.py:33,89)."""
+        out = SparseConvTensor(features, self.indices if indices is None else indices,
+                               self.spatial_shape if spatial_shape is None else spatial_shape, self.batch_size, self.grid)
+        out.indice_dict = self.indice_dict
+        return out
+
+    # BatchNorm statistics partials (sum y, sum y^2) that the producing convolution accumulated in its epilogue.  They belong to one
+    # tensor object AND one version of it: `output.features += skip` (reference model/unet_block.py:36) edits the same object in
+    # place.  (__dict__, not getattr with a default: a missing attribute on this path costs an exception per call.)
+    def stats(self):
+        """The epilogue statistics of the current `.features`: a tensor, the pair of a channel concatenation's halves, or None."""
+        st = self.__dict__.get("_doda_stats")
+        if st is None:
+            return None
+        feats = self.features
+        return st[1] if (st[0] is feats and st[2] == feats._version) else None
+
+    def set_stats(self, stats):
+        feats = self.features
+        self.__dict__["_doda_stats"] = (feats, stats, feats._version)
+
+    def clear_stats(self):
+        self.__dict__.pop("_doda_stats", None)
+
     @property
     def spatial_size(self):
         return int(np.prod(self.spatial_shape))

@@ -20,12 +20,22 @@ def is_spconv_module(module):
     return isinstance(module, SparseModule)
 
 
+def any_hooks(modules):
+    """Does a hook have to fire: one of the four kinds on any of `modules`, or any global module hook?  Everything that
+    bypasses nn.Module.__call__ — _run below, the one-call routes of doda_amd.model — asks here, per call."""
+    if (_mod._global_forward_hooks or _mod._global_forward_pre_hooks or _mod._global_backward_hooks
+            or _mod._global_backward_pre_hooks):
+        return True
+    for m in modules:
+        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
+            return True
+    return False
+
+
 def _run(module, *args, **kwargs):
     """module(*args) without nn.Module.__call__'s hook machinery when the module has no hooks: a
     U-Net step makes ~200 child calls and the step is issue-bound on the host."""
-    if (module._forward_hooks or module._forward_pre_hooks or module._backward_hooks
-            or module._backward_pre_hooks or _mod._global_forward_hooks or _mod._global_forward_pre_hooks
-            or _mod._global_backward_hooks or _mod._global_backward_pre_hooks):
+    if any_hooks((module,)):
         return module(*args, **kwargs)
     return module.forward(*args, **kwargs)
 
@@ -96,11 +106,7 @@ class SparseSequential(SparseModule):
                         # BatchNorm1d [-> ReLU] on .features: one fused HIP path (doda_amd.nn); when the
                         # features came out of a conv that accumulated their statistics, those are used
                         relu = k < len(mods) and type(mods[k]) is nn.ReLU
-                        st = input.__dict__.get("_doda_stats")
-                        # the statistics belong to one tensor object AND one version of it: an in-place edit
-                        # (`output.features += ...`, reference model/unet_block.py:36) keeps the object
-                        feats = input.features
-                        stats = st[1] if (st is not None and st[0] is feats and st[2] == feats._version) else None
+                        stats = input.stats()
                         if take_input and k == 1 and module.training:
                             input.features, residual = _dnn.batch_norm_relu(input.features, module, relu, True, stats)
                         else:

@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from .config import Config, cfg_from_list, cfg_from_yaml_file
+from .model import PyramidPrefetcher, SparseConvNet, point_predictions, tile_levels_for, unwrap, voxelize_and_run
 
 
 # ------------------------------------------------------------------------------------------------ CLI
@@ -175,7 +176,7 @@ def get_git_commit_id():
 
 def save_params(filename, model, optimizer, epoch_log, metric=None):
     """util/model_utils.py:87-94: the reference's checkpoint dictionary, model state on the CPU."""
-    net = model.module if hasattr(model, "module") else model
+    net = unwrap(model)
     state = OrderedDict((k, v.cpu()) for k, v in net.state_dict().items())
     torch.save({"epoch": epoch_log, "state_dict": state, "optimizer": optimizer.state_dict(),
                 "commit_id": get_git_commit_id(), "metric": metric}, filename)
@@ -190,7 +191,7 @@ def get_ckpt(path, to_cpu=True):
 
 def load_params_from_ckpt(path, model, optimizer=None, logger=None):
     ckpt = get_ckpt(path)
-    (model.module if hasattr(model, "module") else model).load_state_dict(ckpt["state_dict"])
+    unwrap(model).load_state_dict(ckpt["state_dict"])
     if optimizer is not None:
         optimizer.load_state_dict(ckpt["optimizer"])
     if logger:
@@ -200,7 +201,7 @@ def load_params_from_ckpt(path, model, optimizer=None, logger=None):
 
 def load_params_from_pretrain(path, model, strict=True, logger=None):
     ckpt = get_ckpt(path)
-    (model.module if hasattr(model, "module") else model).load_state_dict(ckpt["state_dict"], strict=strict)
+    unwrap(model).load_state_dict(ckpt["state_dict"], strict=strict)
     if logger:
         logger("=> loaded pretrained model '%s' (epoch %s)" % (path, ckpt["epoch"]))
     return model
@@ -339,7 +340,6 @@ class Trainer:
     def __init__(self, args, cfg, device, rank=0, world=1, log=print):
         from . import dist as ddist
         from .dsnorm import DSNorm
-        from .model import PyramidPrefetcher, SparseConvNet
         from .spconv import functional as Fsp
         self.args, self.cfg, self.device, self.rank, self.world, self.log = args, cfg, device, rank, world, log
         model = SparseConvNet(cfg)
@@ -362,9 +362,8 @@ class Trainer:
             else:
                 self.model = ddist.wrap_ddp(self.model, device.index)
         self.with_pairs = bool(Fsp.WGRAD_PAIRS and self.fdt == torch.bfloat16)
-        from .model import tile_levels_for
         self.with_tiles = tile_levels_for(self.fdt)
-        net = self.model.module if hasattr(self.model, "module") else self.model
+        net = unwrap(self.model)
         self.n_levels = len(net.unet.nPlanes)
         self.prefetch = PyramidPrefetcher(device, self.n_levels) if device.type == "cuda" else None
         self.iters_done = 0
@@ -387,7 +386,6 @@ class Trainer:
     # one forward + backward of one batch; `domain`: None | "source" | "target" (DSNorm statistics)
     def _pass(self, batch, pyramid, domain, weight=1.0):
         from .dsnorm import set_ds_source, set_ds_target
-        from .model import point_predictions, voxelize_and_run
         if self.cfg.MODEL.get("dsnorm", False) and domain is not None:
             self.model.apply(set_ds_source if domain == "source" else set_ds_target)
         labels = batch["labels"]
@@ -397,7 +395,7 @@ class Trainer:
         (loss * weight if weight != 1.0 else loss).backward()
         # predictions for the meters: the fused head's per-VOXEL argmax with the point -> voxel map (the gather rides in the meters'
         # kernel), or a class per point
-        net = self.model.module if hasattr(self.model, "module") else self.model
+        net = unwrap(self.model)
         vp, p2v = getattr(net, "voxel_pred", None), batch["p2v_map"]
         if vp is not None and p2v.is_cuda and p2v.dtype == torch.int32:
             return loss, (vp, p2v), labels
@@ -500,7 +498,6 @@ class Trainer:
     def _batches(self, epoch, split):
         """(batch, prebuilt rulebooks): worker processes produce the scenes, a feeder thread collates them on the device and
         builds their rulebooks two batches ahead (doda_amd.loader); --inline_loader: everything in this thread, as before."""
-        from .model import PyramidPrefetcher
         if not self.args.inline_loader and self.device.type == "cuda":
             from .loader import DeviceFeeder
             dl, sampler = self._loader(split)

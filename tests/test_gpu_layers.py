@@ -666,9 +666,10 @@ def test_backend_selection():
         M.set_coarse_mode(*old)
 
 
-def test_unet_layers_yield_to_hooks_and_frozen_parameters(native_lib):
+def test_unet_layers_yield_to_hooks_and_frozen_parameters(native_lib, monkeypatch):
     """The one-call subtree must step aside for a forward hook registered on any of its modules (the hook has to fire) and for a
-    frozen parameter (no gradient may be deposited): both fall back to the module-by-module path, per call — the plan is cached."""
+    frozen parameter (no gradient may be deposited): both fall back to the module-by-module path, per call — the plan is cached.
+    A submodule replaced after the plan was made is the one the next one-call step runs and trains."""
     from doda_amd import model as M
     from doda_amd.model import SparseConvNet, cross_entropy, default_cfg, voxelize_and_run
     from doda_amd.scene import make_batch
@@ -691,7 +692,21 @@ def test_unet_layers_yield_to_hooks_and_frozen_parameters(native_lib):
             cross_entropy(voxelize_and_run(cfg, net, bd, d, feature_dtype=torch.bfloat16), bd["labels"]).backward()
             torch.cuda.synchronize()
 
+        one_call = []                                       # what _forward_coarse returned, call by call
+        coarse = M.UBlock._forward_coarse
+        monkeypatch.setattr(M.UBlock, "_forward_coarse", lambda ub, inp: one_call.append(coarse(ub, inp)) or one_call[-1])
         step()                                              # plan made, one call
+        assert one_call[-1] is not None
+        old_bn = net.unet.u.blocks.block0.conv_branch[0]
+        new_bn = torch.nn.BatchNorm1d(old_bn.num_features, eps=1e-4, momentum=0.1).to(d)
+        new_bn.weight.data.fill_(2.0)
+        setattr(net.unet.u.blocks.block0.conv_branch, "0", new_bn)
+        old_bn.weight.grad = old_bn.bias.grad = None         # (no longer the net's: step() does not clear them)
+        step()
+        assert one_call[-1] is not None                     # still one call, over the new module
+        assert new_bn.weight.grad is not None and float(new_bn.weight.grad.abs().sum()) > 0
+        assert int(new_bn.num_batches_tracked) == 1 and int(old_bn.num_batches_tracked) == 1
+        assert old_bn.weight.grad is None and old_bn.bias.grad is None
         seen = []
         deep = net.unet.u.u.blocks.block0
         h = deep.register_forward_hook(lambda m, i, o: seen.append(o.features.shape[0]))

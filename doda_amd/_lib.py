@@ -1,5 +1,5 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h).
+include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h, include/doda_optim.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -191,6 +191,27 @@ SUBSAMPLE_SIGNATURES = {
 SUBSAMPLE_SYMBOLS = tuple(SUBSAMPLE_SIGNATURES)
 SUBSAMPLE_ABI_VERSION = 1  # include/doda_subsample.h DODA_SUBSAMPLE_ABI_VERSION
 SUBSAMPLE_MAX_SEGMENTS, SUBSAMPLE_CHUNK = 64, 1024
+
+# name -> (restype, argtypes); mirrors include/doda_optim.h (the optimizer-step companion ABI, same library)
+class OptimTensor(C.Structure):   # doda_optim_tensor
+    _fields_ = [("p", c_vp), ("g", c_vp), ("state1", c_vp), ("state2", c_vp), ("n", c_i64), ("bias_correction1", c_f64),
+                ("bias_correction2_sqrt", c_f64), ("first_step", c_i32), ("reserved", c_i32)]
+
+
+class OptimHyper(C.Structure):   # doda_optim_hyper
+    _fields_ = [("lr", c_f64), ("beta1", c_f64), ("beta2", c_f64), ("eps", c_f64), ("weight_decay", c_f64), ("nesterov", c_i32),
+                ("maximize", c_i32)]
+
+
+OPTIM_SIGNATURES = {
+    "doda_optim_abi_version": (c_i32, []),
+    "doda_optim_workspace_bytes": (c_sz, [c_i32]),
+    "doda_optim_step": (c_i32, [C.POINTER(OptimTensor), c_i32, c_i32, C.POINTER(OptimHyper), c_f64, c_vp, c_vp, c_sz, c_vp]),
+}
+OPTIM_SYMBOLS = tuple(OPTIM_SIGNATURES)
+OPTIM_ABI_VERSION = 1  # include/doda_optim.h DODA_OPTIM_ABI_VERSION
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
+OPTIM_TILE, OPTIM_NORM_BLOCKS = 2048, 512
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -202,7 +223,8 @@ _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (AUG_SIGNATURES, "doda_aug_abi_version", AUG_ABI_VERSION, "augmentation ABI"),
          (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"),
          (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"),
-         (SUBSAMPLE_SIGNATURES, "doda_subsample_abi_version", SUBSAMPLE_ABI_VERSION, "subsample ABI"))
+         (SUBSAMPLE_SIGNATURES, "doda_subsample_abi_version", SUBSAMPLE_ABI_VERSION, "subsample ABI"),
+         (OPTIM_SIGNATURES, "doda_optim_abi_version", OPTIM_ABI_VERSION, "optimizer ABI"))
 
 _lib = None
 

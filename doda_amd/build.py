@@ -91,7 +91,7 @@ def build_torch_ext(force=False, verbose=True):
         build_native(verbose=verbose)
     stamp_file = EXT_LIB + ".sha1"
     h = hashlib.sha1()
-    for p in (EXT_SRC, os.path.join(HERE, "..", "include", "doda_hip.h")):
+    for p in (EXT_SRC, os.path.join(HERE, "..", "include", "doda_hip.h"), os.path.join(HERE, "..", "include", "doda_optim.h")):
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(torch.__version__.encode())

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/doda_hip.h"
+#include "../../include/doda_optim.h"
 #include <chrono>
 #include <cstdlib>
 
@@ -1839,6 +1840,57 @@ void sgd_step(const std::vector<at::Tensor> &params, const std::vector<at::Tenso
                          maximize ? 1 : 0, desc.data_ptr(), nb, stream_of(params[0])), "doda_sgd_multi");
 }
 
+// ---- optimizer step with the clip folded in: SGD / Adam / AdamW over all parameters (doda_optim_step) --------
+// state1 / state2: momentum buffers (empty list when momentum, passed as beta1, is 0) or exp_avg / exp_avg_sq; bc1 / bc2s: Adam's
+// per-tensor bias corrections; first: SGD's buffer-not-initialised flags; max_norm <= 0: no clip, norm_out untouched.
+void optim_step(int64_t kind, const std::vector<at::Tensor> &params, const std::vector<at::Tensor> &grads,
+                const std::vector<at::Tensor> &state1, const std::vector<at::Tensor> &state2, const std::vector<double> &bc1,
+                const std::vector<double> &bc2s, const std::vector<int64_t> &first, double lr, double beta1, double beta2,
+                double eps, double weight_decay, bool nesterov, bool maximize, double max_norm,
+                const c10::optional<at::Tensor> &norm_out) {
+    const size_t n = params.size();
+    if (n == 0) return;
+    const bool adam = kind != DODA_OPTIM_SGD;
+    const bool need1 = adam || beta1 != 0.0;
+    TORCH_CHECK(kind == DODA_OPTIM_SGD || kind == DODA_OPTIM_ADAM || kind == DODA_OPTIM_ADAMW, "doda optim_step: unknown kind");
+    TORCH_CHECK(grads.size() == n && (!need1 || state1.size() == n) &&
+                (adam ? state2.size() == n && bc1.size() == n && bc2s.size() == n : first.size() == n),
+                "doda optim_step: list lengths differ");
+    std::vector<doda_optim_tensor> t(n);
+    const auto dev = params[0].device();
+    auto like_p = [&](const at::Tensor &x, const at::Tensor &p) {
+        return x.defined() && x.device() == dev && x.scalar_type() == at::kFloat && x.is_contiguous() && x.sizes() == p.sizes();
+    };
+    for (size_t k = 0; k < n; ++k) {
+        const at::Tensor &p = params[k], &g = grads[k];
+        TORCH_CHECK(p.is_cuda() && like_p(p, p) && like_p(g, p),
+                    "doda optim_step: parameters and gradients must be contiguous fp32 tensors on one device");
+        TORCH_CHECK((!need1 || like_p(state1[k], p)) && (!adam || like_p(state2[k], p)), "doda optim_step: bad state buffer");
+        t[k].p = (float *)p.data_ptr();
+        t[k].g = (float *)g.data_ptr();
+        t[k].state1 = need1 ? (float *)state1[k].data_ptr() : nullptr;
+        t[k].state2 = adam ? (float *)state2[k].data_ptr() : nullptr;
+        t[k].n = p.numel();
+        t[k].bias_correction1 = adam ? bc1[k] : 1.0;
+        t[k].bias_correction2_sqrt = adam ? bc2s[k] : 1.0;
+        t[k].first_step = (!adam && first[k]) ? 1 : 0;
+        t[k].reserved = 0;
+    }
+    const bool clip = max_norm > 0.0;
+    float *norm = nullptr;
+    if (clip) {
+        TORCH_CHECK(norm_out.has_value() && norm_out->defined() && norm_out->device() == dev && norm_out->scalar_type() == at::kFloat &&
+                    norm_out->numel() == 1, "doda optim_step: the clip needs an fp32 device scalar for the norm");
+        norm = (float *)norm_out->data_ptr();
+    }
+    const doda_optim_hyper h = {lr, beta1, beta2, eps, weight_decay, nesterov ? 1 : 0, maximize ? 1 : 0};
+    c10::DeviceGuard guard(dev);
+    const size_t nb = doda_optim_workspace_bytes((int32_t)n);
+    at::Tensor ws = pempty({(int64_t)nb}, params[0].options().dtype(at::kByte));
+    check(doda_optim_step(t.data(), (int32_t)n, (int32_t)kind, &h, clip ? max_norm : 0.0, norm, ws.data_ptr(), nb,
+                          stream_of(params[0])), "doda_optim_step");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("indice_conv", &indice_conv, "sparse conv (gather table) with autograd",
           py::arg("features"), py::arg("weight"), py::arg("fwd_tbl"), py::arg("bwd_tbl"), py::arg("n_out"),
@@ -2036,6 +2088,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                   if (p.defined() && p.grad().defined()) const_cast<at::Tensor &>(p).mutable_grad().reset();
           }, "set .grad of every listed parameter to None (203 Python attribute stores per step otherwise)");
     m.def("sgd_step", &sgd_step, "torch.optim.SGD's update of all parameters in one launch",
+          py::call_guard<py::gil_scoped_release>());
+    m.def("optim_step", &optim_step, "SGD / Adam / AdamW update of all parameters in one launch, two with the gradient-norm clip",
           py::call_guard<py::gil_scoped_release>());
     m.def("coarse_ublock", [](const at::Tensor &x, const c10::optional<at::Tensor> &stats_in, const std::vector<int64_t> &kinds,
                               const std::vector<std::vector<c10::optional<at::Tensor>>> &tensors,

@@ -1268,6 +1268,45 @@ def sgd_multi(params, grads, bufs, first, lr, momentum=0.0, dampening=0.0, weigh
                                _stream()), "doda_sgd_multi")
 
 
+def optim_step(kind, params, grads, state1, state2, bc1, bc2s, first, lr, beta1, beta2, eps, weight_decay, nesterov=False,
+               maximize=False, max_norm=0.0, norm_out=None):
+    """One optimizer step over all tensors (doda_optim_step, include/doda_optim.h): kind _lib.OPTIM_SGD / OPTIM_ADAM / OPTIM_ADAMW;
+    state1 / state2: the momentum buffers (entries may be None when the momentum, passed as beta1, is 0) or exp_avg / exp_avg_sq;
+    bc1 / bc2s: Adam's per-tensor bias corrections; first: SGD's buffer-not-initialised flags.  max_norm > 0 clips the global
+    gradient norm first, stores the scaled gradients back and writes the norm to norm_out (fp32 device scalar).  fp32 contiguous
+    device tensors; one launch, two with the clip."""
+    from ._lib import OPTIM_SGD, OptimHyper, OptimTensor
+    n = len(params)
+    if n == 0:
+        return
+    adam = kind != OPTIM_SGD
+    dev = params[0].device
+    arr = (OptimTensor * n)()
+    for k in range(n):
+        p, g = params[k], grads[k]
+        a = state1[k] if state1 else None
+        b = state2[k] if adam else None
+        for t in (p, g, a, b):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or not t.is_cuda or t.shape != p.shape):
+                raise ValueError("optim_step needs contiguous fp32 tensors of the parameter's shape on one HIP device")
+        arr[k].p, arr[k].g = p.data_ptr(), g.data_ptr()
+        arr[k].state1 = a.data_ptr() if a is not None else None
+        arr[k].state2 = b.data_ptr() if b is not None else None
+        arr[k].n = p.numel()
+        if adam:
+            arr[k].bias_correction1, arr[k].bias_correction2_sqrt = bc1[k], bc2s[k]
+        else:
+            arr[k].first_step = int(bool(first[k]))
+    clip = max_norm is not None and max_norm > 0
+    if clip and (norm_out is None or norm_out.dtype != torch.float32 or norm_out.device != dev or norm_out.numel() != 1):
+        raise ValueError("optim_step: the clip needs an fp32 device scalar for the norm")
+    hyper = OptimHyper(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(nesterov)), int(bool(maximize)))
+    nbytes = lib().doda_optim_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().doda_optim_step(arr, n, int(kind), C.byref(hyper), float(max_norm) if clip else 0.0, _p(norm_out) if clip else None,
+                                _p(ws), nbytes, _stream()), "doda_optim_step")
+
+
 # ---- coarse-level op lists (ABI 11, csrc/layers.hip: doda_layers_run) --------------------------------------
 CX_GEMM, CX_BNFWD, CX_BNBWD, CX_STATS = 1, 2, 3, 4
 # widest BatchNorm op the list takes (csrc/bn_totals.hpp BN_TOT_MAX_C = PRE_MAX_C: the LDS channel vectors of lay_bn / bn_apply and

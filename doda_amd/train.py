@@ -143,9 +143,14 @@ def adjust_lr(optim_cfg, optimizer, scheduler, total_epochs, total_iters_per_epo
     raise NotImplementedError(optim_cfg.lr_decay)
 
 
+CLIP_GRAD_NORM = 10   # tool/train.py:100-104
+
+
 def build_optimizer(optim_cfg, model, fused=None):
-    """util/common_utils.py:196-215.  fused: use the fused multi-tensor kernels on the GPU (one launch
-    instead of one per parameter group member; the packed conv weights follow it — doda_amd.spconv.conv)."""
+    """util/common_utils.py:196-215.  fused: on fp32 HIP parameters the optimizers of doda_amd.optim (torch's SGD / Adam / AdamW
+    with the update of all tensors in one native launch; the packed conv weights follow it — doda_amd.spconv.conv), which also
+    take OPTIMIZATION.clip_grad (tool/train.py:100-104: clip_grad_norm_(parameters, 10)) into step(); elsewhere torch's fused
+    multi-tensor kernels.  fused=False and CPU parameters: plain torch optimizers, the clip left to the training loop."""
     params = [p for p in model.parameters() if p.requires_grad]
     kind = optim_cfg.get("optim", "sgd")
     kw = {}
@@ -153,16 +158,24 @@ def build_optimizer(optim_cfg, model, fused=None):
         fused = bool(params) and params[0].is_cuda
     if fused:
         kw["fused"] = True
+    native = fused and all(p.is_cuda and p.dtype == torch.float32 for p in params)
+    clip = {"max_grad_norm": CLIP_GRAD_NORM} if optim_cfg.get("clip_grad", False) else {}
     if kind == "sgd":
-        if fused and all(p.is_cuda and p.dtype == torch.float32 for p in params):
-            from .optim import FusedSGD   # torch.optim.SGD, update of all tensors in one native launch
+        if native:
+            from .optim import FusedSGD
             return FusedSGD(params, lr=optim_cfg.base_lr, momentum=optim_cfg.momentum,
-                            weight_decay=optim_cfg.weight_decay)
+                            weight_decay=optim_cfg.weight_decay, **clip)
         return torch.optim.SGD(params, lr=optim_cfg.base_lr, momentum=optim_cfg.momentum,
                                weight_decay=optim_cfg.weight_decay, **kw)
     if kind == "adam":
+        if native:
+            from .optim import FusedAdam
+            return FusedAdam(params, lr=optim_cfg.base_lr, **clip)
         return torch.optim.Adam(params, lr=optim_cfg.base_lr, **kw)
     if kind == "adamw":
+        if native:
+            from .optim import FusedAdamW
+            return FusedAdamW(params, lr=optim_cfg.base_lr, **clip)
         return torch.optim.AdamW(params, lr=optim_cfg.base_lr, **kw)
     raise NotImplementedError(kind)
 
@@ -571,8 +584,8 @@ class Trainer:
                     self.log("Subsampled batch: source %d points" % labels.shape[0])
             if self.reducer is not None:
                 self.reducer.reduce()
-            if cfg.OPTIMIZATION.get("clip_grad", False):
-                torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=10)
+            if cfg.OPTIMIZATION.get("clip_grad", False) and not getattr(self.optimizer, "clips_in_step", False):
+                torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=CLIP_GRAD_NORM)
             self.optimizer.step()
             meters.update(loss, preds[0], labels, p2v=preds[1])
             self.iters_done += 1

@@ -1,5 +1,5 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h, include/doda_optim.h).
+include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h, include/doda_optim.h, include/doda_pgops.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -212,6 +212,25 @@ OPTIM_SYMBOLS = tuple(OPTIM_SIGNATURES)
 OPTIM_ABI_VERSION = 1  # include/doda_optim.h DODA_OPTIM_ABI_VERSION
 OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
 OPTIM_TILE, OPTIM_NORM_BLOCKS = 2048, 512
+
+# name -> (restype, argtypes); mirrors include/doda_pgops.h (the clustering / segment-pool / proposal-IoU companion ABI, same library)
+_PG_SEG = (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp])
+PGOPS_SIGNATURES = {
+    "doda_pgops_abi_version": (c_i32, []),
+    "doda_pg_components": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "doda_pg_bfs_cluster_h": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32p, c_i32p]),
+    "doda_pg_sec_mean": _PG_SEG,
+    "doda_pg_sec_min": _PG_SEG,
+    "doda_pg_sec_max": _PG_SEG,
+    "doda_pg_roipool_fp": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "doda_pg_sec_mean_bp": _PG_SEG,
+    "doda_pg_roipool_bp": _PG_SEG,
+    "doda_pg_get_iou_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "doda_pg_get_iou": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+}
+PGOPS_SYMBOLS = tuple(PGOPS_SIGNATURES)
+PGOPS_ABI_VERSION = 1  # include/doda_pgops.h DODA_PGOPS_ABI_VERSION
+PG_WAVE_LIST, PG_LONG_SEGMENT, PG_IOU_LDS_INSTANCES = 64, 2048, 8192
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -224,7 +243,8 @@ _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (LOSS_SIGNATURES, "doda_loss_abi_version", LOSS_ABI_VERSION, "loss ABI"),
          (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"),
          (SUBSAMPLE_SIGNATURES, "doda_subsample_abi_version", SUBSAMPLE_ABI_VERSION, "subsample ABI"),
-         (OPTIM_SIGNATURES, "doda_optim_abi_version", OPTIM_ABI_VERSION, "optimizer ABI"))
+         (OPTIM_SIGNATURES, "doda_optim_abi_version", OPTIM_ABI_VERSION, "optimizer ABI"),
+         (PGOPS_SIGNATURES, "doda_pgops_abi_version", PGOPS_ABI_VERSION, "PG_OP ABI"))
 
 _lib = None
 

@@ -1371,3 +1371,133 @@ def set_pre_rows(fwd=None, bwd=None):
     if bwd is not None:
         check(lib().doda_set_option(OPT_PRE_BWD_ROWS, int(bwd)), "doda_set_option")
     return old
+
+
+# ---- the rest of PG_OP: clustering, segment pools, proposal IoU (include/doda_pgops.h, csrc/pgops.hip) -------------------
+def _pg_graph_args(what, semantic_label, ball_query_idxs, start_len, cuda):
+    for t in (semantic_label, ball_query_idxs, start_len):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.is_cuda != cuda:
+            raise RuntimeError("%s: contiguous int32 %s tensors expected" % (what, "device" if cuda else "CPU"))
+    n = semantic_label.numel()
+    if start_len.numel() != 2 * n:
+        raise RuntimeError("%s: start_len must be [N, 2] for N labels" % what)
+    return n, ball_query_idxs.numel()
+
+
+def pg_components(semantic_label, ball_query_idxs, start_len):
+    """(root int32 [N], size int32 [N]): connected components of the ball-query graph restricted to equal semantic labels, edges
+    taken as undirected (doda_pg_components).  root[i] is the smallest point index of i's component, size is the component's point
+    count at roots and 0 elsewhere.  No read-back."""
+    _need_cuda(semantic_label, ball_query_idxs, start_len)
+    n, n_active = _pg_graph_args("pg_components", semantic_label, ball_query_idxs, start_len, True)
+    root = torch.empty(n, dtype=torch.int32, device=semantic_label.device)     # (both written in full by the init launch)
+    size = torch.empty(n, dtype=torch.int32, device=semantic_label.device)
+    check(lib().doda_pg_components(_p(semantic_label), _p(ball_query_idxs), _p(start_len), n, n_active, _p(root), _p(size),
+                                   _stream()), "doda_pg_components")
+    return root, size
+
+
+def pg_cluster(semantic_label, ball_query_idxs, start_len, threshold):
+    """(cluster_idxs int32 [sumNPoint, 2], cluster_offsets int32 [nCluster + 1]) on the device: the components of pg_components
+    with at least `threshold` points, numbered by ascending root — the reference's order, whose seeds ascend and are their
+    component's smallest index —, rows (cluster id, point index).  Inside a cluster the points ascend (the reference lists them in
+    BFS visiting order; no consumer depends on it).  Grouping is torch on the device: a stable sort by root, cumulative sums.  One
+    read-back gives the two output sizes."""
+    root, size = pg_components(semantic_label, ball_query_idxs, start_len)
+    n, dev = root.numel(), root.device
+    if n == 0:
+        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    ar = torch.arange(n, dtype=torch.int32, device=dev)
+    rl = root.long()
+    keep = size[rl] >= int(threshold)
+    kept_root = (root == ar) & keep
+    sum_n, n_cluster = torch.stack((keep.sum(), kept_root.sum())).tolist()          # the one read-back
+    order = torch.sort(torch.where(keep, root, n), stable=True)[1][:sum_n]           # kept points by (root, index)
+    rank = torch.cumsum(kept_root, 0) - 1                                            # cluster number at a kept root
+    cluster_idxs = torch.stack((rank[rl[order]], order), 1).to(torch.int32)
+    roots = torch.sort(torch.where(kept_root, ar, n))[0][:n_cluster].long()          # kept roots ascending
+    cluster_offsets = torch.zeros(n_cluster + 1, dtype=torch.int32, device=dev)
+    cluster_offsets[1:] = torch.cumsum(size[roots], 0)
+    return cluster_idxs.contiguous(), cluster_offsets
+
+
+def pg_bfs_cluster_host(semantic_label, ball_query_idxs, start_len, threshold):
+    """The reference's sequential BFS on CPU tensors (doda_pg_bfs_cluster_h; no GPU touched): the same pair as pg_cluster, clusters
+    and the points inside each in the reference's order."""
+    n, n_active = _pg_graph_args("pg_bfs_cluster_host", semantic_label, ball_query_idxs, start_len, False)
+    idxs = torch.zeros((n, 2), dtype=torch.int32)
+    offsets = torch.zeros(n + 1, dtype=torch.int32)
+    sum_n, n_cluster = C.c_int32(0), C.c_int32(0)
+    check(lib().doda_pg_bfs_cluster_h(_p(semantic_label), _p(ball_query_idxs), _p(start_len), n, n_active, int(threshold), _p(idxs),
+                                      _p(offsets), C.byref(sum_n), C.byref(n_cluster)), "doda_pg_bfs_cluster_h")
+    return idxs[:sum_n.value].clone(), offsets[:n_cluster.value + 1].clone()
+
+
+def _pg_seg_args(what, rows, offsets, seg, n_seg, c, extra=None):
+    """rows: float32 [n_rows, c]; seg: float32 [n_seg, c] (extra: int32 of the same shape); offsets int32 [n_seg + 1]."""
+    ts = (rows, offsets, seg) + (() if extra is None else (extra,))
+    _need_cuda(*ts)
+    n_seg, c = int(n_seg), int(c)
+    ok = (rows.dtype == torch.float32 and seg.dtype == torch.float32 and offsets.dtype == torch.int32
+          and all(t.is_contiguous() for t in ts) and rows.dim() == 2 and rows.shape[1] == c and seg.numel() == n_seg * c
+          and offsets.numel() == n_seg + 1 and (extra is None or (extra.dtype == torch.int32 and extra.numel() == n_seg * c)))
+    if not ok:
+        raise RuntimeError("%s: contiguous float32 [rows, C] / [nProposal, C] and int32 offsets [nProposal + 1] expected" % what)
+    return rows.shape[0], n_seg, c
+
+
+def _pg_pool(name, inp, offsets, out, n_seg, c):
+    n_rows, n_seg, c = _pg_seg_args(name, inp, offsets, out, n_seg, c)
+    check(getattr(lib(), "doda_pg_" + name)(_p(inp), _p(offsets), _p(out), n_rows, n_seg, c, _stream()), "doda_pg_" + name)
+
+
+def sec_mean(inp, offsets, out, n_seg, c):
+    """out[s] = sum over the rows of segment s of inp[row] / float(len) (fp32; 0 for an empty segment)."""
+    _pg_pool("sec_mean", inp, offsets, out, n_seg, c)
+
+
+def sec_min(inp, offsets, out, n_seg, c):
+    """out[s] = column-wise minimum over segment s (+inf for an empty one), bit-exact."""
+    _pg_pool("sec_min", inp, offsets, out, n_seg, c)
+
+
+def sec_max(inp, offsets, out, n_seg, c):
+    """out[s] = column-wise maximum over segment s (-inf for an empty one), bit-exact."""
+    _pg_pool("sec_max", inp, offsets, out, n_seg, c)
+
+
+def sec_mean_bp(d_inp, offsets, d_out, n_seg, c):
+    """d_inp[row] = d_out[s] / float(len) for the rows of every segment; other rows are left as they are."""
+    n_rows, n_seg, c = _pg_seg_args("sec_mean_bp", d_inp, offsets, d_out, n_seg, c)
+    check(lib().doda_pg_sec_mean_bp(_p(d_inp), _p(offsets), _p(d_out), n_rows, n_seg, c, _stream()), "doda_pg_sec_mean_bp")
+
+
+def roipool_fp(feats, offsets, out, maxidx, n_seg, c):
+    """out[s] = column-wise maximum over segment s, maxidx[s] the smallest row that holds it (-inf / -1 where nothing wins)."""
+    n_rows, n_seg, c = _pg_seg_args("roipool_fp", feats, offsets, out, n_seg, c, extra=maxidx)
+    check(lib().doda_pg_roipool_fp(_p(feats), _p(offsets), _p(out), _p(maxidx), n_rows, n_seg, c, _stream()), "doda_pg_roipool_fp")
+
+
+def roipool_bp(d_feats, offsets, maxidx, d_out, n_seg, c):
+    """d_feats[maxidx[s][ch]][ch] += d_out[s][ch]; an argmax outside the rows (-1) is skipped."""
+    n_rows, n_seg, c = _pg_seg_args("roipool_bp", d_feats, offsets, d_out, n_seg, c, extra=maxidx)
+    check(lib().doda_pg_roipool_bp(_p(d_feats), _p(maxidx), _p(d_out), n_rows, n_seg, c, _stream()), "doda_pg_roipool_bp")
+
+
+def get_iou(proposals_idx, proposals_offset, instance_labels, instance_pointnum, proposals_iou, n_instance, n_proposal):
+    """proposals_iou float32 [nProposal, nInstance] = intersection / (proposal + instance - intersection + 1e-5), the reference's
+    expression bit for bit, from one integer histogram per proposal (doda_pg_get_iou)."""
+    ts = (proposals_idx, proposals_offset, instance_labels, instance_pointnum, proposals_iou)
+    _need_cuda(*ts)
+    n_instance, n_proposal = int(n_instance), int(n_proposal)
+    ok = (proposals_idx.dtype == torch.int32 and proposals_offset.dtype == torch.int32 and instance_labels.dtype == torch.int64
+          and instance_pointnum.dtype == torch.int32 and proposals_iou.dtype == torch.float32 and all(t.is_contiguous() for t in ts)
+          and proposals_offset.numel() == n_proposal + 1 and instance_pointnum.numel() == n_instance
+          and proposals_iou.numel() == n_proposal * n_instance)
+    if not ok:
+        raise RuntimeError("get_iou: int32 proposals_idx / proposals_offset [nProposal + 1] / instance_pointnum [nInstance], int64 "
+                           "instance_labels, float32 proposals_iou [nProposal, nInstance], all contiguous")
+    ws = _ws(lib().doda_pg_get_iou_workspace_bytes(n_proposal, n_instance), proposals_idx.device)
+    check(lib().doda_pg_get_iou(_p(proposals_idx), _p(proposals_offset), _p(instance_labels), _p(instance_pointnum),
+                                _p(proposals_iou), instance_labels.numel(), proposals_idx.numel(), n_instance, n_proposal, _p(ws),
+                                ws.numel(), _stream()), "doda_pg_get_iou")

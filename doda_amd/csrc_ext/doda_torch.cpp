@@ -28,11 +28,22 @@
 #include <chrono>
 #include <cstdlib>
 
+// Switches read from the environment, once each.  A flag that defaults to off is on for a value starting with '1'; one that
+// defaults to on is off for a value starting with '0'.
+static inline bool env_flag(const char *name, bool dflt) {
+    const char *e = getenv(name);
+    return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
+}
+static inline long long env_int(const char *name, long long dflt) {
+    const char *e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+
 // Debug aid (DODA_POISON=1): every tensor this file allocates uninitialised is filled with 0xFF bytes (NaN for fp32 / bf16 /
 // fp64, -1 for int32) right after the allocation, on the current stream.  A kernel that reads something it (or a predecessor) did
 // not write then yields NaN instead of whatever the caching allocator left there — the stale values that make such a read an
 // intermittent, plausible-looking error (tools/traindet.py, tools/stepdet.py).
-static const bool g_poison = [] { const char *e = getenv("DODA_POISON"); return e && e[0] == '1'; }();
+static const bool g_poison = env_flag("DODA_POISON", false);
 static inline at::Tensor poisoned(at::Tensor t) {
     if (g_poison && t.defined() && t.is_cuda() && t.numel() > 0)
         (void)hipMemsetAsync(t.data_ptr(), 0xFF, (size_t)t.numel() * t.element_size(), c10::hip::getCurrentHIPStream(t.device().index()).stream());
@@ -43,12 +54,12 @@ static inline at::Tensor pempty(at::IntArrayRef sizes, const at::TensorOptions &
 template <class... A> static inline at::Tensor pempty_like(A &&...a) { return poisoned(at::empty_like(std::forward<A>(a)...)); }
 // Debug aid (DODA_NANCHECK=1, with DODA_POISON=1): after every operator of this file its outputs are searched for NaN (a
 // synchronisation each: slow) and the first hit is reported with the operator and its shapes — where a poisoned byte was read.
-static const bool g_nancheck = [] { const char *e = getenv("DODA_NANCHECK"); return e && e[0] == '1'; }();
+static const bool g_nancheck = env_flag("DODA_NANCHECK", false);
 static int g_nan_reports = 0;
 // Debug aid (DODA_FPLOG=1): a fingerprint (int64 sum of the raw 32-bit words) of every operator output, in call order;
 // fp_log_take() hands the list over and clears it.  Two passes over the same inputs must log the same list: the first entry that
 // differs names the operator whose output changed (tools/fwddet.py).
-static const bool g_fplog = [] { const char *e = getenv("DODA_FPLOG"); return e && e[0] == '1'; }();
+static const bool g_fplog = env_flag("DODA_FPLOG", false);
 static std::vector<std::tuple<std::string, int64_t>> g_fp;
 static std::mutex g_fp_mu;
 static inline void fp_log(const at::Tensor &t, const char *what, const char *which, long long a, long long b, long long c) {
@@ -83,7 +94,7 @@ namespace host_timing {
 struct Slot { const char *name; long long ns = 0, calls = 0; };
 static Slot g_slots[] = {{"residual_block"}, {"conv_backward"}, {"bn_backward"}, {"flush_wgrads"}, {"wgrad_multi (library)"},
                          {"coarse_backward"}, {"coarse_forward"}};
-static const bool g_on = getenv("DODA_HOST_TIMING") && getenv("DODA_HOST_TIMING")[0] == '1';
+static const bool g_on = env_flag("DODA_HOST_TIMING", false);
 struct Scope {
     int k;
     std::chrono::steady_clock::time_point t0;
@@ -97,9 +108,6 @@ struct Scope {
 }  // namespace host_timing
 
 namespace {
-
-using torch::autograd::AutogradContext;
-using torch::autograd::tensor_list;
 
 inline void *stream_of(const at::Tensor &t) {
     return (void *)c10::hip::getCurrentHIPStream(t.device().index()).stream();
@@ -161,7 +169,7 @@ void build_tilebook(const at::Tensor &tbl, void *st) {
 // pass instead of one per conv): a slice per statistics-producing call, forward and backward.  A slice is handed out once:
 // the arena only grows, and a full one is replaced by a fresh zeroed buffer (one 8 MB memset every two or three steps; slices still
 // referenced keep the old storage alive).
-bool g_stats_totals = [] { const char *e = getenv("DODA_STATS_TOTALS"); return !(e && e[0] == '0'); }();
+bool g_stats_totals = env_flag("DODA_STATS_TOTALS", true);
 constexpr int64_t TOT_ARENA_DOUBLES = 1024 * 1024;     // 8 MB: 64 x nc doubles per slice (512 slices of 32 channels)
 std::mutex g_tot_mu;
 at::Tensor g_tot_buf;
@@ -294,20 +302,17 @@ inline bool pairs_usable(const at::Tensor &a, const at::Tensor &b, const PairLis
            a.size(1) % 16 == 0 && b.size(1) % 16 == 0;
 }
 
-at::Tensor wgrad(const at::Tensor &a_in, const at::Tensor &b_in, const at::Tensor &tbl, int64_t n_rows,
-                 const PairLists &pl = PairLists()) {
-    const at::Tensor a = a_in.contiguous(), b = b_in.contiguous();
-    TORCH_CHECK(a.scalar_type() == b.scalar_type(), "doda wgrad: dtype mismatch");
-    const int esz = elem_bytes(a);
-    const int64_t K = tbl.size(0), ld = tbl.size(1), ca = a.size(1), cb = b.size(1);
-    at::Tensor dw = pempty({K, ca, cb}, a.options().dtype(at::kFloat));
-    // one job of the multi-layer entry point (ABI 7: the only weight-gradient entry point); the library picks the
-    // kernel: LDS-staged over the tilebook, pair lists, or the gather table
+// One job of the multi-layer entry point (ABI 7: the only weight-gradient entry point): dw (+)= a^T b over the table; the library
+// picks the kernel: LDS-staged over the tilebook (SubM rulebooks of the fine levels carry one behind the table), pair lists, or
+// the gather table.  a, b: contiguous.
+doda_wgrad_job wgrad_job(const at::Tensor &a, const at::Tensor &b, const at::Tensor &tbl, int64_t n_rows, const PairLists &pl,
+                         const at::Tensor &dw, int flags) {
     doda_wgrad_job j;
     memset(&j, 0, sizeof(j));
     j.a = a.data_ptr(); j.b = b.data_ptr(); j.tbl = (const int32_t *)tbl.data_ptr(); j.dw = (float *)dw.data_ptr();
-    j.ca = (int32_t)ca; j.cb = (int32_t)cb; j.ld = (int32_t)ld; j.K = (int32_t)K; j.n_rows = (int32_t)n_rows;
-    j.elem_bytes = esz; j.n_a = (int32_t)a.size(0);
+    j.ca = (int32_t)a.size(1); j.cb = (int32_t)b.size(1); j.ld = (int32_t)tbl.size(1); j.K = (int32_t)tbl.size(0);
+    j.n_rows = (int32_t)n_rows; j.elem_bytes = (int32_t)elem_bytes(a); j.n_a = (int32_t)a.size(0);
+    j.flags = flags;
     j.tilebook = tilebook_behind(tbl, n_rows);
     if (pairs_usable(a, b, pl)) {
         j.pair_in = (const int32_t *)pl.in.data_ptr();
@@ -317,6 +322,15 @@ at::Tensor wgrad(const at::Tensor &a_in, const at::Tensor &b_in, const at::Tenso
         j.pair_seg = pl.seg.defined() ? (const int32_t *)pl.seg.data_ptr() : nullptr;
         j.pair_seg_nt = pl.seg.defined() ? (int32_t)pl.seg.size(1) : 0;
     }
+    return j;
+}
+
+at::Tensor wgrad(const at::Tensor &a_in, const at::Tensor &b_in, const at::Tensor &tbl, int64_t n_rows,
+                 const PairLists &pl = PairLists()) {
+    const at::Tensor a = a_in.contiguous(), b = b_in.contiguous();
+    TORCH_CHECK(a.scalar_type() == b.scalar_type(), "doda wgrad: dtype mismatch");
+    at::Tensor dw = pempty({tbl.size(0), a.size(1), b.size(1)}, a.options().dtype(at::kFloat));
+    const doda_wgrad_job j = wgrad_job(a, b, tbl, n_rows, pl, dw, 0);
     const size_t wsb = doda_spconv_wgrad_multi_workspace_bytes(&j, 1), dsb = doda_spconv_wgrad_multi_desc_bytes(1);
     at::Tensor ws = pempty({(int64_t)wsb}, a.options().dtype(at::kByte));
     at::Tensor desc = pempty({(int64_t)dsb}, a.options().dtype(at::kByte));
@@ -342,31 +356,43 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> export_pairs(const at::Tensor &tb
     return {pairs, num, ws.narrow(0, 0, K * nt).view({K, nt})};
 }
 
+// An event made on first use.  It belongs to the device it was created on (recording a foreign-device event on a stream fails):
+// on(dev) creates it under that device's guard and replaces it when the device differs from last time's.
+struct DeviceEvent {
+    hipEvent_t ev = nullptr;
+    int dev = -1;
+    const unsigned flags;
+    explicit DeviceEvent(unsigned flags_) : flags(flags_) {}
+    hipEvent_t on(int d) {
+        if (!ev || dev != d) {
+            if (ev) (void)hipEventDestroy(ev);
+            ev = nullptr;
+            c10::hip::HIPGuard dev_guard((c10::DeviceIndex)d);
+            TORCH_CHECK(hipEventCreateWithFlags(&ev, flags) == hipSuccess, "doda: hipEventCreate");
+            dev = d;
+        }
+        return ev;
+    }
+};
+
 // One int32 from the device to the host WITHOUT a spinning wait: copy into pinned memory, then sleep on an event created
 // with hipEventBlockingSync.  Tensor::item() waits in hipStreamSynchronize, which spins by default: the rulebook thread
 // makes six such waits per step (~1.5 ms of a core) next to the issuing thread, which is what paces the step on a busy
 // host.  DODA_SPIN_READBACK=1 restores item().
 bool read_back_blocking(const void *dev_ptr, int32_t *out, int n, void *st, int dev) {   // n <= 16; st: a stream of device `dev`; false: the caller spins
-    static const bool spin = getenv("DODA_SPIN_READBACK") && getenv("DODA_SPIN_READBACK")[0] == '1';
+    static const bool spin = env_flag("DODA_SPIN_READBACK", false);
     if (spin) return false;
-    struct Slot { int32_t *host = nullptr; hipEvent_t ev = nullptr; int dev = -1; };
-    static thread_local Slot slot;
-    // the event belongs to the device it was created on: a thread that later builds a pyramid on another device gets a
-    // new one under that device's guard (recording a foreign-device event on the stream fails); the pinned buffer is shared
-    const int cur = dev;
+    // (a thread that later builds a pyramid on another device gets a new event; the pinned buffer is shared)
+    static thread_local int32_t *host = nullptr;
+    static thread_local DeviceEvent done(hipEventBlockingSync | hipEventDisableTiming);
     c10::hip::HIPGuard dev_guard((c10::DeviceIndex)dev);
-    if (!slot.host)
-        TORCH_CHECK(hipHostMalloc((void **)&slot.host, 64, hipHostMallocDefault) == hipSuccess, "doda: hipHostMalloc");
-    if (!slot.ev || slot.dev != cur) {
-        if (slot.ev) (void)hipEventDestroy(slot.ev);
-        slot.ev = nullptr;
-        TORCH_CHECK(hipEventCreateWithFlags(&slot.ev, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess, "doda: hipEventCreate");
-        slot.dev = cur;
-    }
-    TORCH_CHECK(hipMemcpyAsync(slot.host, dev_ptr, (size_t)n * 4, hipMemcpyDeviceToHost, (hipStream_t)st) == hipSuccess, "doda: hipMemcpyAsync");
-    TORCH_CHECK(hipEventRecord(slot.ev, (hipStream_t)st) == hipSuccess, "doda: hipEventRecord");
-    TORCH_CHECK(hipEventSynchronize(slot.ev) == hipSuccess, "doda: hipEventSynchronize");
-    for (int k = 0; k < n; ++k) out[k] = slot.host[k];
+    if (!host)
+        TORCH_CHECK(hipHostMalloc((void **)&host, 64, hipHostMallocDefault) == hipSuccess, "doda: hipHostMalloc");
+    hipEvent_t ev = done.on(dev);
+    TORCH_CHECK(hipMemcpyAsync(host, dev_ptr, (size_t)n * 4, hipMemcpyDeviceToHost, (hipStream_t)st) == hipSuccess, "doda: hipMemcpyAsync");
+    TORCH_CHECK(hipEventRecord(ev, (hipStream_t)st) == hipSuccess, "doda: hipEventRecord");
+    TORCH_CHECK(hipEventSynchronize(ev) == hipSuccess, "doda: hipEventSynchronize");
+    for (int k = 0; k < n; ++k) out[k] = host[k];
     return true;
 }
 int32_t read_back_i32(const at::Tensor &t, void *st) {
@@ -396,8 +422,7 @@ std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vecto
         {   // room for the direct-address grid behind it (doda_hip.h: grids of <= 2^28 cells; larger ones keep the hash)
             const long double cells = (long double)batch * shape[0] * shape[1] * shape[2];
             static const long long grid_max = [] {      // (csrc/rulebook.hip GRID_MAX_CELLS: the same switch)
-                const char *e = getenv("DODA_RULEBOOK_GRID_MAX_LOG2");
-                const int b = e ? atoi(e) : 28;
+                const long long b = env_int("DODA_RULEBOOK_GRID_MAX_LOG2", 28);
                 return 1ll << (b < 0 ? 0 : b > 30 ? 30 : b);
             }();
             if (m > 0 && cells > 0 && cells <= (long double)grid_max) wsb = (wsb + 255) / 256 * 256 + (size_t)cells * 4;
@@ -443,7 +468,7 @@ std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vecto
         // tile weight gradient, the only consumers left were the six k2 s2 / inverse layers of levels 1-3, and the export (three
         // launches per rulebook on the rulebook stream, 230 us per step) cost four times what the pair-list kernels saved over
         // the gather-table kernel (54 us): 5.2-5.6 -> 5.0 ms per step in alternating runs (tools/pairs_ab.sh).
-        static const bool down_pairs = [] { const char *e = getenv("DODA_WGRAD_PAIRS_DOWN"); return e && e[0] == '1'; }();
+        static const bool down_pairs = env_flag("DODA_WGRAD_PAIRS_DOWN", false);
         if (with_pairs && down_pairs) std::tie(dp, dn, dh) = export_pairs(par_off, m, false, st);
         std::vector<int64_t> oshape = {(shape[0] - 2) / 2 + 1, (shape[1] - 2) / 2 + 1, (shape[2] - 2) / 2 + 1};
         at::Tensor outids = out_idx.narrow(0, 0, m_out);
@@ -536,9 +561,43 @@ struct PendingWgrad {
     PairLists pl;
     int64_t n_rows;
 };
-std::mutex g_wq_mu;
-std::vector<PendingWgrad> g_wq;
-bool g_wq_callback = false, g_defer_wgrad = false;
+// The deferred queue, its split flush (flush_wgrads, flush_wgrads_early) and its side flush (flush_wgrads_side).
+// Under `mu`: pending, callback, task, stream — conv nodes queue from the engine's threads while a flush takes the jobs.  Unlocked:
+// everything else — touched only by the flush entry points and wait_wide_wgrads / set_wgrad_split, which a training step runs
+// strictly one after the other (hooks of the backward pass, its final callback, then the reducer on the issuing thread).
+struct WgradQueue {
+    typedef c10::optional<c10::hip::HIPStream> Stream;
+    std::mutex mu;
+    std::vector<PendingWgrad> pending;
+    bool callback = false;        // flush_wgrads is registered with the engine for graph task `task`
+    int task = -2;
+    Stream stream;                // the backward pass's stream (of the last job queued)
+    bool split = false;           // set_wgrad_split: wide layers first, `early` recorded behind them
+    DeviceEvent early{hipEventDisableTiming};
+    bool early_valid = false;
+    Stream side_stream, side_main;
+    DeviceEvent fork{hipEventDisableTiming}, join{hipEventDisableTiming};
+    std::vector<PendingWgrad> side_keep;
+    bool side_pending = false;
+
+    // the jobs queued so far and the stream they belong to; `final`: the backward pass is over
+    std::vector<PendingWgrad> take(Stream &st, bool final = false) {
+        std::vector<PendingWgrad> q;
+        std::lock_guard<std::mutex> lock(mu);
+        q.swap(pending);
+        st = stream;
+        if (final) {
+            callback = false;
+            task = -2;
+        }
+        return q;
+    }
+    void record_early(const c10::hip::HIPStream &st) {
+        TORCH_CHECK(hipEventRecord(early.on((int)st.device_index()), st.stream()) == hipSuccess, "doda: hipEventRecord");
+        early_valid = true;
+    }
+} g_wq;
+bool g_defer_wgrad = false;
 // (set_direct_grads, with set_defer_wgrad) parameter gradients of the extension's own nodes are written to .grad by the
 // nodes themselves — conv weights by the deferred launch, BatchNorm gamma / beta by the BatchNorm backward — and the nodes keep
 // NO autograd edge to those leaves: the engine then has 203 AccumulateGrad nodes less to schedule per U-Net step (~0.5 ms of
@@ -570,8 +629,6 @@ inline void deposit_grad(const at::Tensor &param, const at::Tensor &g) {
         slot.add_(g.reshape(slot.sizes()));
     }
 }
-int g_wq_task = -2;
-c10::optional<c10::hip::HIPStream> g_wq_stream;
 
 void issue_wgrads(std::vector<PendingWgrad> &q, const c10::hip::HIPStream &st) {
     if (q.empty()) return;
@@ -591,26 +648,7 @@ void issue_wgrads(std::vector<PendingWgrad> &q, const c10::hip::HIPStream &st) {
             if (!target.defined()) target = pempty(p.weight.sizes(), p.weight.options());
             fresh[k] = target;
         }
-        doda_wgrad_job j;
-        memset(&j, 0, sizeof(j));
-        j.a = p.a.data_ptr(); j.b = p.b.data_ptr();
-        j.tbl = (const int32_t *)p.tbl.data_ptr();
-        j.dw = (float *)target.data_ptr();
-        j.ca = (int32_t)p.a.size(1); j.cb = (int32_t)p.b.size(1);
-        j.ld = (int32_t)p.tbl.size(1); j.K = (int32_t)p.tbl.size(0);
-        j.n_rows = (int32_t)p.n_rows; j.elem_bytes = (int32_t)elem_bytes(p.a);
-        j.n_a = (int32_t)p.a.size(0);
-        j.flags = flags;
-        j.tilebook = tilebook_behind(p.tbl, p.n_rows);   // SubM rulebooks of the fine levels carry one behind the table
-        if (pairs_usable(p.a, p.b, p.pl)) {
-            j.pair_in = (const int32_t *)p.pl.in.data_ptr();
-            j.pair_out = (const int32_t *)p.pl.out.data_ptr();
-            j.pair_num = p.pl.num.defined() ? (const int32_t *)p.pl.num.data_ptr() : nullptr;
-            j.pair_seg = p.pl.seg.defined() ? (const int32_t *)p.pl.seg.data_ptr() : nullptr;
-            j.pair_seg_nt = p.pl.seg.defined() ? (int32_t)p.pl.seg.size(1) : 0;
-            j.pair_ld = (int32_t)p.pl.ld();
-        }
-        jobs[k] = j;
+        jobs[k] = wgrad_job(p.a, p.b, p.tbl, p.n_rows, p.pl, target, flags);
     }
     const auto opt = q[0].a.options().dtype(at::kByte);
     const size_t wsb = doda_spconv_wgrad_multi_workspace_bytes(jobs.data(), (int32_t)jobs.size());
@@ -651,10 +689,6 @@ void issue_in_rounds(std::vector<PendingWgrad> &q, const c10::hip::HIPStream &st
 // recorded behind them: the all-reduce of their gradients (and of everything AccumulateGrad delivered during
 // backward) can start on another stream while the narrow layers' kernels still run.  The rule is static
 // (channel counts of the weight), so every rank cuts its gradients the same way whatever its batch looks like.
-bool g_wq_split = false, g_ev_early_valid = false;
-hipEvent_t g_ev_early = nullptr;
-int g_ev_early_dev = -1;   // device the event lives on (one training process drives one device; re-made if that changes)
-
 inline bool narrow_weight(const at::Tensor &w) {   // [kD, kH, kW, Cin, Cout]
     return w.dim() == 5 && w.size(3) <= 32 && w.size(4) <= 32;
 }
@@ -664,88 +698,53 @@ inline bool narrow_weight(const at::Tensor &w) {   // [kD, kH, kW, Cin, Cout]
 // pass's stream, and run under the coarse levels' chain of launch-floor kernels (few rows: most CUs idle).  The backward
 // pass's stream waits for them in flush_wgrads(), before it issues the rest; the queued tensors are kept until then (the
 // caching allocator would otherwise hand their memory to the main stream while the side stream still reads it).
-std::vector<PendingWgrad> g_side_keep;
-c10::optional<c10::hip::HIPStream> g_side_stream, g_side_main;
-hipEvent_t g_ev_fork = nullptr, g_ev_join = nullptr;
-int g_ev_side_dev = -1;
-bool g_side_pending = false;
-
 int64_t flush_wgrads_side() {
-    std::vector<PendingWgrad> q;
-    c10::optional<c10::hip::HIPStream> st;
-    {
-        std::lock_guard<std::mutex> lock(g_wq_mu);
-        q.swap(g_wq);
-        st = g_wq_stream;
-    }
+    WgradQueue &Q = g_wq;
+    WgradQueue::Stream st;
+    std::vector<PendingWgrad> q = Q.take(st);
     if (q.empty() || !st) return 0;
     host_timing::Scope host_scope(3);
     const int dev = (int)st->device_index();
     c10::hip::HIPGuard dev_guard(dev);
-    if (g_ev_side_dev != dev) {
-        if (g_ev_fork) hipEventDestroy(g_ev_fork);
-        if (g_ev_join) hipEventDestroy(g_ev_join);
-        TORCH_CHECK(hipEventCreateWithFlags(&g_ev_fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&g_ev_join, hipEventDisableTiming) == hipSuccess, "doda: hipEventCreate");
-        g_ev_side_dev = dev;
-        g_side_stream = c10::hip::getStreamFromPool(false, (c10::DeviceIndex)dev);
-    }
+    if (!Q.side_stream || (int)Q.side_stream->device_index() != dev) Q.side_stream = c10::hip::getStreamFromPool(false, (c10::DeviceIndex)dev);
+    const hipEvent_t fork = Q.fork.on(dev), join = Q.join.on(dev);
     const int64_t n = (int64_t)q.size();
-    std::vector<PendingWgrad> keep(q);   // (references: issue_in_rounds consumes its argument)
-    if (g_side_pending) {                // a second side flush in one backward pass: it runs behind the first
-        g_side_keep.insert(g_side_keep.end(), keep.begin(), keep.end());
-    } else {
-        g_side_keep.swap(keep);
-    }
-    TORCH_CHECK(hipEventRecord(g_ev_fork, st->stream()) == hipSuccess &&
-                hipStreamWaitEvent(g_side_stream->stream(), g_ev_fork, 0) == hipSuccess, "doda: side flush fork");
-    issue_in_rounds(q, *g_side_stream);
-    TORCH_CHECK(hipEventRecord(g_ev_join, g_side_stream->stream()) == hipSuccess, "doda: side flush join event");
-    g_side_main = st;
-    g_side_pending = true;
+    // (references: issue_in_rounds consumes its argument.  side_keep is empty unless a side flush is pending: a second one in the
+    // same backward pass runs behind the first and adds to it)
+    Q.side_keep.insert(Q.side_keep.end(), q.begin(), q.end());
+    TORCH_CHECK(hipEventRecord(fork, st->stream()) == hipSuccess &&
+                hipStreamWaitEvent(Q.side_stream->stream(), fork, 0) == hipSuccess, "doda: side flush fork");
+    issue_in_rounds(q, *Q.side_stream);
+    TORCH_CHECK(hipEventRecord(join, Q.side_stream->stream()) == hipSuccess, "doda: side flush join event");
+    Q.side_main = st;
+    Q.side_pending = true;
     return n;
 }
 // the backward pass's stream waits for the side flush; true when there was one
-bool join_side_wgrads(const c10::optional<c10::hip::HIPStream> &st) {
-    if (!g_side_pending) return false;
-    const c10::hip::HIPStream &main = st ? *st : *g_side_main;
-    TORCH_CHECK(hipStreamWaitEvent(main.stream(), g_ev_join, 0) == hipSuccess, "doda: side flush join");
-    g_side_pending = false;
-    g_side_keep.clear();   // (freed memory is re-used on `main`, behind the wait)
+bool join_side_wgrads(const WgradQueue::Stream &st) {
+    WgradQueue &Q = g_wq;
+    if (!Q.side_pending) return false;
+    const c10::hip::HIPStream &main = st ? *st : *Q.side_main;
+    TORCH_CHECK(hipStreamWaitEvent(main.stream(), Q.join.ev, 0) == hipSuccess, "doda: side flush join");
+    Q.side_pending = false;
+    Q.side_keep.clear();   // (freed memory is re-used on `main`, behind the wait)
     return true;
 }
 
 void flush_wgrads() {
     host_timing::Scope host_scope(3);
-    std::vector<PendingWgrad> q;
-    c10::optional<c10::hip::HIPStream> st;
-    {
-        std::lock_guard<std::mutex> lock(g_wq_mu);
-        q.swap(g_wq);
-        st = g_wq_stream;
-        g_wq_callback = false;
-        g_wq_task = -2;
-    }
+    WgradQueue::Stream st;
+    std::vector<PendingWgrad> q = g_wq.take(st, true);
     join_side_wgrads(st);
     if (q.empty() || !st) return;   // nothing queued (or no backward pass has run yet: no stream recorded)
-    if (!g_wq_split) {
+    if (!g_wq.split) {
         issue_in_rounds(q, *st);
         return;
     }
     std::vector<PendingWgrad> wide, narrow;
     for (PendingWgrad &p : q) (narrow_weight(p.weight) ? narrow : wide).push_back(std::move(p));
     issue_in_rounds(wide, *st);
-    if (g_ev_early && g_ev_early_dev != (int)st->device_index()) {
-        hipEventDestroy(g_ev_early);
-        g_ev_early = nullptr;
-    }
-    if (!g_ev_early) {
-        c10::hip::HIPGuard dev_guard(st->device_index());
-        TORCH_CHECK(hipEventCreateWithFlags(&g_ev_early, hipEventDisableTiming) == hipSuccess, "doda: hipEventCreate");
-        g_ev_early_dev = (int)st->device_index();
-    }
-    TORCH_CHECK(hipEventRecord(g_ev_early, st->stream()) == hipSuccess, "doda: hipEventRecord");
-    g_ev_early_valid = true;
+    g_wq.record_early(*st);
     issue_in_rounds(narrow, *st);
 }
 
@@ -754,28 +753,13 @@ void flush_wgrads() {
 // and record the event the reducer's side stream waits for.  The engine callback stays registered: jobs queued afterwards
 // (the encoder of levels 1-2) are issued by the ordinary flush when backward ends.  Returns the number of jobs issued.
 int64_t flush_wgrads_early() {
-    std::vector<PendingWgrad> q;
-    c10::optional<c10::hip::HIPStream> st;
-    {
-        std::lock_guard<std::mutex> lock(g_wq_mu);
-        q.swap(g_wq);
-        st = g_wq_stream;
-    }
+    WgradQueue::Stream st;
+    std::vector<PendingWgrad> q = g_wq.take(st);
     if (q.empty() || !st) return 0;
     const int64_t n = (int64_t)q.size();
     join_side_wgrads(st);
     issue_in_rounds(q, *st);
-    if (g_ev_early && g_ev_early_dev != (int)st->device_index()) {
-        hipEventDestroy(g_ev_early);
-        g_ev_early = nullptr;
-    }
-    if (!g_ev_early) {
-        c10::hip::HIPGuard dev_guard(st->device_index());
-        TORCH_CHECK(hipEventCreateWithFlags(&g_ev_early, hipEventDisableTiming) == hipSuccess, "doda: hipEventCreate");
-        g_ev_early_dev = (int)st->device_index();
-    }
-    TORCH_CHECK(hipEventRecord(g_ev_early, st->stream()) == hipSuccess, "doda: hipEventRecord");
-    g_ev_early_valid = true;
+    g_wq.record_early(*st);
     return n;
 }
 
@@ -787,16 +771,17 @@ bool try_defer_wgrad(const at::Tensor &features, const at::Tensor &dy, const at:
         return false;
     const int task = torch::autograd::get_current_graph_task_id();
     if (task < 0) return false;   // not inside an engine run (e.g. a functional call of the node)
-    std::lock_guard<std::mutex> lock(g_wq_mu);
-    if (g_wq_task != task) {      // leftovers of a backward pass that never completed
-        g_wq.clear();
-        g_wq_callback = false;
-        g_wq_task = task;
+    WgradQueue &Q = g_wq;
+    std::lock_guard<std::mutex> lock(Q.mu);
+    if (Q.task != task) {      // leftovers of a backward pass that never completed
+        Q.pending.clear();
+        Q.callback = false;
+        Q.task = task;
     }
-    g_wq.push_back(PendingWgrad{features.contiguous(), dy, tbl, weight, pl, n_rows});
-    g_wq_stream = c10::hip::getCurrentHIPStream(dy.device().index());
-    if (!g_wq_callback) {
-        g_wq_callback = true;
+    Q.pending.push_back(PendingWgrad{features.contiguous(), dy, tbl, weight, pl, n_rows});
+    Q.stream = c10::hip::getCurrentHIPStream(dy.device().index());
+    if (!Q.callback) {
+        Q.callback = true;
         torch::autograd::Engine::get_default_engine().queue_callback([]() { flush_wgrads(); });
     }
     return true;
@@ -836,7 +821,7 @@ thread_local std::shared_ptr<BNLink> g_last_bn;
 bool g_bn_fusion = true;
 // below: the one-launch BatchNorm kernels (csrc/bn.hip bn_small_*) instead of conv-epilogue statistics (DODA_STATS_MIN_ROWS, also
 // read by spconv/functional.py: the two thresholds move together)
-const int64_t BN_SMALL_ROWS = [] { const char *e = getenv("DODA_STATS_MIN_ROWS"); return e ? (int64_t)atoll(e) : (int64_t)4096; }();
+const int64_t BN_SMALL_ROWS = env_int("DODA_STATS_MIN_ROWS", 4096);
 
 // features, weight [k,k,k,Cin,Cout], fwd_tbl, bwd_tbl, n_out, bwd_layout, packed fwd / data-grad,
 // optional residual (y = conv + residual; its gradient is the incoming gradient itself).
@@ -983,6 +968,25 @@ at::Tensor add_operand(const at::Tensor &e, int64_t m, int64_t c, int64_t &ld) {
     return e.contiguous();
 }
 
+// How BatchNorm statistics reached a backward op: not at all (or in neither form below), as fp32 rows [rows, 2, c] of a conv
+// epilogue, or as fp64 totals (is_totals).
+enum class StatsKind { None, Rows, Totals };
+inline StatsKind stats_kind(const at::Tensor &st, int64_t c) {
+    if (!st.defined()) return StatsKind::None;
+    if (is_totals(st, c)) return StatsKind::Totals;
+    return st.scalar_type() == at::kFloat ? StatsKind::Rows : StatsKind::None;
+}
+// The kernel of a BatchNorm backward: final + apply over statistics from the consuming conv's data-grad epilogue (Totals: up to
+// 256 channels; Rows), its own statistics pass with (Add) or without (Plain) the pass-through gradient summed into dx, or torch
+// ops over the running statistics (Eval).  extra_fits: there is a pass-through gradient and it has the dtype of x.
+enum class BNBwd { Totals, Rows, Add, Plain, Eval };
+inline BNBwd bn_bwd_route(StatsKind stats, bool c_le_256, bool training, bool extra_fits) {
+    if (stats == StatsKind::Totals && c_le_256) return BNBwd::Totals;
+    if (stats == StatsKind::Rows) return BNBwd::Rows;
+    if (!training) return BNBwd::Eval;
+    return extra_fits ? BNBwd::Add : BNBwd::Plain;
+}
+
 // ---- fused BatchNorm1d(+ReLU).  Gradient edges: 0 x, 1 weight, 2 bias. ----------------------------
 // With `passthrough` the op has a second output: an alias of x whose gradient (the skip connection of a
 // pre-activation residual block) is summed into dx by the apply pass (doda_bn_relu_bwd_add) instead of
@@ -1024,73 +1028,57 @@ struct BNNode : public torch::autograd::Node {
             link->stats.reset();
             link->dz.reset();
         }
-        if (stats.defined() && is_totals(stats, x.size(1)) && x.size(1) <= 256) {
-            const int64_t m = x.size(0), c = x.size(1);
-            int64_t add_ld = c;
-            const at::Tensor add = extra.defined() ? add_operand(extra, m, c, add_ld) : at::Tensor();
+        const int64_t m = x.size(0), c = x.size(1);
+        const BNBwd route = bn_bwd_route(stats_kind(stats, c), c <= 256, training, extra.defined() && extra.scalar_type() == x.scalar_type());
+        int64_t add_ld = c;
+        at::Tensor add;   // the second gradient, where the route's kernel sums it into dx
+        if (route != BNBwd::Eval) {
+            if (extra.defined() && route != BNBwd::Plain) {
+                add = add_operand(extra, m, c, add_ld);
+                extra = at::Tensor();
+            }
             dx = pempty_like(x);
             dg = grad_out(weight, c);
             db = grad_out(bias, c);
-            check(doda_bn_relu_bwd_totals(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, elem_bytes(x), (const double *)stats.data_ptr(),
-                                          (const float *)mean.data_ptr(), (const float *)invstd.data_ptr(),
-                                          (const float *)weight.data_ptr(), (const float *)bias.data_ptr(), relu ? 1 : 0,
-                                          add.defined() ? add.data_ptr() : nullptr, (int)add_ld, dx.data_ptr(),
-                                          (float *)dg.data_ptr(), (float *)db.data_ptr(), stream_of(x)),
-                  "doda_bn_relu_bwd_totals");
-            extra = at::Tensor();
-        } else if (stats.defined() && stats.scalar_type() == at::kFloat) {
-            const int64_t m = x.size(0), c = x.size(1);
-            int64_t add_ld = c;
-            const at::Tensor add = extra.defined() ? add_operand(extra, m, c, add_ld) : at::Tensor();
-            dx = pempty_like(x);
-            dg = grad_out(weight, c);
-            db = grad_out(bias, c);
+        }
+        const int esz = elem_bytes(x), rl = relu ? 1 : 0;
+        const float *mp = (const float *)mean.data_ptr(), *ip = (const float *)invstd.data_ptr();
+        const float *gp = (const float *)weight.data_ptr(), *bp = (const float *)bias.data_ptr();
+        const void *addp = add.defined() ? add.data_ptr() : nullptr;
+        float *dgp = dg.defined() ? (float *)dg.data_ptr() : nullptr, *dbp = db.defined() ? (float *)db.data_ptr() : nullptr;
+        switch (route) {
+        case BNBwd::Totals:
+            check(doda_bn_relu_bwd_totals(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, esz, (const double *)stats.data_ptr(), mp, ip, gp, bp, rl,
+                                          addp, (int)add_ld, dx.data_ptr(), dgp, dbp, stream_of(x)), "doda_bn_relu_bwd_totals");
+            break;
+        case BNBwd::Rows: {
             at::Tensor coef = pempty({3 * c}, x.options().dtype(at::kFloat));
-            check(doda_bn_relu_bwd_stats(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, elem_bytes(x),
-                                            (const float *)stats.data_ptr(), (int)stats.size(0),
-                                            (const float *)mean.data_ptr(), (const float *)invstd.data_ptr(),
-                                            (const float *)weight.data_ptr(), (const float *)bias.data_ptr(), relu ? 1 : 0,
-                                            add.defined() ? add.data_ptr() : nullptr, (int)add_ld, dx.data_ptr(),
-                                            (float *)dg.data_ptr(), (float *)db.data_ptr(), (float *)coef.data_ptr(),
-                                            stream_of(x)),
+            check(doda_bn_relu_bwd_stats(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, esz, (const float *)stats.data_ptr(), (int)stats.size(0),
+                                         mp, ip, gp, bp, rl, addp, (int)add_ld, dx.data_ptr(), dgp, dbp, (float *)coef.data_ptr(), stream_of(x)),
                   "doda_bn_relu_bwd_stats");
-            extra = at::Tensor();
-        } else if (training && extra.defined() && extra.scalar_type() == x.scalar_type()) {
-            const int64_t m = x.size(0), c = x.size(1);
-            int64_t add_ld = c;
-            const at::Tensor add = add_operand(extra, m, c, add_ld);
-            dx = pempty_like(x);
-            dg = grad_out(weight, c);
-            db = grad_out(bias, c);
+            break;
+        }
+        case BNBwd::Add:
+        case BNBwd::Plain: {
             const size_t wsb = doda_bn_workspace_bytes((int)m, (int)c);
             at::Tensor ws = pempty({(int64_t)wsb}, x.options().dtype(at::kByte));
-            check(doda_bn_relu_bwd_add(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, elem_bytes(x),
-                                          (const float *)mean.data_ptr(), (const float *)invstd.data_ptr(),
-                                          (const float *)weight.data_ptr(), (const float *)bias.data_ptr(),
-                                          relu ? 1 : 0, add.data_ptr(), (int)add_ld, dx.data_ptr(), (float *)dg.data_ptr(),
-                                          (float *)db.data_ptr(), ws.data_ptr(), wsb, stream_of(x)),
-                  "doda_bn_relu_bwd_add");
-            extra = at::Tensor();
-        } else if (training) {
-            const int64_t m = x.size(0), c = x.size(1);
-            dx = pempty_like(x);
-            dg = grad_out(weight, c);
-            db = grad_out(bias, c);
-            const size_t wsb = doda_bn_workspace_bytes((int)m, (int)c);
-            at::Tensor ws = pempty({(int64_t)wsb}, x.options().dtype(at::kByte));
-            check(doda_bn_relu_bwd(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, elem_bytes(x),
-                                   (const float *)mean.data_ptr(), (const float *)invstd.data_ptr(),
-                                   (const float *)weight.data_ptr(), (const float *)bias.data_ptr(), relu ? 1 : 0,
-                                   dx.data_ptr(), (float *)dg.data_ptr(), (float *)db.data_ptr(), ws.data_ptr(), wsb,
-                                   stream_of(x)),
-                  "doda_bn_relu_bwd");
-        } else {  // running statistics are constants
+            if (route == BNBwd::Add)
+                check(doda_bn_relu_bwd_add(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, esz, mp, ip, gp, bp, rl, addp, (int)add_ld, dx.data_ptr(),
+                                           dgp, dbp, ws.data_ptr(), wsb, stream_of(x)), "doda_bn_relu_bwd_add");
+            else
+                check(doda_bn_relu_bwd(x.data_ptr(), dy.data_ptr(), (int)m, (int)c, esz, mp, ip, gp, bp, rl, dx.data_ptr(), dgp, dbp,
+                                       ws.data_ptr(), wsb, stream_of(x)), "doda_bn_relu_bwd");
+            break;
+        }
+        case BNBwd::Eval: {   // running statistics are constants
             at::Tensor xh = (x.to(at::kFloat) - mean) * invstd;
             at::Tensor dz = dy.to(at::kFloat);
             if (relu) dz = dz * ((xh * weight + bias) > 0);
             dx = (dz * (weight * invstd)).to(x.scalar_type());
             dg = (dz * xh).sum(0);
             db = dz.sum(0);
+            break;
+        }
         }
         if (extra.defined()) dx = dx + extra;
         if (g_nancheck || g_fplog) {
@@ -1122,6 +1110,26 @@ struct BNNode : public torch::autograd::Node {
     std::string name() const override { return "DodaBNReLUBackward"; }
 };
 
+// The kernel of a BatchNorm forward over m rows of c channels: statistics from the epilogues of the producing convs — fp64 totals
+// (Totals; of both halves when x is a concatenation), fp32 rows of the two halves of a concatenation (CatRows) or of x (Rows) —
+// or the op's own statistics pass / the running statistics (Plain: also every tensor of at most DODA_STATS_MIN_ROWS rows).
+enum class BNFwd { Totals, CatRows, Rows, Plain };
+inline BNFwd bn_fwd_route(bool training, int64_t m, int64_t c, const at::Tensor &stats, const at::Tensor &stats_b) {
+    if (training && m > BN_SMALL_ROWS && c <= 256 && stats.defined() && stats.scalar_type() == at::kDouble &&
+        (stats_b.defined() ? (stats.dim() == 4 && stats_b.dim() == 4 && is_totals(stats, stats.size(2) * 4) &&
+                              is_totals(stats_b, c - stats.size(2) * 4) && stats.size(2) > 0 && stats.size(2) * 4 < c)
+                           : is_totals(stats, c)))
+        return BNFwd::Totals;
+    if (training && stats.defined() && stats_b.defined() && m > BN_SMALL_ROWS && stats.dim() == 3 &&
+        stats_b.dim() == 3 && stats.size(2) + stats_b.size(2) == c && stats.scalar_type() == at::kFloat &&
+        stats_b.scalar_type() == at::kFloat && stats.is_contiguous() && stats_b.is_contiguous() && stats.size(2) % 4 == 0)
+        return BNFwd::CatRows;
+    if (training && stats.defined() && m > BN_SMALL_ROWS && stats.dim() == 3 && stats.size(2) == c &&
+        stats.scalar_type() == at::kFloat && stats.is_contiguous())
+        return BNFwd::Rows;
+    return BNFwd::Plain;
+}
+
 // stats: (sum x, sum x^2) partials of x from the epilogue of the conv that produced it, or undefined
 std::vector<at::Tensor> bn_relu_impl(const at::Tensor &x_in, const at::Tensor &weight, const at::Tensor &bias,
                                      const at::Tensor &running_mean, const at::Tensor &running_var,
@@ -1145,58 +1153,45 @@ std::vector<at::Tensor> bn_relu_impl(const at::Tensor &x_in, const at::Tensor &w
             mean = running_mean.to(at::kFloat).contiguous();
             invstd = at::rsqrt(running_var.to(at::kFloat) + eps).contiguous();
         }
-        if (training && m > BN_SMALL_ROWS && c <= 256 && stats.defined() && stats.scalar_type() == at::kDouble &&
-            (stats_b.defined() ? (stats.dim() == 4 && stats_b.dim() == 4 && is_totals(stats, stats.size(2) * 4) &&
-                                  is_totals(stats_b, c - stats.size(2) * 4) && stats.size(2) > 0 && stats.size(2) * 4 < c)
-                               : is_totals(stats, c))) {
-            // ABI 9: statistics as totals — ONE launch, also for a channel concatenation [a | b] (two producers)
+        const float *gp = (const float *)weight.data_ptr(), *bp = (const float *)bias.data_ptr();
+        float *mp = (float *)mean.data_ptr(), *ip = (float *)invstd.data_ptr();
+        float *rmp = (float *)running_mean.data_ptr(), *rvp = (float *)running_var.data_ptr();
+        int64_t *nbtp = nbt.defined() ? (int64_t *)nbt.data_ptr() : nullptr;
+        const int rl = relu ? 1 : 0;
+        switch (bn_fwd_route(training, m, c, stats, stats_b)) {
+        case BNFwd::Totals:   // ABI 9: ONE launch, also for a channel concatenation [a | b] (two producers)
             check(doda_bn_relu_fwd_totals(x.data_ptr(), (int)m, (int)c, esz, (const double *)stats.data_ptr(),
                                           stats_b.defined() ? (const double *)stats_b.data_ptr() : nullptr, (int)stats.size(2) * 4,
-                                          (float)eps, (float)momentum, (const float *)weight.data_ptr(),
-                                          (const float *)bias.data_ptr(), (float *)running_mean.data_ptr(),
-                                          (float *)running_var.data_ptr(), nbt.defined() ? (int64_t *)nbt.data_ptr() : nullptr,
-                                          relu ? 1 : 0, y.data_ptr(), (float *)mean.data_ptr(), (float *)invstd.data_ptr(),
-                                          stream_of(x)),
+                                          (float)eps, (float)momentum, gp, bp, rmp, rvp, nbtp, rl, y.data_ptr(), mp, ip, stream_of(x)),
                   "doda_bn_relu_fwd_totals");
-        } else if (training && stats.defined() && stats_b.defined() && m > BN_SMALL_ROWS && stats.dim() == 3 &&
-            stats_b.dim() == 3 && stats.size(2) + stats_b.size(2) == c && stats.scalar_type() == at::kFloat &&
-            stats_b.scalar_type() == at::kFloat && stats.is_contiguous() && stats_b.is_contiguous() && stats.size(2) % 4 == 0) {
+            break;
+        case BNFwd::CatRows: {
             // x is a channel concatenation [a | b] (the U-Net level's skip + upsampled features): BatchNorm statistics are
             // per channel, so the two halves' statistics rows — from the epilogues of the two convs that produced them —
             // are reduced separately into the halves of the per-channel vectors, and one apply pass follows: the
             // standalone statistics sweep over the concatenated tensor is gone
             const int64_t ca = stats.size(2), cb = stats_b.size(2);
-            float *mp = (float *)mean.data_ptr(), *ip = (float *)invstd.data_ptr();
-            float *rmp = (float *)running_mean.data_ptr(), *rvp = (float *)running_var.data_ptr();
             check(doda_bn_fwd_final((const float *)stats.data_ptr(), (int)stats.size(0), (int)m, (int)ca, (float)eps,
-                                    (float)momentum, rmp, rvp, nbt.defined() ? (int64_t *)nbt.data_ptr() : nullptr, mp, ip,
-                                    stream_of(x)), "doda_bn_fwd_final");
+                                    (float)momentum, rmp, rvp, nbtp, mp, ip, stream_of(x)), "doda_bn_fwd_final");
             check(doda_bn_fwd_final((const float *)stats_b.data_ptr(), (int)stats_b.size(0), (int)m, (int)cb, (float)eps,
                                     (float)momentum, rmp + ca, rvp + ca, nullptr, mp + ca, ip + ca, stream_of(x)),
                   "doda_bn_fwd_final");
-            check(doda_bn_relu_apply(x.data_ptr(), (int)m, (int)c, esz, mp, ip, (const float *)weight.data_ptr(),
-                                     (const float *)bias.data_ptr(), relu ? 1 : 0, y.data_ptr(), stream_of(x)),
-                  "doda_bn_relu_apply");
-        } else if (training && stats.defined() && m > BN_SMALL_ROWS && stats.dim() == 3 && stats.size(2) == c &&
-            stats.scalar_type() == at::kFloat && stats.is_contiguous()) {
-            check(doda_bn_relu_fwd_stats(x.data_ptr(), (int)m, (int)c, esz, (const float *)stats.data_ptr(),
-                                         (int)stats.size(0), (float)eps, (float)momentum,
-                                         (const float *)weight.data_ptr(), (const float *)bias.data_ptr(),
-                                         (float *)running_mean.data_ptr(), (float *)running_var.data_ptr(),
-                                         nbt.defined() ? (int64_t *)nbt.data_ptr() : nullptr, relu ? 1 : 0, y.data_ptr(),
-                                         (float *)mean.data_ptr(), (float *)invstd.data_ptr(), stream_of(x)),
+            check(doda_bn_relu_apply(x.data_ptr(), (int)m, (int)c, esz, mp, ip, gp, bp, rl, y.data_ptr(), stream_of(x)), "doda_bn_relu_apply");
+            break;
+        }
+        case BNFwd::Rows:
+            check(doda_bn_relu_fwd_stats(x.data_ptr(), (int)m, (int)c, esz, (const float *)stats.data_ptr(), (int)stats.size(0), (float)eps,
+                                         (float)momentum, gp, bp, rmp, rvp, nbtp, rl, y.data_ptr(), mp, ip, stream_of(x)),
                   "doda_bn_relu_fwd_stats");
-        } else {
-        const size_t wsb = doda_bn_workspace_bytes((int)m, (int)c);
-        at::Tensor ws = pempty({(int64_t)wsb}, x.options().dtype(at::kByte));
-        check(doda_bn_relu_fwd(x.data_ptr(), (int)m, (int)c, esz, (float)eps, (float)momentum,
-                               (const float *)weight.data_ptr(), (const float *)bias.data_ptr(),
-                               training ? (float *)running_mean.data_ptr() : nullptr,
-                               training ? (float *)running_var.data_ptr() : nullptr,
-                               training && nbt.defined() ? (int64_t *)nbt.data_ptr() : nullptr, training ? 1 : 0,
-                               relu ? 1 : 0, y.data_ptr(), (float *)mean.data_ptr(), (float *)invstd.data_ptr(),
-                               ws.data_ptr(), wsb, stream_of(x)),
-              "doda_bn_relu_fwd");
+            break;
+        case BNFwd::Plain: {
+            const size_t wsb = doda_bn_workspace_bytes((int)m, (int)c);
+            at::Tensor ws = pempty({(int64_t)wsb}, x.options().dtype(at::kByte));
+            check(doda_bn_relu_fwd(x.data_ptr(), (int)m, (int)c, esz, (float)eps, (float)momentum, gp, bp, training ? rmp : nullptr,
+                                   training ? rvp : nullptr, training ? nbtp : nullptr, training ? 1 : 0, rl, y.data_ptr(), mp, ip,
+                                   ws.data_ptr(), wsb, stream_of(x)), "doda_bn_relu_fwd");
+            break;
+        }
         }
         if (g_nancheck || g_fplog) {
             nan_check(x, "bn forward", "INPUT x", x.size(0), x.size(1));
@@ -1319,6 +1314,11 @@ std::vector<at::Tensor> residual_block(const at::Tensor &x, const c10::optional<
 // bn x5 = gamma, beta, running_mean, running_var, num_batches_tracked; conv x3 = weight, packed forward, packed data-grad.
 namespace coarse {
 
+// positions in the tensor lists above (doda_amd/model.py _block_step, _updown_step)
+enum { RB_TABLE = 0, RB_BN1 = 1, RB_CONV1 = 6, RB_BN2 = 9, RB_CONV2 = 14, RB_SKIP = 17, RB_IDENT = 20,
+       RB_SKIP_PAIRS = 21 /* the identity table again when it also serves as the skip's pair lists; may be absent */, RB_TENSORS = 22 };
+enum { UD_FWD_TABLE = 0, UD_BWD_TABLE = 1, UD_BN = 2, UD_CONV = 7, UD_TENSORS = 10 };
+
 typedef std::vector<c10::optional<at::Tensor>> TList;
 
 struct Arena {   // device scratch that is never handed out as a tensor: a few chunks instead of a hundred allocations
@@ -1400,6 +1400,9 @@ struct Builder {
     bool first = true;
     int esz = 2;
     std::vector<at::Tensor> tot_keep;   // totals slices of this pass (zeroed arena of stats_totals_take)
+    // every tensor an op points at stays alive until the launch is queued (a freed block could be handed out again by the next
+    // at::empty of this very pass; after the launch the caching allocator re-uses it only for work queued LATER on this stream)
+    std::vector<at::Tensor> keep_alive;
     int launches = 0;
 
     doda_cx_op &push(int kind, int flags) {
@@ -1438,6 +1441,13 @@ struct Builder {
         launches = n + n2;
     }
 
+    // the BatchNorm of L as an op reads it: per-channel vectors and, backward (`with_input`), the BatchNorm's input
+    static void bn_fields(doda_cx_op &o, const Layer &L, bool with_input) {
+        o.gamma = (const float *)L.bn.gamma.data_ptr(); o.beta = (const float *)L.bn.beta.data_ptr();
+        o.mean = L.mean; o.invstd = L.invstd;
+        if (with_input) { o.aux = L.x.p; o.aux_ld = L.x.ld; }
+    }
+
     // ---- forward ----
     void stats_of(Val &x) {   // a tensor that arrives without statistics (the executor's input)
         x.stats = stat_buf(x.c);
@@ -1455,11 +1465,10 @@ struct Builder {
         first = false;
         o.rows = x.rows; o.c_in = x.c; o.x_ld = x.ld; o.y_ld = x.c; o.x = x.p; o.y = L.a.data_ptr();
         o.eps = L.bn.eps; o.momentum = L.bn.mom;
-        o.gamma = (const float *)L.bn.gamma.data_ptr(); o.beta = (const float *)L.bn.beta.data_ptr();
         o.running_mean = (float *)L.bn.rm.data_ptr(); o.running_var = (float *)L.bn.rv.data_ptr();
+        if (training) { L.mean = arena.floats(x.c); L.invstd = arena.floats(x.c); }
+        bn_fields(o, L, false);
         if (training) {
-            L.mean = arena.floats(x.c); L.invstd = arena.floats(x.c);
-            o.mean = L.mean; o.invstd = L.invstd;
             o.stats = x.stats; o.stats_b = x.stats_b; o.c_split = x.c_split > 0 ? x.c_split : x.c;
             o.nbt = L.bn.nbt.defined() ? (int64_t *)L.bn.nbt.data_ptr() : nullptr;
         } else {
@@ -1488,6 +1497,75 @@ struct Builder {
             o.stats = out.stats;
         }
     }
+
+    // ---- backward ----
+    // gamma / beta gradient targets: the reducer's bucket views when the parameters have homes, existing .grad tensors
+    // (accumulate) or fresh tensors deposited afterwards
+    struct PGrad { at::Tensor param, buf; bool accum = false, fresh = false; };
+    std::vector<PGrad> pgrads;
+    int task = -1;        // the backward pass's graph task
+    bool plain = true;    // plain_accumulating_backward()
+    float *pgrad(const at::Tensor &param, int64_t c, int &flags) {
+        PGrad pg;
+        pg.param = param;
+        at::Tensor cur = param.grad();
+        if (!plain) {   // a pass restricted to specific inputs: the kernel's gamma / beta sums go to scratch
+            pg.buf = pempty({c}, param.options().dtype(at::kFloat));
+        } else if (cur.defined() && cur.scalar_type() == at::kFloat && cur.is_contiguous() && cur.numel() == c) {
+            pg.buf = cur; pg.accum = true; flags |= DODA_CX_F_ACCUM;
+        } else {
+            at::Tensor h;
+            if (param.is_leaf() && param.scalar_type() == at::kFloat && param.numel() == c) h = take_grad_home(param, task);
+            pg.buf = h.defined() ? h : pempty({c}, param.options().dtype(at::kFloat));
+            pg.fresh = true;
+        }
+        pgrads.push_back(pg);
+        return (float *)pg.buf.data_ptr();
+    }
+    // dz = data gradient of L's conv applied to `dy`, masked by L's ReLU; statistics for L's BatchNorm backward
+    void *gemm_bwd(const Layer &L, const at::Tensor &dy, bool identity, float *&st, bool barrier) {
+        void *dz = arena.alloc((size_t)L.n_in * L.c_in * esz);
+        st = stat_buf(L.c_in);
+        doda_cx_op &o = push(DODA_CX_GEMM, (barrier && !first ? DODA_CX_F_BARRIER : 0) | DODA_CX_F_RELU | (identity ? DODA_CX_F_IDENTITY : 0));
+        first = false;
+        o.rows = L.n_in; o.rows_in = L.n_out; o.c_in = L.c_out; o.c_out = L.c_in;
+        o.K = identity ? 1 : (int32_t)L.bwd_tbl.size(0);
+        o.tbl = identity ? nullptr : (const int32_t *)L.bwd_tbl.data_ptr();
+        o.tbl_ld = identity ? L.n_in : (int32_t)L.bwd_tbl.size(1);
+        if (!identity) o.tilebook = tilebook_behind(L.bwd_tbl, L.n_in);
+        o.x = dy.data_ptr(); o.x_ld = L.c_out;
+        o.w = L.cv.pk_bwd.data_ptr();
+        o.y = dz; o.y_ld = L.c_in;
+        bn_fields(o, L, true);
+        o.stats = st;
+        return dz;
+    }
+    // gradient of L's BatchNorm input from dz (+ add); a concatenated input splits into two dense tensors
+    void bn_bwd(const Layer &L, void *dz, float *st, const at::Tensor &add, at::Tensor &left, at::Tensor &right) {
+        int flags = DODA_CX_F_BARRIER;
+        const int c = L.c_in;
+        const int split = (L.x.c_split > 0 && L.x.c_split < c) ? L.x.c_split : c;
+        left = pempty({L.n_in, split}, bf);
+        keep_alive.push_back(left);
+        if (split < c) { right = pempty({L.n_in, c - split}, bf); keep_alive.push_back(right); }
+        int f1 = 0, f2 = 0;
+        float *dg = pgrad(L.bn.gamma, c, f1), *db = pgrad(L.bn.beta, c, f2);
+        if ((f1 != 0) != (f2 != 0)) {   // one accumulates, the other does not: give both fresh buffers and add afterwards
+            PGrad &pa = pgrads[pgrads.size() - 2], &pb = pgrads.back();
+            if (pa.accum) { pa.buf = pempty({c}, pa.param.options().dtype(at::kFloat)); pa.accum = false; pa.fresh = true; dg = (float *)pa.buf.data_ptr(); }
+            if (pb.accum) { pb.buf = pempty({c}, pb.param.options().dtype(at::kFloat)); pb.accum = false; pb.fresh = true; db = (float *)pb.buf.data_ptr(); }
+        } else if (f1) flags |= DODA_CX_F_ACCUM;
+        flags |= DODA_CX_F_RELU;   // (the data-grad kernels store dz unmasked: the op masks, and needs beta)
+        doda_cx_op &o = push(DODA_CX_BNBWD, flags);
+        o.rows = L.n_in; o.c_in = c; o.c_split = split;
+        o.x = dz; o.x_ld = c;
+        bn_fields(o, L, true);
+        if (add.defined()) { o.res = add.data_ptr(); o.res_ld = (int32_t)add.size(1); }
+        o.y = left.data_ptr(); o.y_ld = split;
+        if (split < c) { o.y2 = right.data_ptr(); o.y2_ld = c - split; }
+        o.stats = st;
+        o.dgamma = dg; o.dbeta = db;
+    }
 };
 
 int g_coarse_launches_fwd = 0, g_coarse_launches_bwd = 0;   // launches of the last per-layer forward / backward list (tests, tools)
@@ -1496,10 +1574,6 @@ struct CoarseNode : public torch::autograd::Node {
     std::vector<Step> steps;
     std::vector<at::Tensor> keep;      // arena chunks and tensors the saved pointers refer to
     at::Tensor x_in;                   // (kept for its size / options)
-
-    // gamma / beta gradient targets: the reducer's bucket views when the parameters have homes, existing .grad tensors
-    // (accumulate) or fresh tensors deposited afterwards
-    struct PGrad { at::Tensor param, buf; bool accum = false, fresh = false; };
 
     variable_list apply(variable_list &&grads) override {
         host_timing::Scope host_scope(5);
@@ -1511,103 +1585,30 @@ struct CoarseNode : public torch::autograd::Node {
         B.esz = elem_bytes(g);
         B.bf = g.options();
         B.arena.opt = g.options().dtype(at::kByte);
-        const int task = torch::autograd::get_current_graph_task_id();
-        std::vector<PGrad> pgrads;
-        const bool plain = plain_accumulating_backward();
-        auto pgrad = [&](const at::Tensor &param, int64_t c, int &flags) -> float * {
-            PGrad pg;
-            pg.param = param;
-            at::Tensor cur = param.grad();
-            if (!plain) {   // a pass restricted to specific inputs: the kernel's gamma / beta sums go to scratch
-                pg.buf = pempty({c}, param.options().dtype(at::kFloat));
-            } else if (cur.defined() && cur.scalar_type() == at::kFloat && cur.is_contiguous() && cur.numel() == c) {
-                pg.buf = cur; pg.accum = true; flags |= DODA_CX_F_ACCUM;
-            } else {
-                at::Tensor h;
-                if (param.is_leaf() && param.scalar_type() == at::kFloat && param.numel() == c) h = take_grad_home(param, task);
-                pg.buf = h.defined() ? h : pempty({c}, param.options().dtype(at::kFloat));
-                pg.fresh = true;
-            }
-            pgrads.push_back(pg);
-            return (float *)pg.buf.data_ptr();
-        };
+        B.task = torch::autograd::get_current_graph_task_id();
+        B.plain = plain_accumulating_backward();
         struct WJob { at::Tensor a, b, tbl, weight; int64_t n_rows; PairLists pl; };
         std::vector<WJob> wjobs;
-        bool first = true;
-        // dz = data gradient of L's conv applied to `dy`, masked by L's ReLU; statistics for L's BatchNorm backward
-        auto gemm_bwd = [&](const Layer &L, const at::Tensor &dy, bool identity, float *&st, bool barrier) -> void * {
-            void *dz = B.arena.alloc((size_t)L.n_in * L.c_in * B.esz);
-            st = B.stat_buf(L.c_in);
-            doda_cx_op &o = B.push(DODA_CX_GEMM, (barrier && !first ? DODA_CX_F_BARRIER : 0) | DODA_CX_F_RELU | (identity ? DODA_CX_F_IDENTITY : 0));
-            first = false;
-            o.rows = L.n_in; o.rows_in = L.n_out; o.c_in = L.c_out; o.c_out = L.c_in;
-            o.K = identity ? 1 : (int32_t)L.bwd_tbl.size(0);
-            o.tbl = identity ? nullptr : (const int32_t *)L.bwd_tbl.data_ptr();
-            o.tbl_ld = identity ? L.n_in : (int32_t)L.bwd_tbl.size(1);
-            if (!identity) o.tilebook = tilebook_behind(L.bwd_tbl, L.n_in);
-            o.x = dy.data_ptr(); o.x_ld = L.c_out;
-            o.w = L.cv.pk_bwd.data_ptr();
-            o.y = dz; o.y_ld = L.c_in;
-            o.aux = L.x.p; o.aux_ld = L.x.ld;
-            o.mean = L.mean; o.invstd = L.invstd;
-            o.gamma = (const float *)L.bn.gamma.data_ptr(); o.beta = (const float *)L.bn.beta.data_ptr();
-            o.stats = st;
-            return dz;
-        };
-        // gradient of L's BatchNorm input from dz (+ add); a concatenated input splits into two dense tensors
-        auto bn_bwd = [&](const Layer &L, void *dz, float *st, const at::Tensor &add, at::Tensor &left, at::Tensor &right) {
-            int flags = DODA_CX_F_BARRIER;
-            const int c = L.c_in;
-            const int split = (L.x.c_split > 0 && L.x.c_split < c) ? L.x.c_split : c;
-            left = pempty({L.n_in, split}, B.bf);
-            keep_alive.push_back(left);   // (every tensor an op points at stays alive until the launch is queued: a freed block
-            //                               could be handed out again by the next at::empty of this very pass)
-            if (split < c) { right = pempty({L.n_in, c - split}, B.bf); keep_alive.push_back(right); }
-            float *dg = nullptr, *db = nullptr;
-            {
-                int f1 = 0, f2 = 0;
-                dg = pgrad(L.bn.gamma, c, f1);
-                db = pgrad(L.bn.beta, c, f2);
-                if ((f1 != 0) != (f2 != 0)) {   // one accumulates, the other does not: give both fresh buffers and add afterwards
-                    PGrad &pa = pgrads[pgrads.size() - 2], &pb = pgrads.back();
-                    if (pa.accum) { pa.buf = pempty({c}, pa.param.options().dtype(at::kFloat)); pa.accum = false; pa.fresh = true; dg = (float *)pa.buf.data_ptr(); }
-                    if (pb.accum) { pb.buf = pempty({c}, pb.param.options().dtype(at::kFloat)); pb.accum = false; pb.fresh = true; db = (float *)pb.buf.data_ptr(); }
-                } else if (f1) flags |= DODA_CX_F_ACCUM;
-            }
-            flags |= DODA_CX_F_RELU;   // (the data-grad kernels store dz unmasked: the op masks, and needs beta)
-            doda_cx_op &o = B.push(DODA_CX_BNBWD, flags);
-            o.beta = (const float *)L.bn.beta.data_ptr();
-            o.rows = L.n_in; o.c_in = c; o.c_split = split;
-            o.x = dz; o.x_ld = c;
-            o.aux = L.x.p; o.aux_ld = L.x.ld;
-            if (add.defined()) { o.res = add.data_ptr(); o.res_ld = (int32_t)add.size(1); }
-            o.y = left.data_ptr(); o.y_ld = split;
-            if (split < c) { o.y2 = right.data_ptr(); o.y2_ld = c - split; }
-            o.stats = st;
-            o.mean = L.mean; o.invstd = L.invstd;
-            o.gamma = (const float *)L.bn.gamma.data_ptr();
-            o.dgamma = dg; o.dbeta = db;
-        };
         std::vector<at::Tensor> skip_grads;
         for (size_t si = steps.size(); si-- > 0;) {
             const Step &S = steps[si];
             if (S.kind == 0) {
                 float *st2 = nullptr, *st1 = nullptr;
-                void *dz2 = gemm_bwd(S.l2, g, false, st2, true);
+                void *dz2 = B.gemm_bwd(S.l2, g, false, st2, true);
                 at::Tensor gS;
                 if (S.has_skip) {   // data gradient of the 1x1 skip conv: no mask, no statistics; independent of dz2
                     gS = pempty({S.l1.n_in, S.l1.c_in}, B.bf);
-                    keep_alive.push_back(gS);
+                    B.keep_alive.push_back(gS);
                     doda_cx_op &o = B.push(DODA_CX_GEMM, DODA_CX_F_IDENTITY);
                     o.tbl = (const int32_t *)S.ident.data_ptr();
                     o.rows = S.l1.n_in; o.rows_in = S.l1.n_in; o.c_in = S.l2.c_out; o.c_out = S.l1.c_in; o.K = 1; o.tbl_ld = S.l1.n_in;
                     o.x = g.data_ptr(); o.x_ld = S.l2.c_out; o.w = S.skip.pk_bwd.data_ptr(); o.y = gS.data_ptr(); o.y_ld = S.l1.c_in;
                 }
                 at::Tensor g1, none;
-                bn_bwd(S.l2, dz2, st2, at::Tensor(), g1, none);
-                void *dz1 = gemm_bwd(S.l1, g1, false, st1, true);
+                B.bn_bwd(S.l2, dz2, st2, at::Tensor(), g1, none);
+                void *dz1 = B.gemm_bwd(S.l1, g1, false, st1, true);
                 at::Tensor left, right;
-                bn_bwd(S.l1, dz1, st1, S.has_skip ? gS : g, left, right);
+                B.bn_bwd(S.l1, dz1, st1, S.has_skip ? gS : g, left, right);
                 wjobs.push_back({S.l2.a, g, S.l2.fwd_tbl, S.l2.cv.weight, S.l2.n_out, PairLists()});
                 wjobs.push_back({S.l1.a, g1, S.l1.fwd_tbl, S.l1.cv.weight, S.l1.n_out, PairLists()});
                 if (S.has_skip) {
@@ -1619,14 +1620,14 @@ struct CoarseNode : public torch::autograd::Node {
                 else g = left;
             } else {
                 float *st = nullptr;
-                void *dz = gemm_bwd(S.l1, g, false, st, true);
+                void *dz = B.gemm_bwd(S.l1, g, false, st, true);
                 at::Tensor add, left, none;
                 if (S.kind == 1) {
                     TORCH_CHECK(!skip_grads.empty(), "doda coarse: unbalanced down / up steps");
                     add = skip_grads.back();
                     skip_grads.pop_back();
                 }
-                bn_bwd(S.l1, dz, st, add, left, none);
+                B.bn_bwd(S.l1, dz, st, add, left, none);
                 wjobs.push_back({S.l1.a, g, S.l1.fwd_tbl, S.l1.cv.weight, S.l1.n_out, PairLists()});
                 g = left;
             }
@@ -1634,21 +1635,20 @@ struct CoarseNode : public torch::autograd::Node {
         B.run(g);
         // parameter gradients: the weight gradients join the step's deferred launch; gamma / beta are bound now (not in a
         // backward pass restricted to specific inputs: see plain_accumulating_backward)
-        if (!plain) wjobs.clear();
+        if (!B.plain) wjobs.clear();
         for (WJob &w : wjobs) {
             if (!try_defer_wgrad(w.a, w.b, w.tbl, w.n_rows, w.weight, w.pl))
                 deposit_grad(w.weight, wgrad(w.a, w.b, w.tbl, w.n_rows, w.pl).reshape(w.weight.sizes()).to(w.weight.scalar_type()));
         }
-        for (PGrad &pg : pgrads)
+        for (Builder::PGrad &pg : B.pgrads)
             if (pg.fresh) deposit_grad(pg.param, pg.buf);
         // (the arena of this pass must outlive the launch: the caching allocator re-uses a freed block only for work queued
         // LATER on this stream, which is ordered behind the launch)
-        keep_alive.clear();
+        B.keep_alive.clear();
         g_coarse_launches_bwd = B.launches;
         if (task_should_compute_output(0)) out[0] = g;
         return out;
     }
-    std::vector<at::Tensor> keep_alive;
     void release_variables() override {
         steps.clear();
         keep.clear();
@@ -1697,15 +1697,15 @@ std::vector<at::Tensor> coarse_ublock(const at::Tensor &x_in, const c10::optiona
         S.kind = (int)kinds[si];
         const bool last = si + 1 == kinds.size();
         if (S.kind == 0) {
-            TORCH_CHECK((t.size() == 21 || t.size() == 22) && sc.size() == 4 && t[0].has_value(), "doda coarse_ublock: RB step");
-            const at::Tensor &tbl = *t[0];
+            TORCH_CHECK((t.size() == RB_TENSORS - 1 || t.size() == RB_TENSORS) && sc.size() == 4 && t[RB_TABLE].has_value(), "doda coarse_ublock: RB step");
+            const at::Tensor &tbl = *t[RB_TABLE];
             const int n = cur.rows;
             TORCH_CHECK(tbl.dim() == 2 && tbl.size(0) == 27 && tbl.size(1) == n && tbl.scalar_type() == at::kInt, "doda coarse_ublock: SubM table");
-            S.l1.bn = bn_of(t, 1, sc[0], sc[1]);
-            S.l1.cv = cv_of(t, 6);
-            S.l2.bn = bn_of(t, 9, sc[2], sc[3]);
-            S.l2.cv = cv_of(t, 14);
-            S.has_skip = t[17].has_value() && t[17]->defined();
+            S.l1.bn = bn_of(t, RB_BN1, sc[0], sc[1]);
+            S.l1.cv = cv_of(t, RB_CONV1);
+            S.l2.bn = bn_of(t, RB_BN2, sc[2], sc[3]);
+            S.l2.cv = cv_of(t, RB_CONV2);
+            S.has_skip = t[RB_SKIP].has_value() && t[RB_SKIP]->defined();
             const int cin = cur.c, cout = (int)S.l1.cv.weight.size(-1);
             TORCH_CHECK(S.l1.cv.weight.size(-2) == cin && S.l2.cv.weight.size(-2) == cout && S.l2.cv.weight.size(-1) == cout &&
                         (S.has_skip || cin == cout), "doda coarse_ublock: channel counts of a residual block");
@@ -1719,10 +1719,10 @@ std::vector<at::Tensor> coarse_ublock(const at::Tensor &x_in, const c10::optiona
             B.gemm_fwd(S.l1, tbl, false, y1, nullptr, training, true);
             Val skipv = cur;
             if (S.has_skip) {   // 1x1 conv of the block's raw input (no barrier: nothing it reads was written since the last one)
-                S.skip = cv_of(t, 17);
-                TORCH_CHECK(t[20].has_value(), "doda coarse_ublock: identity table of the skip conv");
-                S.ident = *t[20];
-                S.skip_pairs = t.size() > 21 && t[21].has_value() && t[21]->defined();
+                S.skip = cv_of(t, RB_SKIP);
+                TORCH_CHECK(t[RB_IDENT].has_value(), "doda coarse_ublock: identity table of the skip conv");
+                S.ident = *t[RB_IDENT];
+                S.skip_pairs = t.size() > RB_SKIP_PAIRS && t[RB_SKIP_PAIRS].has_value() && t[RB_SKIP_PAIRS]->defined();
                 TORCH_CHECK(cur.t.defined() && cur.ld == cur.c, "doda coarse_ublock: the skip conv's input must be dense");
                 skipv = B.dense(n, cout, false);
                 Layer sk;
@@ -1751,11 +1751,11 @@ std::vector<at::Tensor> coarse_ublock(const at::Tensor &x_in, const c10::optiona
             if (!last && kinds[si + 1] == 1) skips.back().left = y;
             cur = y;
         } else if (S.kind == 1 || S.kind == 2) {
-            TORCH_CHECK(t.size() == 10 && sc.size() == 3 && t[0].has_value() && t[1].has_value(), "doda coarse_ublock: down / up step");
-            S.l1.bn = bn_of(t, 2, sc[0], sc[1]);
-            S.l1.cv = cv_of(t, 7);
-            S.l1.fwd_tbl = *t[0];
-            S.l1.bwd_tbl = *t[1];
+            TORCH_CHECK(t.size() == UD_TENSORS && sc.size() == 3 && t[UD_FWD_TABLE].has_value() && t[UD_BWD_TABLE].has_value(), "doda coarse_ublock: down / up step");
+            S.l1.bn = bn_of(t, UD_BN, sc[0], sc[1]);
+            S.l1.cv = cv_of(t, UD_CONV);
+            S.l1.fwd_tbl = *t[UD_FWD_TABLE];
+            S.l1.bwd_tbl = *t[UD_BWD_TABLE];
             S.l1.K = 8;
             const int n_out = (int)sc[2], cin = cur.c, cout = (int)S.l1.cv.weight.size(-1);
             TORCH_CHECK(S.l1.fwd_tbl.size(0) == 8 && S.l1.fwd_tbl.size(1) == n_out && S.l1.bwd_tbl.size(0) == 8 && S.l1.bwd_tbl.size(1) == cur.rows &&
@@ -1891,6 +1891,28 @@ void optim_step(int64_t kind, const std::vector<at::Tensor> &params, const std::
                           stream_of(params[0])), "doda_optim_step");
 }
 
+// (tiles, tiles above the 64-byte-row capacity, above the list capacity) of the tilebook behind `tbl`, read back from the builder's
+// two counters at its end (a synchronisation); false, and `over` untouched, when the table has none
+static bool tilebook_overflow(const at::Tensor &tbl, std::tuple<int64_t, int64_t, int64_t> &over) {
+    const void *tb = tilebook_behind(tbl, tbl.dim() == 2 ? tbl.size(1) : 0);
+    if (!tb) return false;
+    const int64_t T = doda_tilebook_tile();
+    char *p = (char *)const_cast<void *>(tb) + doda_tilebook_bytes((int32_t)tbl.size(1), (int32_t)tbl.size(0)) - 8;
+    int32_t ov[2] = {0, 0};
+    if (!read_back_blocking(p, ov, 2, stream_of(tbl), (int)tbl.device().index())) {
+        at::Tensor host = at::from_blob(p, {2}, tbl.options()).cpu();
+        ov[0] = host[0].item<int32_t>();
+        ov[1] = host[1].item<int32_t>();
+    }
+    over = std::make_tuple((tbl.size(1) + T - 1) / T, (int64_t)ov[0], (int64_t)ov[1]);
+    return true;
+}
+
+// {tensor, tensor or undefined} as Python's (tensor, tensor or None)
+static std::pair<at::Tensor, c10::optional<at::Tensor>> with_optional(const std::vector<at::Tensor> &r) {
+    return {r[0], r[1].defined() ? c10::optional<at::Tensor>(r[1]) : c10::nullopt};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("indice_conv", &indice_conv, "sparse conv (gather table) with autograd",
           py::arg("features"), py::arg("weight"), py::arg("fwd_tbl"), py::arg("bwd_tbl"), py::arg("n_out"),
@@ -1910,9 +1932,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                   const c10::optional<at::Tensor> &residual, const c10::optional<at::Tensor> &pair_in,
                                   const c10::optional<at::Tensor> &pair_out, const c10::optional<at::Tensor> &pair_num,
                                   const c10::optional<at::Tensor> &pair_seg) {
-        auto r = indice_conv_impl(features, weight, fwd_tbl, bwd_tbl, n_out, bwd_layout, pk_fwd, pk_bwd, residual,
-                                  pair_in, pair_out, pair_num, pair_seg, true);
-        return std::make_pair(r[0], r[1].defined() ? c10::optional<at::Tensor>(r[1]) : c10::nullopt);
+        return with_optional(indice_conv_impl(features, weight, fwd_tbl, bwd_tbl, n_out, bwd_layout, pk_fwd, pk_bwd, residual,
+                                              pair_in, pair_out, pair_num, pair_seg, true));
     }, "sparse conv that also returns the BatchNorm statistics partials of its output",
           py::arg("features"), py::arg("weight"), py::arg("fwd_tbl"), py::arg("bwd_tbl"), py::arg("n_out"),
           py::arg("bwd_layout"), py::arg("pk_fwd"), py::arg("pk_bwd"), py::arg("residual"),
@@ -1925,9 +1946,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                const std::vector<c10::optional<at::Tensor>> &rb, int64_t n_out,
                                const c10::optional<at::Tensor> &skip, bool want_stats,
                                const std::vector<c10::optional<at::Tensor>> &sc, const c10::optional<at::Tensor> &stats_in_b) {
-        auto r = residual_block(x, stats_in, bn1, bn2, training, momentum1, eps1, momentum2, eps2, cv1, cv2, rb, n_out, skip,
-                                want_stats, sc, stats_in_b);
-        return std::make_pair(r[0], r[1].defined() ? c10::optional<at::Tensor>(r[1]) : c10::nullopt);
+        return with_optional(residual_block(x, stats_in, bn1, bn2, training, momentum1, eps1, momentum2, eps2, cv1, cv2, rb, n_out, skip,
+                                            want_stats, sc, stats_in_b));
     }, "BatchNorm -> ReLU -> SubM conv -> BatchNorm -> ReLU -> SubM conv (+ skip) in one call",
           py::arg("x"), py::arg("stats_in"), py::arg("bn1"), py::arg("bn2"), py::arg("training"), py::arg("momentum1"),
           py::arg("eps1"), py::arg("momentum2"), py::arg("eps2"), py::arg("cv1"), py::arg("cv2"), py::arg("rb"),
@@ -1953,26 +1973,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               // in ONE call without the GIL: the rulebook thread's read-back does not stall the issuing thread
               auto levels = build_pyramid(indices, shape, batch, n_levels, pairs_min_rows, tile_min_rows, tile_levels,
                                           wgrad_tile_levels);
-              int64_t nt = -1, o64 = 0, o32 = 0;
-              if (!levels.empty()) {
-                  const at::Tensor &tbl = std::get<0>(levels[0]);
-                  const void *tb = tilebook_behind(tbl, tbl.dim() == 2 ? tbl.size(1) : 0);
-                  if (tb) {
-                      const int64_t T = doda_tilebook_tile(), K = tbl.size(0), UMAX = doda_tilebook_umax();
-                      nt = (tbl.size(1) + T - 1) / T;
-                      (void)K; (void)UMAX; (void)nt;
-                      char *p = (char *)const_cast<void *>(tb) + doda_tilebook_bytes((int32_t)tbl.size(1), (int32_t)tbl.size(0)) - 8;
-                      int32_t ov[2] = {0, 0};
-                      if (!read_back_blocking(p, ov, 2, stream_of(tbl), (int)tbl.device().index())) {
-                          at::Tensor over = at::from_blob(p, {2}, tbl.options()).cpu();
-                          ov[0] = over[0].item<int32_t>();
-                          ov[1] = over[1].item<int32_t>();
-                      }
-                      o64 = ov[0];
-                      o32 = ov[1];
-                  }
-              }
-              return std::make_tuple(levels, nt, o64, o32);
+              std::tuple<int64_t, int64_t, int64_t> over{-1, 0, 0};
+              if (!levels.empty()) tilebook_overflow(std::get<0>(levels[0]), over);
+              return std::make_tuple(levels, std::get<0>(over), std::get<1>(over), std::get<2>(over));
           }, py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("n_levels"), py::arg("pairs_min_rows") = -1,
           py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::arg("wgrad_tile_levels") = 0,
           py::call_guard<py::gil_scoped_release>());
@@ -2006,17 +2009,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               at::Tensor ucount = at::from_blob(p + nt * UMAX * 4 + nt * T * LW * 4, {nt}, o32).clone();
               return std::make_tuple(ulist, lidx, ucount);
           });
-    m.def("tilebook_overflow", [](const at::Tensor &tbl) {   // (tiles, tiles above the 64-byte-row capacity, above the list capacity); syncs
-              const void *tb = tilebook_behind(tbl, tbl.size(1));
-              TORCH_CHECK(tb, "doda tilebook_overflow: no tilebook");
-              const int64_t T = doda_tilebook_tile(), nt = (tbl.size(1) + T - 1) / T, K = tbl.size(0), UMAX = doda_tilebook_umax();
-              (void)K; (void)UMAX; (void)nt;
-              char *p = (char *)const_cast<void *>(tb) + doda_tilebook_bytes((int32_t)tbl.size(1), (int32_t)tbl.size(0)) - 8;
-              at::Tensor over = at::from_blob(p, {2}, tbl.options()).cpu();
-              return std::make_tuple(nt, (int64_t)over[0].item<int32_t>(), (int64_t)over[1].item<int32_t>());
+    m.def("tilebook_overflow", [](const at::Tensor &tbl) {   // syncs
+              std::tuple<int64_t, int64_t, int64_t> over;
+              TORCH_CHECK(tilebook_overflow(tbl, over), "doda tilebook_overflow: no tilebook");
+              return over;
           }, py::call_guard<py::gil_scoped_release>());   // (called on the rulebook thread: its read-back must not hold the GIL)
     m.def("set_tile_kernel", [](bool on) { doda_set_option(DODA_OPT_TILE_KERNEL, on ? 1 : 0); });
-    m.def("pending_wgrads", []() { std::lock_guard<std::mutex> lock(g_wq_mu); return (int64_t)g_wq.size(); });
+    m.def("pending_wgrads", []() { std::lock_guard<std::mutex> lock(g_wq.mu); return (int64_t)g_wq.pending.size(); });
     m.def("set_defer_wgrad", [](bool on) { g_defer_wgrad = on; },
           "queue conv weight gradients during backward and issue them in one multi-layer call at its end");
     m.def("get_defer_wgrad", []() { return g_defer_wgrad; });
@@ -2067,12 +2066,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("set_grad_home", &set_grad_home, "view of a flat gradient bucket that receives the parameter's gradient in place (None: forget)");
     m.def("drop_grad_home", &drop_grad_home, "forget the parameter's home if it is this view; returns whether it was");
     m.def("clear_grad_homes", &clear_grad_homes);
-    m.def("set_wgrad_split", [](bool on) { g_wq_split = on; if (!on) g_ev_early_valid = false; },
+    m.def("set_wgrad_split", [](bool on) { g_wq.split = on; if (!on) g_wq.early_valid = false; },
           "issue the wide layers' weight gradients first and record an event behind them (GradAllReduce)");
     m.def("wait_wide_wgrads", [](int64_t stream) {
-              if (!g_ev_early_valid) return false;
-              g_ev_early_valid = false;
-              TORCH_CHECK(hipStreamWaitEvent((hipStream_t)stream, g_ev_early, 0) == hipSuccess, "doda: hipStreamWaitEvent");
+              if (!g_wq.early_valid) return false;
+              g_wq.early_valid = false;
+              TORCH_CHECK(hipStreamWaitEvent((hipStream_t)stream, g_wq.early.ev, 0) == hipSuccess, "doda: hipStreamWaitEvent");
               return true;
           }, "make `stream` wait for the wide layers' weight gradients of the last flush; false if there was no split flush");
     m.def("host_timing", []() {   // {name: (microseconds, calls)} since the last call; empty unless DODA_HOST_TIMING=1
@@ -2096,8 +2095,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                               const std::vector<std::vector<double>> &scalars, bool training, int64_t gate_step, py::object gate) {
         std::function<void()> between;
         if (gate_step >= 0 && !gate.is_none()) between = [gate]() { gate(); };   // (the GIL is held throughout this call)
-        auto r = coarse::coarse_ublock(x, stats_in, kinds, tensors, scalars, training, gate_step, between);
-        return std::make_pair(r[0], r[1].defined() ? c10::optional<at::Tensor>(r[1]) : c10::nullopt);
+        return with_optional(coarse::coarse_ublock(x, stats_in, kinds, tensors, scalars, training, gate_step, between));
     }, "a U-Net subtree of coarse levels as one op list per direction: per-layer launches issued inside the library with the "
        "BatchNorm ops folded into the convolutions (doda_layers_run)",
           py::arg("x"), py::arg("stats_in"), py::arg("kinds"), py::arg("tensors"), py::arg("scalars"), py::arg("training"),

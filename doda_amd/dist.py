@@ -97,7 +97,7 @@ class _Bucket:
                 from ._ext import ext as _ext
             except Exception:
                 _ext = None
-            if _ext is not None and hasattr(_ext, "grads_into_views"):
+            if _ext is not None:
                 return int(_ext.grads_into_views(self.params, self.views))   # (the same pass without the interpreter)
         moved = 0
         for p, v in zip(self.params, self.views):
@@ -159,7 +159,7 @@ class GradAllReduce:
         except Exception:
             _ext = None
         on_gpu = bool(self.params) and self.params[0].is_cuda
-        if overlap and self.active and on_gpu and _ext is not None and hasattr(_ext, "set_wgrad_split"):
+        if overlap and self.active and on_gpu and _ext is not None:
             narrow = [p for p in self.params if p.dim() == 5 and p.shape[3] <= 32 and p.shape[4] <= 32]
             # (round 5) a U-Net: the LATE set is instead what the backward pass produces last — the encoder of levels 1-2
             # (input conv, blocks and strided conv of the two finest levels: 0.2 of the 30 MB); everything else is complete
@@ -171,8 +171,7 @@ class GradAllReduce:
             # OPT-IN (DODA_EARLY_ALLREDUCE=1): measured under a forced one-rank RCCL group the mid-backward flush + collective
             # issue cost the host-bound step 0.8-1.0 ms (6.8-7.0 against 5.7-6.0 ms with the end-of-backward split below),
             # more than the 0.35-0.7 ms an 8-GPU ring would expose
-            if (os.environ.get("DODA_EARLY_ALLREDUCE", "0") == "1" and hasattr(_ext, "flush_wgrads_early") and enc
-                    and len(enc) < len(named) and any(n.startswith("unet.u.u.") for n, _ in named)):
+            if (os.environ.get("DODA_EARLY_ALLREDUCE", "0") == "1" and enc and len(enc) < len(named) and any(n.startswith("unet.u.u.") for n, _ in named)):
                 narrow = enc
                 self._early_mode = True
             if narrow and len(narrow) < len(self.params):
@@ -185,7 +184,7 @@ class GradAllReduce:
         if self.active:
             self.buckets = [_Bucket(b) for b in self._cut([p for p in self.params if id(p) not in narrow_ids], bucket_mb)]
             self.late_buckets = [_Bucket(b) for b in self._cut([p for p in self.params if id(p) in narrow_ids], bucket_mb)]
-            if on_gpu and _ext is not None and hasattr(_ext, "set_grad_home"):
+            if on_gpu and _ext is not None:
                 self._ext = _ext
                 for b in self.buckets + self.late_buckets:
                     for p, v in zip(b.params, b.views):

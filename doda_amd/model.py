@@ -259,8 +259,7 @@ class ResidualBlock(SparseModule):
         path does not hold — then the modules run one by one as before."""
         ext, d, feats = Fsp._ext, self._description(), input.features
         # (hooks — feature taps, profilers — must fire: module by module then)
-        if (ext is None or not Fsp._SERIAL or not hasattr(ext, "residual_block") or d is None or not d.per_block or any_hooks(d.modules)
-                or not feats.is_cuda or feats.dim() != 2 or feats.shape[0] < 2 or feats.dtype not in (torch.float32, torch.bfloat16)):
+        if (ext is None or not Fsp._SERIAL or d is None or not d.per_block or any_hooks(d.modules) or not feats.is_cuda or feats.dim() != 2 or feats.shape[0] < 2 or feats.dtype not in (torch.float32, torch.bfloat16)):
             return None
         training = d.bn1.training
         # the 1x1 skip convolution (reference model/unet_block.py:18-21) runs inside the extension call, on the first
@@ -413,7 +412,7 @@ class UBlock(nn.Module):
         """The whole subtree in one executor call, or None when a precondition fails (then the modules run one by one)."""
         ext = Fsp._ext
         feats = input.features
-        if (ext is None or not Fsp._SERIAL or not hasattr(ext, "coarse_ublock") or not feats.is_cuda or feats.dim() != 2
+        if (ext is None or not Fsp._SERIAL or not feats.is_cuda or feats.dim() != 2
                 or choose_coarse_backend(feats.shape[0], feats.dtype) is None):
             return None
         plan = _described(self, _describe_subtree)

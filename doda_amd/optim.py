@@ -39,7 +39,7 @@ from ._ext import ext as _ext
 
 def _optim_step(*args):
     """doda_optim_step through the extension, or through ctypes when the extension is not loaded."""
-    if _ext is not None and hasattr(_ext, "optim_step"):
+    if _ext is not None:
         _ext.optim_step(*args)
     else:
         _ops.optim_step(*args)
@@ -69,7 +69,7 @@ class _Fused:
     def zero_grad(self, set_to_none=True):
         """torch's zero_grad(set_to_none=True) walks the parameters in Python (0.2 ms per step for the U-Net's 203); one
         extension call does the same stores.  set_to_none=False (in-place zeroing) is torch's."""
-        if not set_to_none or _ext is None or not hasattr(_ext, "clear_grads"):
+        if not set_to_none or _ext is None:
             return super().zero_grad(set_to_none=set_to_none)
         for group in self.param_groups:
             _ext.clear_grads(group["params"])

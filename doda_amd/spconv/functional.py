@@ -39,8 +39,7 @@ def set_deferred_wgrad(on):
     _ext.set_defer_wgrad(bool(on))
     # the extension's nodes then also deposit BatchNorm gamma / beta gradients themselves and keep no autograd edges to their
     # parameters (203 AccumulateGrad nodes less per U-Net step; DODA_DIRECT_GRADS=0: ordinary edges)
-    if hasattr(_ext, "set_direct_grads"):
-        _ext.set_direct_grads(bool(on) and os.environ.get("DODA_DIRECT_GRADS", "1") != "0")
+    _ext.set_direct_grads(bool(on) and os.environ.get("DODA_DIRECT_GRADS", "1") != "0")
     return bool(on)
 
 

@@ -1,5 +1,6 @@
 """ctypes binding of libdoda_hip.so (include/doda_hip.h and its companions include/doda_selftrain.h, include/doda_mix.h,
-include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h, include/doda_optim.h, include/doda_pgops.h).
+include/doda_aug.h, include/doda_loss.h, include/doda_eval.h, include/doda_subsample.h, include/doda_optim.h, include/doda_pgops.h,
+include/doda_pointops.h).
 
 There is no fallback: if the shared library is missing or lacks a symbol, importing the product
 path raises.  PyTorch is used only for device memory and streams; every signature below is
@@ -231,6 +232,26 @@ PGOPS_SIGNATURES = {
 PGOPS_SYMBOLS = tuple(PGOPS_SIGNATURES)
 PGOPS_ABI_VERSION = 1  # include/doda_pgops.h DODA_PGOPS_ABI_VERSION
 PG_WAVE_LIST, PG_LONG_SEGMENT, PG_IOU_LDS_INSTANCES = 64, 2048, 8192
+
+# name -> (restype, argtypes); mirrors include/doda_pointops.h (the rest of pointops2_cuda: sampling, grouping, interpolation,
+# subtraction, aggregation; same library)
+POINTOPS_SIGNATURES = {
+    "doda_pointops_abi_version": (c_i32, []),
+    "doda_po_transpose_workspace_bytes": (c_sz, [c_i32]),
+    "doda_po_transpose": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "doda_po_grouping_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_grouping_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_interpolation_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_interpolation_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_subtraction_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_subtraction_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_aggregation_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "doda_po_aggregation_bwd": (c_i32, [c_vp] * 10 + [c_i32] * 5 + [c_vp]),
+    "doda_po_furthestsampling": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+}
+POINTOPS_SYMBOLS = tuple(POINTOPS_SIGNATURES)
+POINTOPS_ABI_VERSION = 1  # include/doda_pointops.h DODA_POINTOPS_ABI_VERSION
+PO_WAVE_LIST, PO_FPS_BLOCK, PO_FPS_REG, PO_FPS_MAX_DIM = 64, 1024, 8, 8
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 ABI_VERSION = 12  # include/doda_hip.h DODA_ABI_VERSION
@@ -244,7 +265,8 @@ _ABIS = ((_SIGNATURES, "doda_abi_version", ABI_VERSION, "ABI"),
          (EVAL_SIGNATURES, "doda_eval_abi_version", EVAL_ABI_VERSION, "evaluation ABI"),
          (SUBSAMPLE_SIGNATURES, "doda_subsample_abi_version", SUBSAMPLE_ABI_VERSION, "subsample ABI"),
          (OPTIM_SIGNATURES, "doda_optim_abi_version", OPTIM_ABI_VERSION, "optimizer ABI"),
-         (PGOPS_SIGNATURES, "doda_pgops_abi_version", PGOPS_ABI_VERSION, "PG_OP ABI"))
+         (PGOPS_SIGNATURES, "doda_pgops_abi_version", PGOPS_ABI_VERSION, "PG_OP ABI"),
+         (POINTOPS_SIGNATURES, "doda_pointops_abi_version", POINTOPS_ABI_VERSION, "pointops ABI"))
 
 _lib = None
 

@@ -1501,3 +1501,143 @@ def get_iou(proposals_idx, proposals_offset, instance_labels, instance_pointnum,
     check(lib().doda_pg_get_iou(_p(proposals_idx), _p(proposals_offset), _p(instance_labels), _p(instance_pointnum),
                                 _p(proposals_iou), instance_labels.numel(), proposals_idx.numel(), n_instance, n_proposal, _p(ws),
                                 ws.numel(), _stream()), "doda_pg_get_iou")
+
+
+# ---- the rest of pointops2_cuda: sampling, grouping, interpolation, subtraction, aggregation (include/doda_pointops.h) --------
+def _po_check(what, floats=(), ints=()):
+    """float32 / int32, contiguous, on the device."""
+    _need_cuda(*floats, *ints)
+    for t in floats:
+        if t.dtype != torch.float32:
+            raise TypeError("%s: float32 tensors expected, got %s" % (what, t.dtype))
+    for t in ints:
+        if t.dtype != torch.int32:
+            raise TypeError("%s: int32 index / offset tensors expected, got %s" % (what, t.dtype))
+    for t in (*floats, *ints):
+        if not t.is_contiguous():
+            raise RuntimeError("%s: contiguous tensors expected" % what)
+
+
+def _po_shape(what, ok):
+    if not ok:
+        raise RuntimeError("%s: tensor shapes do not match the sizes" % what)
+
+
+po_transpose_calls = 0   # how many times the index by destination was built (tests count it)
+
+
+def po_transpose(idx, n):
+    """(start int32 [n + 1], pos int32 [m * nsample]) of idx int32 [m, nsample]: for every destination j in [0, n) the flat positions
+    p with idx.view(-1)[p] == j, ascending, at pos[start[j] : start[j + 1]]; entries outside [0, n) are dropped."""
+    global po_transpose_calls
+    _po_check("po_transpose", ints=(idx,))
+    _po_shape("po_transpose", idx.dim() == 2)
+    n = int(n)
+    m, nsample = idx.shape
+    start = torch.zeros(n + 1, dtype=torch.int32, device=idx.device)
+    pos = torch.empty(m * nsample, dtype=torch.int32, device=idx.device)
+    nbytes = lib().doda_po_transpose_workspace_bytes(n)
+    ws = _ws(nbytes, idx.device)
+    check(lib().doda_po_transpose(_p(idx), m, nsample, n, _p(start), _p(pos), _p(ws), ws.numel(), _stream()), "doda_po_transpose")
+    po_transpose_calls += 1
+    return start, pos
+
+
+def _po_transposed_ok(what, start, pos, n, total):
+    _po_check(what, ints=(start, pos))
+    _po_shape(what, start.numel() == n + 1 and pos.numel() >= total)
+
+
+def po_grouping_fwd(inp, idx, out):
+    """out [m, nsample, c] = inp [n, c] rows at idx [m, nsample]; an index outside [0, n) reads as 0."""
+    _po_check("po_grouping_fwd", (inp, out), (idx,))
+    _po_shape("po_grouping_fwd", inp.dim() == 2 and idx.dim() == 2 and out.numel() == idx.numel() * inp.shape[1])
+    n, c = inp.shape
+    check(lib().doda_po_grouping_fwd(_p(inp), _p(idx), _p(out), n, idx.shape[0], idx.shape[1], c, _stream()), "doda_po_grouping_fwd")
+
+
+def po_grouping_bwd(d_out, start, pos, d_inp):
+    """d_inp [n, c] = per destination the sum, in ascending position, of the rows of d_out [m * nsample, c]."""
+    _po_check("po_grouping_bwd", (d_out, d_inp))
+    n, c = d_inp.shape
+    total = d_out.numel() // max(c, 1)
+    _po_shape("po_grouping_bwd", d_inp.dim() == 2 and d_out.numel() == total * c)
+    _po_transposed_ok("po_grouping_bwd", start, pos, n, total)
+    check(lib().doda_po_grouping_bwd(_p(d_out), _p(start), _p(pos), _p(d_inp), n, total, c, _stream()), "doda_po_grouping_bwd")
+
+
+def po_interpolation_fwd(inp, idx, w, out):
+    """out [m, c] = sum_i inp[idx[r, i]] * w[r, i], i ascending (inp [n, c], idx / w [m, k])."""
+    _po_check("po_interpolation_fwd", (inp, w, out), (idx,))
+    _po_shape("po_interpolation_fwd", inp.dim() == 2 and idx.dim() == 2 and w.shape == idx.shape
+              and out.shape == (idx.shape[0], inp.shape[1]))
+    n, c = inp.shape
+    check(lib().doda_po_interpolation_fwd(_p(inp), _p(idx), _p(w), _p(out), n, idx.shape[0], idx.shape[1], c, _stream()),
+          "doda_po_interpolation_fwd")
+
+
+def po_interpolation_bwd(d_out, w, start, pos, d_inp):
+    """d_inp [n, c] = per destination the sum, in ascending position p, of d_out[p // k] * w.view(-1)[p]."""
+    _po_check("po_interpolation_bwd", (d_out, w, d_inp))
+    _po_shape("po_interpolation_bwd", d_out.dim() == 2 and w.dim() == 2 and d_inp.dim() == 2 and w.shape[0] == d_out.shape[0]
+              and d_inp.shape[1] == d_out.shape[1])
+    (m, k), (n, c) = w.shape, d_inp.shape
+    _po_transposed_ok("po_interpolation_bwd", start, pos, n, m * k)
+    check(lib().doda_po_interpolation_bwd(_p(d_out), _p(w), _p(start), _p(pos), _p(d_inp), n, m, k, c, _stream()),
+          "doda_po_interpolation_bwd")
+
+
+def po_subtraction_fwd(a, b, idx, out):
+    """out [m, nsample, c] = a[r] - b[idx[r, i]] (a [m, c], b [n, c])."""
+    _po_check("po_subtraction_fwd", (a, b, out), (idx,))
+    _po_shape("po_subtraction_fwd", a.dim() == 2 and b.dim() == 2 and idx.dim() == 2 and a.shape[1] == b.shape[1]
+              and idx.shape[0] == a.shape[0] and out.numel() == idx.numel() * a.shape[1])
+    check(lib().doda_po_subtraction_fwd(_p(a), _p(b), _p(idx), _p(out), b.shape[0], a.shape[0], idx.shape[1], a.shape[1], _stream()),
+          "doda_po_subtraction_fwd")
+
+
+def po_subtraction_bwd(d_out, start, pos, d_a, d_b):
+    """d_a [m, c] = sum_i d_out[r, i], i ascending; d_b [n, c] = per destination the sum of -d_out[p] in ascending position."""
+    _po_check("po_subtraction_bwd", (d_out, d_a, d_b))
+    _po_shape("po_subtraction_bwd", d_out.dim() == 3 and d_a.shape == (d_out.shape[0], d_out.shape[2]) and d_b.dim() == 2
+              and d_b.shape[1] == d_out.shape[2])
+    m, nsample, c = d_out.shape
+    _po_transposed_ok("po_subtraction_bwd", start, pos, d_b.shape[0], m * nsample)
+    check(lib().doda_po_subtraction_bwd(_p(d_out), _p(start), _p(pos), _p(d_a), _p(d_b), d_b.shape[0], m, nsample, c, _stream()),
+          "doda_po_subtraction_bwd")
+
+
+def _po_aggregation_sizes(what, inp, position, w, idx):
+    _po_shape(what, inp.dim() == 2 and position.dim() == 3 and w.dim() == 3 and idx.shape == position.shape[:2]
+              and w.shape[:2] == position.shape[:2] and position.shape[2] == inp.shape[1] and w.shape[2] >= 1)
+    m, nsample, c = position.shape
+    return inp.shape[0], m, nsample, c, w.shape[2]
+
+
+def po_aggregation_fwd(inp, position, w, idx, out):
+    """out [m, c] = sum_i (inp[idx[r, i]] + position[r, i]) * w[r, i, ch % w_c], i ascending."""
+    _po_check("po_aggregation_fwd", (inp, position, w, out), (idx,))
+    n, m, nsample, c, w_c = _po_aggregation_sizes("po_aggregation_fwd", inp, position, w, idx)
+    _po_shape("po_aggregation_fwd", out.shape == (m, c))
+    check(lib().doda_po_aggregation_fwd(_p(inp), _p(position), _p(w), _p(idx), _p(out), n, m, nsample, c, w_c, _stream()),
+          "doda_po_aggregation_fwd")
+
+
+def po_aggregation_bwd(inp, position, w, idx, start, pos, d_out, d_inp, d_position, d_w):
+    """The three gradients of po_aggregation_fwd (include/doda_pointops.h states each sum's order)."""
+    _po_check("po_aggregation_bwd", (inp, position, w, d_out, d_inp, d_position, d_w), (idx,))
+    n, m, nsample, c, w_c = _po_aggregation_sizes("po_aggregation_bwd", inp, position, w, idx)
+    _po_shape("po_aggregation_bwd", d_out.shape == (m, c) and d_inp.shape == inp.shape and d_position.shape == position.shape
+              and d_w.shape == w.shape)
+    _po_transposed_ok("po_aggregation_bwd", start, pos, n, m * nsample)
+    check(lib().doda_po_aggregation_bwd(_p(inp), _p(position), _p(w), _p(idx), _p(start), _p(pos), _p(d_out), _p(d_inp),
+                                        _p(d_position), _p(d_w), n, m, nsample, c, w_c, _stream()), "doda_po_aggregation_bwd")
+
+
+def po_furthestsampling(xyz, offset, new_offset, tmp, idx):
+    """idx int32 [m]: furthest point sampling of xyz [n, dim] per batch segment; offset / new_offset int32 [B] are END offsets.  tmp:
+    float32 [n] workspace, initialised by the kernel.  Ties go to the lowest point index (include/doda_pointops.h)."""
+    _po_check("po_furthestsampling", (xyz, tmp), (offset, new_offset, idx))
+    _po_shape("po_furthestsampling", xyz.dim() == 2 and tmp.numel() >= xyz.shape[0] and offset.numel() == new_offset.numel())
+    check(lib().doda_po_furthestsampling(_p(xyz), _p(offset), _p(new_offset), _p(tmp), _p(idx), xyz.shape[0], idx.numel(),
+                                         offset.numel(), xyz.shape[1], _stream()), "doda_po_furthestsampling")

@@ -11,6 +11,9 @@ import numpy as np
 import torch
 
 from ._lib import LOVASZ_MAX_POINTS_PER_VOXEL, DodaNativeError, check, lib  # noqa: F401
+from ._lib import (CX_BNBWD, CX_BNFWD, CX_F_ACCUM, CX_F_BARRIER, CX_F_IDENTITY, CX_F_RELU, CX_F_TRAINING, CX_GEMM, CX_STATS,  # noqa: F401
+                   PACK_DESC, STATS_SLOTS, WGRAD_ACCUMULATE)
+from ._lib import ConvEpilogue as _ConvEpilogue, CxOp as _CxOp, SgdTensor as _SgdTensor, WgradJob as _WgradJob
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -312,9 +315,6 @@ def _feat_ok(x, name):
         raise RuntimeError("%s must be a contiguous [rows, channels] tensor" % name)
 
 
-STATS_SLOTS = 8     # DODA_STATS_SLOTS
-
-
 def totals_zeros(nc, device):
     """Zeroed fp64 totals for nc channels in the library's layout (doda_conv_epilogue.stats_totals): [8 slots, 2 sums, nc / 4
     groups, 16] — a 128-byte line per four channels, the first four doubles of a group used."""
@@ -333,15 +333,6 @@ def totals_from_rows(rows):
     for k in range(n):
         t[k % STATS_SLOTS, :, :, :4] += rows[k].double().view(2, nc // 4, 4)
     return t
-
-
-class _ConvEpilogue(C.Structure):   # doda_conv_epilogue (include/doda_hip.h, ABI 11)
-    _fields_ = [("residual", C.c_void_p), ("stats", C.c_void_p), ("stats_rows_h", C.POINTER(C.c_int32)),
-                ("bn_x", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_invstd", C.c_void_p), ("bn_gamma", C.c_void_p),
-                ("bn_beta", C.c_void_p), ("bn_relu", C.c_int32), ("tilebook_rows", C.c_int32),
-                ("tilebook", C.c_void_p), ("residual_bcast", C.c_int32), ("stats_totals", C.c_void_p),
-                ("x_ld", C.c_int32), ("y_ld", C.c_int32), ("residual_ld", C.c_int32), ("bn_x_ld", C.c_int32),   # ABI 11: row strides
-                ("prologue", C.c_void_p)]                                                                         # ABI 11: doda_conv_prologue *
 
 
 def tilebook_build(tbl, n_rows=None):
@@ -471,9 +462,7 @@ class PackPlan:
         n = len(entries)
         dsz = l.doda_spconv_pack_desc_bytes()
         assert dsz == 48
-        desc = np.zeros(n, dtype=np.dtype([("w", "<u8"), ("out", "<u8"), ("K", "<i4"), ("kc", "<i4"),
-                                           ("nc", "<i4"), ("layout", "<i4"), ("esz", "<i4"),
-                                           ("n_chunk", "<i4"), ("NB", "<i4"), ("pad", "<i4")]))
+        desc = np.zeros(n, dtype=PACK_DESC)
         self.outputs = []
         for k, (w, K, kc, nc, layout, esz) in enumerate(entries):
             if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == K * kc * nc):
@@ -493,19 +482,6 @@ class PackPlan:
     def run(self):
         check(lib().doda_spconv_pack_multi(_p(self.desc_dev), _p(self.blk_dev), self.n, self.total,
                                            _stream()), "doda_spconv_pack_multi")
-
-
-class _WgradJob(C.Structure):   # doda_wgrad_job (include/doda_hip.h, ABI 2)
-    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("tbl", C.c_void_p), ("dw", C.c_void_p),
-                ("ca", C.c_int32), ("cb", C.c_int32), ("ld", C.c_int32), ("K", C.c_int32),
-                ("n_rows", C.c_int32), ("elem_bytes", C.c_int32),
-                ("pair_in", C.c_void_p), ("pair_out", C.c_void_p), ("pair_num", C.c_void_p),
-                ("pair_ld", C.c_int32), ("n_a", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
-                ("pair_seg", C.c_void_p), ("pair_seg_nt", C.c_int32), ("reserved2", C.c_int32),
-                ("tilebook", C.c_void_p)]
-
-
-WGRAD_ACCUMULATE = 1
 
 
 class WgradPlan:
@@ -1239,11 +1215,6 @@ def eval_score(feats, weight, bias, p2v, idx, labels_all, ignore_index, hist, wa
     return out, pred
 
 
-class _SgdTensor(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("n", C.c_int64),
-                ("first_step", C.c_int32), ("reserved", C.c_int32)]
-
-
 def sgd_multi(params, grads, bufs, first, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
               maximize=False):
     """torch.optim.SGD's update of all (param, grad, momentum buffer) triples in one launch (doda_sgd_multi).
@@ -1308,24 +1279,10 @@ def optim_step(kind, params, grads, state1, state2, bc1, bc2s, first, lr, beta1,
 
 
 # ---- coarse-level op lists (ABI 11, csrc/layers.hip: doda_layers_run) --------------------------------------
-CX_GEMM, CX_BNFWD, CX_BNBWD, CX_STATS = 1, 2, 3, 4
-# widest BatchNorm op the list takes (csrc/bn_totals.hpp BN_TOT_MAX_C = PRE_MAX_C: the LDS channel vectors of lay_bn / bn_apply and
-# of the folded gather prologue); a list with a wider one is refused with DODA_ERR_UNSUPPORTED before anything launches
+# the CX_* kinds and flags are _lib's (doda_hip.h).  Widest BatchNorm op the list takes (csrc/bn_totals.hpp BN_TOT_MAX_C = PRE_MAX_C:
+# the LDS channel vectors of lay_bn / bn_apply and of the folded gather prologue); a list with a wider one is refused with
+# DODA_ERR_UNSUPPORTED before anything launches
 CX_BN_MAX_C = 256
-CX_F_BARRIER, CX_F_IDENTITY, CX_F_RELU, CX_F_TRAINING, CX_F_ACCUM = 1, 2, 4, 8, 16
-
-
-class _CxOp(C.Structure):   # doda_cx_op
-    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("rows", C.c_int32), ("rows_in", C.c_int32),
-                ("c_in", C.c_int32), ("c_out", C.c_int32), ("K", C.c_int32), ("tbl_ld", C.c_int32),
-                ("x_ld", C.c_int32), ("y_ld", C.c_int32), ("res_ld", C.c_int32), ("aux_ld", C.c_int32),
-                ("y2_ld", C.c_int32), ("n_part", C.c_int32), ("c_split", C.c_int32), ("reserved", C.c_int32),
-                ("eps", C.c_float), ("momentum", C.c_float),
-                ("x", C.c_void_p), ("w", C.c_void_p), ("tbl", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p),
-                ("res", C.c_void_p), ("aux", C.c_void_p), ("stats", C.c_void_p), ("stats_b", C.c_void_p),
-                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p),
-                ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("nbt", C.c_void_p),
-                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("tilebook", C.c_void_p)]
 
 
 def _cx_array(ops, n_part):

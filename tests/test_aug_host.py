@@ -2,7 +2,6 @@
 doda_amd.aug against what the reference's own DataAugmentor computed (tests/golden/aug_golden.npz, made by
 tests/golden/make_aug_golden.py), the configuration and the command line."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,29 +9,6 @@ import pytest
 from tests import aug_cases as ac
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_aug_header_symbols_exported_and_other_abis_unchanged(native_lib):
-    from doda_amd import _lib
-    aug = _declared("doda_aug.h")
-    assert aug == set(_lib.AUG_SYMBOLS) and all(n.startswith("doda_aug_") for n in aug)
-    for name in aug:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_aug_abi_version() == 1 == _lib.AUG_ABI_VERSION
-    core, st, mix = _declared("doda_hip.h"), _declared("doda_selftrain.h"), _declared("doda_mix.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70
-    assert st == set(_lib.SELFTRAIN_SYMBOLS) and len(st) == 5 and mix == set(_lib.MIX_SYMBOLS) and len(mix) == 6
-    assert not (core & aug) and not (st & aug) and not (mix & aug)
-    assert native_lib.doda_abi_version() == 12 and native_lib.doda_st_abi_version() == 1 and native_lib.doda_mix_abi_version() == 1
-    text = open(os.path.join(ROOT, "include", "doda_aug.h")).read()
-    assert re.search(r"#define DODA_AUG_MAX_SEGMENTS %d\b" % _lib.AUG_MAX_SEGMENTS, text)
-    assert re.search(r"#define DODA_AUG_CHUNK %d\b" % _lib.AUG_CHUNK, text)
-    assert re.search(r"#define DODA_AUG_MAX_GRID_CELLS \(1 << 24\)", text) and _lib.AUG_MAX_GRID_CELLS == 1 << 24
 
 
 def test_aug_entry_points_report_bad_arguments(native_lib):

@@ -1,34 +1,11 @@
 """Full-cloud evaluation, host side (no GPU): the companion C ABI include/doda_eval.h, argument errors as statuses, the seeded
 subsample and the collated `*_all` keys (reference dataset/dataset.py:74-77, dataset/s3dis.py:96-130), the sharding of scenes over
 ranks and the `python -m doda_amd.test` command line (reference tool/test.py)."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 from tests import eval_cases as ec
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_eval_header_symbols_exported_and_core_abi_unchanged(native_lib):
-    from doda_amd import _lib
-    ev = _declared("doda_eval.h")
-    assert ev == set(_lib.EVAL_SYMBOLS) and all(name.startswith("doda_eval_") for name in ev)
-    for name in ev:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_eval_abi_version() == 1 == _lib.EVAL_ABI_VERSION
-    core = _declared("doda_hip.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and not (core & ev)
-    assert C.sizeof(_lib.EvalScene) == 44
 
 
 def _scene(n_end, m_end, dims=(1, 1, 1), base=0, side=0.08):

@@ -4,7 +4,6 @@ plain torch optimizers, the fallback conditions, and the fp64 restatement of tes
 import copy
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,28 +12,6 @@ import torch
 from tests import optim_cases as oc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_optim_header_symbols_exported_and_core_abi_unchanged(native_lib):
-    from doda_amd import _lib
-    opt = _declared("doda_optim.h")
-    assert opt == set(_lib.OPTIM_SYMBOLS) and all(name.startswith("doda_optim_") for name in opt)
-    for name in opt:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_optim_abi_version() == 1 == _lib.OPTIM_ABI_VERSION
-    core = _declared("doda_hip.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and not (core & opt) and native_lib.doda_abi_version() == 12
-    text = open(os.path.join(ROOT, "include", "doda_optim.h")).read()
-    assert re.search(r"#define DODA_OPTIM_TILE %d\b" % _lib.OPTIM_TILE, text) and _lib.OPTIM_TILE == oc.TILE
-    assert re.search(r"#define DODA_OPTIM_NORM_BLOCKS %d\b" % _lib.OPTIM_NORM_BLOCKS, text) and _lib.OPTIM_NORM_BLOCKS == oc.NORM_BLOCKS
-    for k, name in enumerate(("SGD", "ADAM", "ADAMW")):
-        assert re.search(r"#define DODA_OPTIM_%s %d\b" % (name, k), text) and getattr(_lib, "OPTIM_" + name) == k
-    assert C.sizeof(_lib.OptimTensor) == 64 and C.sizeof(_lib.OptimHyper) == 48
 
 
 def test_optim_entry_points_report_bad_arguments(native_lib):

@@ -2,8 +2,6 @@
 against the restatement of tests/pgops_cases.py (cluster order and order inside a cluster), the two restatements against each other
 on symmetric graphs, the wrappers' shapes and dtypes, and the restatement of sec_mean against its float64 bound."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,28 +9,7 @@ import torch
 
 from tests import pgops_cases as pc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAPHS = pc.graph_cases()
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_pgops_header_symbols_exported_and_core_abi_unchanged(native_lib):
-    from doda_amd import _lib
-    pg = _declared("doda_pgops.h")
-    assert pg == set(_lib.PGOPS_SYMBOLS) and all(name.startswith("doda_pg") for name in pg) and len(pg) == 11
-    for name in pg:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_pgops_abi_version() == 1 == _lib.PGOPS_ABI_VERSION
-    core = _declared("doda_hip.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and not (core & pg) and native_lib.doda_abi_version() == 12
-    text = open(os.path.join(ROOT, "include", "doda_pgops.h")).read()
-    assert re.search(r"#define DODA_PG_WAVE_LIST %d\b" % _lib.PG_WAVE_LIST, text)
-    assert re.search(r"#define DODA_PG_IOU_LDS_INSTANCES %d\b" % _lib.PG_IOU_LDS_INSTANCES, text)
-    assert re.search(r"#define DODA_PG_LONG_SEGMENT %d\b" % _lib.PG_LONG_SEGMENT, text) and _lib.PG_LONG_SEGMENT == pc.LONG_SEGMENT
 
 
 def test_pgops_entry_points_report_bad_arguments(native_lib):

@@ -1,41 +1,12 @@
 """pointops, host side (no GPU): the companion C ABI include/doda_pointops.h and its argument errors, the `pointops2_cuda` surface,
 and the restatements of tests/pointops_cases.py against float64 and against the reference's tie rule."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 from tests import pointops_cases as pc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, WORKSPACE = -1, -5
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_pointops_header_symbols_exported_and_other_abis_unchanged(native_lib):
-    from doda_amd import _lib
-    po = _declared("doda_pointops.h")
-    assert po == set(_lib.POINTOPS_SYMBOLS) and all(name.startswith("doda_po") for name in po) and len(po) == 12
-    for name in po:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_pointops_abi_version() == 1 == _lib.POINTOPS_ABI_VERSION
-    core, pg = _declared("doda_hip.h"), _declared("doda_pgops.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and native_lib.doda_abi_version() == 12
-    assert pg == set(_lib.PGOPS_SYMBOLS) and len(pg) == 11 and native_lib.doda_pgops_abi_version() == 1
-    assert not (core & po) and not (pg & po)
-    text = open(os.path.join(ROOT, "include", "doda_pointops.h")).read()
-    for name, value in (("WAVE_LIST", _lib.PO_WAVE_LIST), ("FPS_BLOCK", _lib.PO_FPS_BLOCK), ("FPS_REG", _lib.PO_FPS_REG),
-                        ("FPS_MAX_DIM", _lib.PO_FPS_MAX_DIM)):
-        assert re.search(r"#define DODA_PO_%s %d\b" % (name, value), text), name
-    assert (_lib.PO_WAVE_LIST, _lib.PO_FPS_BLOCK, _lib.PO_FPS_REG) == (pc.WAVE_LIST, pc.FPS_BLOCK, pc.FPS_REG)
-    assert "deliberate fix" in text and "TIES GO TO THE LOWEST POINT INDEX" in text
 
 
 def _calls(lib):

@@ -16,25 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = sc.cases()
 
 
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_subsample_header_symbols_exported_and_core_abi_unchanged(native_lib):
-    from doda_amd import _lib
-    sub = _declared("doda_subsample.h")
-    assert sub == set(_lib.SUBSAMPLE_SYMBOLS) and all(name.startswith("doda_subsample_") for name in sub)
-    for name in sub:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_subsample_abi_version() == 1 == _lib.SUBSAMPLE_ABI_VERSION
-    core = _declared("doda_hip.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and not (core & sub) and native_lib.doda_abi_version() == 12
-    text = open(os.path.join(ROOT, "include", "doda_subsample.h")).read()
-    assert re.search(r"#define DODA_SUBSAMPLE_MAX_SEGMENTS %d\b" % _lib.SUBSAMPLE_MAX_SEGMENTS, text) and _lib.SUBSAMPLE_MAX_SEGMENTS >= 32
-    assert re.search(r"#define DODA_SUBSAMPLE_CHUNK %d\b" % _lib.SUBSAMPLE_CHUNK, text)
-
-
 def test_subsample_entry_points_report_bad_arguments(native_lib):
     """Argument errors come back as statuses before anything is launched; nothing to keep is nothing to do."""
     lib = native_lib

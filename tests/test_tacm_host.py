@@ -1,37 +1,10 @@
 """Tail-aware cuboid mixing, host side (no GPU): the companion C ABI include/doda_mix.h, the mixing plan and the split sampler of
 doda_amd.tacm against what the reference's own tacm() / SplitSampler computed (tests/golden/tacm_golden.npz, made by
 tests/golden/make_tacm_golden.py), the new config and the command line."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from tests import tacm_cases as tc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    return set(re.findall(r"\b(doda_[a-z0-9_]+)\s*\(", text))
-
-
-def test_mix_header_symbols_exported_and_other_abis_unchanged(native_lib):
-    from doda_amd import _lib
-    mix = _declared("doda_mix.h")
-    assert mix == set(_lib.MIX_SYMBOLS) and all(n.startswith("doda_mix_") for n in mix)
-    for name in mix:
-        assert hasattr(native_lib, name), name
-    assert native_lib.doda_mix_abi_version() == 1
-    core, st = _declared("doda_hip.h"), _declared("doda_selftrain.h")
-    assert core == set(_lib.EXPORTED_SYMBOLS) and len(core) == 70 and st == set(_lib.SELFTRAIN_SYMBOLS) and len(st) == 5
-    assert not (core & mix) and not (st & mix)
-    assert native_lib.doda_abi_version() == 12 and native_lib.doda_st_abi_version() == 1
-    text = open(os.path.join(ROOT, "include", "doda_mix.h")).read()
-    for name, val in (("MAX_SEGMENTS", _lib.MIX_MAX_SEGMENTS), ("MAX_CUBOIDS", _lib.MIX_MAX_CUBOIDS), ("MAX_CLASSES", _lib.MIX_MAX_CLASSES),
-                      ("CHUNK", _lib.MIX_CHUNK), ("FIXED_BITS", _lib.MIX_FIXED_BITS)):
-        assert re.search(r"#define DODA_MIX_%s %d\b" % (name, val), text), name
 
 
 def test_mix_entry_points_report_bad_arguments(native_lib):

@@ -295,6 +295,21 @@ ABIS.append(Abi("doda_pointops.h", "doda_pointops_abi_version", 1, "pointops ABI
     "doda_po_furthestsampling": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
 }, constants=_named("PO_WAVE_LIST", "PO_FPS_BLOCK", "PO_FPS_REG", "PO_FPS_MAX_DIM")))
 
+# ---- include/doda_vss.h: virtual scan simulation --------------------------------------------------------------------------------
+VSS_MAX_SEGMENTS, VSS_CHUNK, VSS_MAX_GRID, VSS_EXHAUSTIVE, VSS_KEY_NONE = 64, 1024, 64, 1, 0x7fffffff
+ABIS.append(Abi("doda_vss.h", "doda_vss_abi_version", 1, "virtual-scan ABI", {
+    "doda_vss_abi_version": (c_i32, []),
+    "doda_vss_blocks": (c_i64, [c_i64p, c_i32]),
+    "doda_vss_bounds": (c_i32, [c_vp, c_vp, c_i64p, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "doda_vss_image": (c_i32, [c_vp, c_vp, c_i64p, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "doda_vss_view": (c_i32, [c_vp, c_vp, c_i64p, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "doda_vss_flip": (c_i32, [c_vp, c_i64p, c_i32, c_vp, c_vp, c_f64p, c_vp, c_vp, c_vp]),
+    "doda_vss_extreme": (c_i32, [c_vp, c_vp, c_i32p, c_i32, c_vp, c_f64p, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "doda_vss_count": (c_i32, [c_vp, c_i64p, c_i32, c_vp, c_vp, c_vp]),
+    "doda_vss_emit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64p, c_i32, c_vp, c_vp, c_i64p, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                              c_vp]),
+}, constants=_named("VSS_MAX_SEGMENTS", "VSS_CHUNK", "VSS_MAX_GRID", "VSS_EXHAUSTIVE", "VSS_KEY_NONE")))
+
 _lib = None
 
 

@@ -10,14 +10,15 @@ The reference augments every sample with numpy / scipy in DataLoader workers.  H
                                 jitter randn(3, 3), flip rand, rotation rand + 3 rand, elastic rand, 3 randn(bb) per pass,
                                 rand(3) per crop iteration
 
-`shuffle` is accepted and does nothing (a row permutation of the points: DESIGN.md §2); `vss` raises NotImplementedError.
-Deviations from the reference are listed in DESIGN.md §13."""
+`shuffle` is accepted and does nothing (a row permutation of the points: DESIGN.md §2).  `vss` is accepted as the FIRST entry (where
+every reference config has it: it needs the untransformed scene in metres, z up) and runs before everything else (doda_amd.vss);
+anywhere else it raises NotImplementedError.  Deviations from the reference are listed in DESIGN.md §13."""
 import math
 
 import numpy as np
 import torch
 
-from . import _lib, segments
+from . import _lib, segments, vss
 from ._lib import check, lib
 from .segments import SeededDraws, launch_on, offsets_h, per_sample, stream_handle   # noqa: F401  (SeededDraws: for the callers)
 
@@ -55,39 +56,48 @@ class AugConfig:
     (voxel_scale, full_scale, max_npoint, point_range).  No DATA_AUG.aug_list, or DATA_AUG.enabled false, is a disabled one."""
 
     def __init__(self, aug_list=None, scene_aug=None, elastic=None, voxel_scale=50, full_scale=(128, 512), max_npoint=250000,
-                 point_range=200000000, enabled=True):
+                 point_range=200000000, enabled=True, vss_section=None, class_names=None, ignore_label=255):
         self.aug_list = [str(a) for a in (aug_list or [])]
         self.enabled = bool(enabled) and len(self.aug_list) > 0
-        for a in self.aug_list:
+        for k, a in enumerate(self.aug_list):
             if a == "vss":
-                raise NotImplementedError("DATA_AUG.aug_list: vss (virtual scan simulation) is not implemented on the device")
+                if k != 0:
+                    raise NotImplementedError("DATA_AUG.aug_list: vss (virtual scan simulation) must come first in the list: it "
+                                              "works on the untransformed scene (metres, z up)")
+                continue
             if a not in KNOWN:
                 raise ValueError("DATA_AUG.aug_list: unknown entry %r (known: %s)" % (a, ", ".join(KNOWN)))
         self.scene_aug, self.elastic = scene_aug, elastic
         self.voxel_scale, self.full_scale = voxel_scale, [int(v) for v in full_scale]
         self.max_npoint, self.point_range = int(max_npoint), point_range
+        self.vss_section, self.class_names, self.ignore_label = vss_section, list(class_names or []), int(ignore_label)
+        # the vss stage: the section where the list names it (first), a disabled configuration otherwise
+        self.vss = vss.VssConfig(vss_section if (self.enabled and "vss" in self.aug_list) else None, self.class_names, self.ignore_label)
         if self.enabled and "elastic" in self.aug_list and check_key(self.elastic):
             for gran_fac, _ in self.elastic["value"]:
                 if not gran_fac * self.voxel_scale // 50 >= 1:
                     raise ValueError("DATA_AUG.elastic: granularity %s * voxel_scale // 50 is below one voxel" % gran_fac)
 
     @classmethod
-    def from_cfg(cls, data_cfg):
-        """From a dataset config (cfg.DATA_CONFIG or cfg.DATA_CONFIG_TAR)."""
+    def from_cfg(cls, data_cfg, class_names=None):
+        """From a dataset config (cfg.DATA_CONFIG or cfg.DATA_CONFIG_TAR).  class_names: the names the labels carry where a class
+        mapper replaced the dataset's own (DATA_CLASS.class_names otherwise); only vss reads them."""
         proc = data_cfg.get("DATA_PROCESSOR", {}) or {}
-        kw = dict(voxel_scale=proc.get("voxel_scale", 50), full_scale=proc.get("full_scale", [128, 512]),
+        klass = data_cfg.get("DATA_CLASS", {}) or {}
+        kw = dict(class_names=class_names or klass.get("class_names", None), ignore_label=klass.get("ignore_label", 255),
+                  voxel_scale=proc.get("voxel_scale", 50), full_scale=proc.get("full_scale", [128, 512]),
                   max_npoint=proc.get("max_npoint", 250000), point_range=proc.get("point_range", 200000000))
         sec = data_cfg.get("DATA_AUG", None)
         if sec is None or "aug_list" not in sec:
             return cls(enabled=False, **kw)
         return cls(aug_list=sec["aug_list"], scene_aug=sec.get("scene_aug", None), elastic=sec.get("elastic", None),
-                   enabled=sec.get("enabled", True), **kw)
+                   enabled=sec.get("enabled", True), vss_section=sec.get("vss", None), **kw)
 
     def with_list(self, aug_list):
         """The same configuration under another aug_list (the cuboid-mixing dataset's [elastic, crop, shuffle],
         dataset/mix_dataset.py:18)."""
         return AugConfig(aug_list, self.scene_aug, self.elastic, self.voxel_scale, self.full_scale, self.max_npoint,
-                         self.point_range, self.enabled)
+                         self.point_range, self.enabled, self.vss_section, self.class_names, self.ignore_label)
 
 
 # ------------------------------------------------------------------------------------------------ randomness
@@ -107,6 +117,11 @@ class RandomStateDraws:
         shape = tuple(int(v) for v in shape)
         self.log.append(("randn", int(np.prod(shape))))
         return self.rs.randn(*shape)
+
+    def randint(self, n):
+        """numpy.random.randint(n), which numpy.random.choice(n) draws too."""
+        self.log.append(("randint", 1))
+        return int(self.rs.randint(int(n)))
 
 
 # ------------------------------------------------------------------------------------------------ the plan (host, fp64)
@@ -351,7 +366,8 @@ def augment_batch(xyz_mid, labels, offsets, cfg, draws, masks=None, stream=None,
     small read-backs block the calling thread only — the loader thread).
     -> the dictionary DeviceScenes._finish returns without "id": locs32 int32 [M, 4] (batch index batch0 + b, voxel
     coordinates), locs_float fp32 [M, 3], labels32 int32 [M], offsets int32 [B + 1], spatial_shape; plus mask1 / mask2 when masks
-    were given.  Raises EmptySample when a sample keeps no point."""
+    were given.  Raises EmptySample when a sample keeps no point.  With `vss` first in the list the virtual scans run first
+    (doda_amd.vss.run: occlusion + jitter, compacted) and the rest of the list sees their output."""
     if not cfg.enabled:
         raise ValueError("augment_batch: the configuration has no DATA_AUG.aug_list")
     B = len(offsets) - 1
@@ -360,6 +376,12 @@ def augment_batch(xyz_mid, labels, offsets, cfg, draws, masks=None, stream=None,
     draws = per_sample(draws, B, "augment_batch")
     assert xyz_mid.is_cuda and xyz_mid.dtype == torch.float32 and xyz_mid.dim() == 2 and xyz_mid.shape[1] == 3
     assert int(offsets[-1]) == xyz_mid.shape[0] == labels.shape[0]
-    xyz_mid, labels = xyz_mid.contiguous(), labels.to(torch.int32).contiguous()
+    xyz_mid, labels, offsets = xyz_mid.contiguous(), labels.to(torch.int32).contiguous(), [int(v) for v in offsets]
     with launch_on(stream):
-        return _run(xyz_mid, labels, [int(v) for v in offsets], cfg, draws, masks, stream, return_debug, batch0)
+        scan = vss.run(xyz_mid, labels, offsets, cfg.vss, draws, masks, stream, return_debug) if cfg.vss.enabled else None
+        if scan is not None:     # the rest of the list sees the scanned, jittered samples
+            xyz_mid, labels, offsets, masks = scan["xyz"], scan["labels"], scan["offsets"], scan["masks"]
+        out = _run(xyz_mid, labels, offsets, cfg, draws, masks, stream, return_debug, batch0)
+        if return_debug:
+            out["debug"]["vss"] = scan
+        return out

@@ -64,6 +64,9 @@ class SeededDraws:
     def randn(self, shape):
         return self.g.standard_normal(tuple(int(v) for v in shape))
 
+    def randint(self, n):
+        return int(self.g.integers(int(n)))
+
     def permutation(self, n):
         return self.g.permutation(n)
 

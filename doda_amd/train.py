@@ -306,12 +306,16 @@ def make_loader(cfg, args, device, rank, world, epoch, split="train"):
 
 # ------------------------------------------------------------------------------------------------ training
 
-def aug_config_of(cfg, split):
+def aug_config_of(cfg, split, class_names=None):
     """doda_amd.aug.AugConfig of a split's dataset config: DATA_CONFIG_TAR for the target split (where the experiment has one),
-    DATA_CONFIG otherwise.  No DATA_AUG.aug_list there = disabled = the loaders' own rigid augmentation."""
+    DATA_CONFIG otherwise.  No DATA_AUG.aug_list there = disabled = the loaders' own rigid augmentation.  class_names: the names
+    of the split's labels where a class mapper gave them (vss looks up wall / floor / ceiling); otherwise COMMON_CLASSES' names
+    where the dataset config has none of its own."""
     from .aug import AugConfig
     key = "DATA_CONFIG_TAR" if (split == "target" and "DATA_CONFIG_TAR" in cfg) else "DATA_CONFIG"
-    return AugConfig.from_cfg(cfg[key])
+    own = (cfg[key].get("DATA_CLASS", {}) or {}).get("class_names", None)
+    common = (cfg.get("COMMON_CLASSES", {}) or {}).get("class_names", None)
+    return AugConfig.from_cfg(cfg[key], class_names=list(class_names or own or common or []))
 
 
 def check_aug_loader(cfg, args):
@@ -442,14 +446,15 @@ class Trainer:
                 src = self._datasets["train"]
                 dsc = MixedDeviceScenes(ds.paths, src.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank,
                                         self.world, self.device, self.tacm, self.split_sampler, augment=ds.augment, shuffle=True,
-                                        full_scale0=fs0, source_seed=src.seed + seed + 1, aug_cfg=aug_config_of(self.cfg, split),
+                                        full_scale0=fs0, source_seed=src.seed + seed + 1,
+                                        aug_cfg=aug_config_of(self.cfg, split, getattr(ds, "class_names", None)),
                                         downsampling_scale=downsampling_scale_of(self.cfg, split),
                                         source_downsampling_scale=downsampling_scale_of(self.cfg, "train"))
                 self._loaders[split] = (dsc, dsc)
             else:
                 dsc = DeviceScenes(ds.paths, ds.length, ds.voxel_scale, ds.seed + seed, self.args.batch_size, self.rank, self.world,
                                    self.device, augment=ds.augment, shuffle=split != "val",
-                                   full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split),
+                                   full_scale0=fs0, aug_cfg=aug_config_of(self.cfg, split, getattr(ds, "class_names", None)),
                                    downsampling_scale=downsampling_scale_of(self.cfg, split), subsample_seed=seed, min_extent=min_extent)
                 self._loaders[split] = (dsc, dsc)
             if split in self._labels:

@@ -310,6 +310,24 @@ ABIS.append(Abi("doda_vss.h", "doda_vss_abi_version", 1, "virtual-scan ABI", {
                               c_vp]),
 }, constants=_named("VSS_MAX_SEGMENTS", "VSS_CHUNK", "VSS_MAX_GRID", "VSS_EXHAUSTIVE", "VSS_KEY_NONE")))
 
+# ---- include/doda_spconv.h: transposed-conv rulebook, max pooling by element size, dense volume <-> rows -----------------------------
+SPCONV_MAX_KERNEL_VOLUME, SPCONV_DENSE_CHUNK = 27, 1024
+_SP_DENSE = (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp])
+ABIS.append(Abi("doda_spconv.h", "doda_spconv_abi_version", 1, "spconv-surface ABI", {
+    "doda_spconv_abi_version": (c_i32, []),
+    "doda_rulebook_deconv_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "doda_rulebook_deconv_assign": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "doda_rulebook_deconv_tables": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32,
+                                            c_vp, c_sz, c_vp]),
+    "doda_maxpool_fwd": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "doda_maxpool_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "doda_dense_scatter": _SP_DENSE,
+    "doda_dense_gather": _SP_DENSE,
+    "doda_from_dense_workspace_bytes": (c_sz, [c_i64]),
+    "doda_from_dense_count": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "doda_from_dense_emit": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+}, constants=_named("SPCONV_MAX_KERNEL_VOLUME", "SPCONV_DENSE_CHUNK")))
+
 _lib = None
 
 

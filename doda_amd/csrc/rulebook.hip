@@ -13,6 +13,7 @@
 // All kernels are HBM/L2-latency-bound integer work: one lane per voxel, coalesced reads of the
 // int4 coordinate rows, coalesced table writes (tbl[o][t] with t across lanes).
 #include "common.hpp"
+#include "../../include/doda_spconv.h"
 #include <stdlib.h>
 
 namespace {
@@ -312,16 +313,26 @@ struct ConvGeo {
     GridDesc out;                 // output spatial shape
 };
 
-// enumeration of getValidOutPos; calls f(rank, ox, oy, oz, offset) for the VALID positions
-template <class F>
+// enumeration of getValidOutPos; calls f(rank, ox, oy, oz, offset) for the VALID positions.
+// TR: the transposed convolution's enumeration instead (include/doda_spconv.h) — upstream's getValidOutPosTranspose order [MEM]:
+// input p reaches q = p * stride - padding + k * dilation, the positions run from the upper bound lower + (k - 1) * dilation
+// downwards, last axis fastest, and the offset index is sum mul * (q - lower) / dilation.  A second enumeration, not a second
+// builder: the touch keys, the first-touch numbering and the tables below are the same code for both.
+template <bool TR, class F>
 __device__ __forceinline__ void for_valid_out(const int4 c, const ConvGeo &g, F f) {
     const int pos[3] = {c.y, c.z, c.w};
     int lo[3], up[3], cs[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = (pos[a] - (g.k[a] - 1) * g.d[a] - 1 + g.s[a] + g.p[a]) / g.s[a];
-        up[a] = (pos[a] + g.p[a]) / g.s[a];
-        cs[a] = (up[a] - lo[a]) / g.d[a] + 1;
+        if (TR) {
+            lo[a] = pos[a] * g.s[a] - g.p[a];
+            up[a] = lo[a] + (g.k[a] - 1) * g.d[a];
+            cs[a] = g.k[a];
+        } else {
+            lo[a] = (pos[a] - (g.k[a] - 1) * g.d[a] - 1 + g.s[a] + g.p[a]) / g.s[a];
+            up[a] = (pos[a] + g.p[a]) / g.s[a];
+            cs[a] = (up[a] - lo[a]) / g.d[a] + 1;
+        }
     }
     const int shape[3] = {g.out.X, g.out.Y, g.out.Z};
     int rank = 0;
@@ -335,7 +346,8 @@ __device__ __forceinline__ void for_valid_out(const int4 c, const ConvGeo &g, F 
                 for (int a = 2; a >= 0; --a) {
                     v[a] = up[a] - cnt[a] * g.d[a];
                     valid &= v[a] >= 0 && v[a] <= shape[a] - 1;
-                    off += mul * (pos[a] - v[a] * g.s[a] + g.p[a]) / g.d[a];
+                    if (TR) off += mul * ((v[a] - lo[a]) / g.d[a]);
+                    else off += mul * (pos[a] - v[a] * g.s[a] + g.p[a]) / g.d[a];
                     mul *= g.k[a];
                 }
                 if (valid) {
@@ -345,17 +357,19 @@ __device__ __forceinline__ void for_valid_out(const int4 c, const ConvGeo &g, F 
             }
 }
 
+template <bool TR>
 __global__ __launch_bounds__(256) void conv_touch(const int4 *__restrict__ indices, int m, ConvGeo g,
                                                   unsigned long long *tab, uint32_t mask, HashFmt hf) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
-    for_valid_out(c, g, [&](int rank, int ox, int oy, int oz, int) {
+    for_valid_out<TR>(c, g, [&](int rank, int ox, int oy, int oz, int) {
         hash_insert_min(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out), (uint32_t)j * (uint32_t)g.K + (uint32_t)rank);
     });
 }
 
 // flag[j*K + rank] = 1 where that candidate is the first touch of its output cell
+template <bool TR>
 __global__ __launch_bounds__(256) void conv_first(const int4 *__restrict__ indices, int m, ConvGeo g,
                                                   const unsigned long long *__restrict__ tab,
                                                   uint32_t mask, HashFmt hf, int32_t *__restrict__ flag) {
@@ -363,7 +377,7 @@ __global__ __launch_bounds__(256) void conv_first(const int4 *__restrict__ indic
     if (j >= m) return;
     const int4 c = indices[j];
     for (int r = 0; r < g.K; ++r) flag[(long long)j * g.K + r] = 0;
-    for_valid_out(c, g, [&](int rank, int ox, int oy, int oz, int) {
+    for_valid_out<TR>(c, g, [&](int rank, int ox, int oy, int oz, int) {
         const uint32_t mine = (uint32_t)j * (uint32_t)g.K + (uint32_t)rank;
         if ((uint32_t)hash_find(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out)) == mine) flag[mine] = 1;
     });
@@ -371,6 +385,7 @@ __global__ __launch_bounds__(256) void conv_first(const int4 *__restrict__ indic
 
 // the first-touch candidates write their output's coordinates and replace the table value (touch
 // key) of their cell by the output id
+template <bool TR>
 __global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indices, int m, ConvGeo g,
                                                    unsigned long long *tab, uint32_t mask, HashFmt hf,
                                                    const int32_t *__restrict__ flag,
@@ -379,7 +394,7 @@ __global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indi
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
-    for_valid_out(c, g, [&](int rank, int ox, int oy, int oz, int) {
+    for_valid_out<TR>(c, g, [&](int rank, int ox, int oy, int oz, int) {
         const long long e = (long long)j * g.K + rank;
         if (!flag[e]) return;
         const int id = rank_of[e];
@@ -392,6 +407,7 @@ __global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indi
 }
 
 // tbl[off][out] = j and tbl_rev[off][j] = out for every (input, output, offset) triple
+template <bool TR>
 __global__ __launch_bounds__(256) void conv_tables(const int4 *__restrict__ indices, int m, ConvGeo g,
                                                    const unsigned long long *__restrict__ tab,
                                                    uint32_t mask, HashFmt hf, int32_t *__restrict__ tbl, int ld_out,
@@ -400,7 +416,7 @@ __global__ __launch_bounds__(256) void conv_tables(const int4 *__restrict__ indi
     if (j >= m) return;
     const int4 c = indices[j];
     for (int o = 0; o < g.K; ++o) tbl_rev[(long long)o * ld_in + j] = -1;
-    for_valid_out(c, g, [&](int, int ox, int oy, int oz, int off) {
+    for_valid_out<TR>(c, g, [&](int, int ox, int oy, int oz, int off) {
         const int out = hash_find(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out));
         tbl_rev[(long long)off * ld_in + j] = out;
         tbl[(long long)off * ld_out + out] = j;
@@ -640,6 +656,66 @@ bool make_geo(const int32_t *shape, const int32_t *k, const int32_t *s, const in
     g->out = GridDesc{o[0], o[1], o[2]};
     return true;
 }
+
+// transposed geometry: out = (in - 1) * stride - 2 * padding + kernel + output_padding (include/doda_spconv.h)
+bool make_geo_transposed(const int32_t *shape, const int32_t *k, const int32_t *s, const int32_t *p, const int32_t *d,
+                         const int32_t *op, ConvGeo *g) {
+    g->K = 1;
+    int o[3];
+    for (int a = 0; a < 3; ++a) {
+        if (k[a] < 1 || s[a] < 1 || p[a] < 0 || d[a] < 1 || op[a] < 0 || shape[a] < 1) return false;
+        g->k[a] = k[a]; g->s[a] = s[a]; g->p[a] = p[a]; g->d[a] = d[a];
+        if ((long long)g->K * k[a] > 0x7fffffffll) return false;
+        g->K *= k[a];
+        const long long e = ((long long)shape[a] - 1) * s[a] - 2ll * p[a] + k[a] + op[a];
+        // (the upper bound of an input position, (in - 1) * stride - padding + (kernel - 1) * dilation, stays an int as well)
+        const long long hi = ((long long)shape[a] - 1) * s[a] + ((long long)k[a] - 1) * d[a];
+        if (e < 1 || e > 0x7fffffffll || hi > 0x7fffffffll) return false;
+        o[a] = (int)e;
+    }
+    g->out = GridDesc{o[0], o[1], o[2]};
+    return true;
+}
+
+// the two halves of a build over a ready geometry (TR: which enumeration), shared by the forward and the transposed entry points
+template <bool TR>
+int conv_assign(const int32_t *indices, int32_t m, int32_t batch, const ConvGeo &g, int32_t *out_shape_h, int32_t *count_out,
+                void *ws, size_t ws_bytes, doda_stream_t stream) {
+    if (g.K > 27 || (long long)m * g.K > 0x3fffffffll) return DODA_ERR_UNSUPPORTED;
+    out_shape_h[0] = g.out.X; out_shape_h[1] = g.out.Y; out_shape_h[2] = g.out.Z;
+    hipStream_t s = as_stream(stream);
+    if (m == 0) { hipMemsetAsync(count_out, 0, sizeof(int32_t), s); return DODA_OK; }
+    if (!indices || !ws) return DODA_ERR_INVALID;
+    HashFmt hf;   // values are touch keys j * K + rank
+    if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
+    const ConvWs w = carve_conv(ws, m, g.K);
+    if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
+    const int grid = div_up(m, 256);
+    hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
+    hipLaunchKernelGGL(conv_touch<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf);
+    hipLaunchKernelGGL(conv_first<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
+                       w.flag);
+    return exclusive_scan_i32(w.flag, w.rank, m * g.K, count_out, w.scan, s);
+}
+
+template <bool TR>
+int conv_fill(const int32_t *indices, int32_t m, int32_t batch, const ConvGeo &g, int32_t m_out, int32_t *out_indices,
+              int32_t *tbl, int32_t ld_out, int32_t *tbl_rev, int32_t ld_in, void *ws, size_t ws_bytes, doda_stream_t stream) {
+    if (g.K > 27 || (long long)m * g.K > 0x3fffffffll) return DODA_ERR_UNSUPPORTED;
+    if (!indices || !out_indices || !tbl || !tbl_rev || !ws) return DODA_ERR_INVALID;
+    HashFmt hf;   // the split the assign half used for this table
+    if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
+    const ConvWs w = carve_conv(ws, m, g.K);
+    if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
+    hipStream_t s = as_stream(stream);
+    const int grid = div_up(m, 256);
+    if (m_out > 0) hipMemsetAsync(tbl, 0xFF, (size_t)g.K * ld_out * 4, s);
+    hipLaunchKernelGGL(conv_number<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
+                       w.flag, w.rank, (int4 *)out_indices);
+    hipLaunchKernelGGL(conv_tables<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
+                       tbl, ld_out, tbl_rev, ld_in);
+    return doda_check_launch();
+}
 }  // namespace
 
 extern "C" size_t doda_rulebook_conv_workspace_bytes(int32_t m, int32_t K) {
@@ -655,21 +731,7 @@ extern "C" int doda_rulebook_conv_assign(const int32_t *indices, int32_t m, cons
         return DODA_ERR_INVALID;
     ConvGeo g;
     if (!make_geo(shape_h, ksize_h, stride_h, pad_h, dil_h, &g)) return DODA_ERR_INVALID;
-    if (g.K > 27 || (long long)m * g.K > 0x3fffffffll) return DODA_ERR_UNSUPPORTED;
-    out_shape_h[0] = g.out.X; out_shape_h[1] = g.out.Y; out_shape_h[2] = g.out.Z;
-    hipStream_t s = as_stream(stream);
-    if (m == 0) { hipMemsetAsync(count_out, 0, sizeof(int32_t), s); return DODA_OK; }
-    if (!indices || !ws) return DODA_ERR_INVALID;
-    HashFmt hf;   // values are touch keys j * K + rank
-    if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const ConvWs w = carve_conv(ws, m, g.K);
-    if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
-    const int grid = div_up(m, 256);
-    hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
-    hipLaunchKernelGGL(conv_touch, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf);
-    hipLaunchKernelGGL(conv_first, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
-                       w.flag);
-    return exclusive_scan_i32(w.flag, w.rank, m * g.K, count_out, w.scan, s);
+    return conv_assign<false>(indices, m, batch, g, out_shape_h, count_out, ws, ws_bytes, stream);
 }
 
 extern "C" int doda_rulebook_conv_tables(const int32_t *indices, int32_t m, const int32_t *shape_h,
@@ -683,20 +745,34 @@ extern "C" int doda_rulebook_conv_tables(const int32_t *indices, int32_t m, cons
     if (m == 0) return DODA_OK;
     ConvGeo g;
     if (!make_geo(shape_h, ksize_h, stride_h, pad_h, dil_h, &g)) return DODA_ERR_INVALID;
-    if (g.K > 27) return DODA_ERR_UNSUPPORTED;
-    if (!indices || !out_indices || !tbl || !tbl_rev || !ws) return DODA_ERR_INVALID;
-    HashFmt hf;   // the split doda_rulebook_conv_assign used for this table
-    if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const ConvWs w = carve_conv(ws, m, g.K);
-    if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
-    hipStream_t s = as_stream(stream);
-    const int grid = div_up(m, 256);
-    if (m_out > 0) hipMemsetAsync(tbl, 0xFF, (size_t)g.K * ld_out * 4, s);
-    hipLaunchKernelGGL(conv_number, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
-                       w.flag, w.rank, (int4 *)out_indices);
-    hipLaunchKernelGGL(conv_tables, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
-                       tbl, ld_out, tbl_rev, ld_in);
-    return doda_check_launch();
+    return conv_fill<false>(indices, m, batch, g, m_out, out_indices, tbl, ld_out, tbl_rev, ld_in, ws, ws_bytes, stream);
+}
+
+// ---- transposed convolution (include/doda_spconv.h): the same two halves over the transposed enumeration ------------------------
+extern "C" size_t doda_rulebook_deconv_workspace_bytes(int32_t m, int32_t K) { return doda_rulebook_conv_workspace_bytes(m, K); }
+
+extern "C" int doda_rulebook_deconv_assign(const int32_t *indices, int32_t m, const int32_t *shape_h, int32_t batch,
+                                           const int32_t *ksize_h, const int32_t *stride_h, const int32_t *pad_h,
+                                           const int32_t *dil_h, const int32_t *outpad_h, int32_t *out_shape_h, int32_t *count_out,
+                                           void *ws, size_t ws_bytes, doda_stream_t stream) {
+    if (m < 0 || !shape_h || !ksize_h || !stride_h || !pad_h || !dil_h || !outpad_h || !out_shape_h || !count_out)
+        return DODA_ERR_INVALID;
+    ConvGeo g;
+    if (!make_geo_transposed(shape_h, ksize_h, stride_h, pad_h, dil_h, outpad_h, &g)) return DODA_ERR_INVALID;
+    return conv_assign<true>(indices, m, batch, g, out_shape_h, count_out, ws, ws_bytes, stream);
+}
+
+extern "C" int doda_rulebook_deconv_tables(const int32_t *indices, int32_t m, const int32_t *shape_h, int32_t batch,
+                                           const int32_t *ksize_h, const int32_t *stride_h, const int32_t *pad_h,
+                                           const int32_t *dil_h, const int32_t *outpad_h, int32_t m_out, int32_t *out_indices,
+                                           int32_t *tbl, int32_t ld_out, int32_t *tbl_rev, int32_t ld_in, void *ws, size_t ws_bytes,
+                                           doda_stream_t stream) {
+    if (m < 0 || m_out < 0 || ld_out < m_out || ld_in < m || !shape_h || !ksize_h || !stride_h || !pad_h || !dil_h || !outpad_h)
+        return DODA_ERR_INVALID;
+    if (m == 0) return DODA_OK;
+    ConvGeo g;
+    if (!make_geo_transposed(shape_h, ksize_h, stride_h, pad_h, dil_h, outpad_h, &g)) return DODA_ERR_INVALID;
+    return conv_fill<true>(indices, m, batch, g, m_out, out_indices, tbl, ld_out, tbl_rev, ld_in, ws, ws_bytes, stream);
 }
 
 // SubM with per-axis odd kernel sizes (K <= 27); the cubic 1 / 3 cases keep doda_rulebook_subm

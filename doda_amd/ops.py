@@ -1598,3 +1598,123 @@ def po_furthestsampling(xyz, offset, new_offset, tmp, idx):
     _po_shape("po_furthestsampling", xyz.dim() == 2 and tmp.numel() >= xyz.shape[0] and offset.numel() == new_offset.numel())
     check(lib().doda_po_furthestsampling(_p(xyz), _p(offset), _p(new_offset), _p(tmp), _p(idx), xyz.shape[0], idx.numel(),
                                          offset.numel(), xyz.shape[1], _stream()), "doda_po_furthestsampling")
+
+
+# ------------------------------------------------------------------------------------------
+# the rest of the spconv surface (include/doda_spconv.h): transposed rulebook, max pooling by element size, dense volumes
+# ------------------------------------------------------------------------------------------
+def rulebook_deconv(indices, spatial_shape, batch_size, ksize, stride, padding, dilation, output_padding):
+    """Rulebook of a transposed sparse convolution (K <= 27).  Returns (out_indices int32 [M_out,4], tbl int32 [K,M_out],
+    tbl_rev int32 [K,M], out_shape list[3]) in the layout of rulebook_conv.  One D2H sync (M_out)."""
+    indices = _check_indices(indices)
+    m = indices.shape[0]
+    dev = indices.device
+    shape_c, _ = _shape3(spatial_shape)
+    k, s, p, d, op = _i3(ksize), _i3(stride), _i3(padding), _i3(dilation), _i3(output_padding)
+    K = k[0] * k[1] * k[2]
+    out_shape_c = (C.c_int32 * 3)()
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib().doda_rulebook_deconv_workspace_bytes(m, K)
+    if nbytes == 0:
+        raise DodaNativeError("doda_rulebook_deconv: kernel volume %d or size not supported" % K)
+    ws = _ws(nbytes, dev)
+    check(lib().doda_rulebook_deconv_assign(_p(indices), m, shape_c, int(batch_size), k, s, p, d, op, out_shape_c,
+                                            _p(count), _p(ws), ws.numel(), _stream()), "doda_rulebook_deconv_assign")
+    m_out = int(count.item())
+    out_idx = torch.empty((m_out, 4), dtype=torch.int32, device=dev)
+    tbl = torch.empty((K, m_out), dtype=torch.int32, device=dev)
+    tbl_rev = torch.empty((K, m), dtype=torch.int32, device=dev)
+    check(lib().doda_rulebook_deconv_tables(_p(indices), m, shape_c, int(batch_size), k, s, p, d, op, m_out,
+                                            _p(out_idx), _p(tbl), m_out, _p(tbl_rev), m, _p(ws), ws.numel(),
+                                            _stream()), "doda_rulebook_deconv_tables")
+    return out_idx, tbl, tbl_rev, [int(v) for v in out_shape_c]
+
+
+def _pool_tbl(tbl, rows, what):
+    _need_cuda(tbl)
+    if tbl.dtype != torch.int32 or tbl.dim() != 2 or not tbl.is_contiguous() or tbl.shape[1] < rows:
+        raise RuntimeError("%s: the table must be a contiguous int32 [K, >= %d] tensor" % (what, rows))
+
+
+def maxpool_fwd_rows(x, tbl, n_out):
+    """Indice max pooling of fp32 or bf16 rows over the outputs' table [K, n_out] (doda_maxpool_fwd): y [n_out, c] in x's dtype."""
+    _feat_ok(x, "x")
+    _pool_tbl(tbl, n_out, "maxpool_fwd_rows")
+    y = torch.empty((n_out, x.shape[1]), dtype=x.dtype, device=x.device)
+    check(lib().doda_maxpool_fwd(_p(x), x.shape[1], _esz(x), _p(tbl), tbl.shape[1], tbl.shape[0], x.shape[0], n_out, _p(y),
+                                 _stream()), "doda_maxpool_fwd")
+    return y
+
+
+def maxpool_bwd_rows(x, y, dy, tbl_rev, dx=None):
+    """Gradient of maxpool_fwd_rows over the inputs' table [K, n_in] (doda_maxpool_bwd): every row of dx is written once, so a dx
+    handed in needs no fill."""
+    for t, name in ((x, "x"), (y, "y"), (dy, "dy")):
+        _feat_ok(t, name)
+    _pool_tbl(tbl_rev, x.shape[0], "maxpool_bwd_rows")
+    if dx is None:
+        dx = torch.empty_like(x)
+    if not (y.dtype == dy.dtype == dx.dtype == x.dtype and y.shape == dy.shape and y.shape[1] == x.shape[1]
+            and dx.shape == x.shape and dx.is_contiguous() and dx.is_cuda):
+        raise RuntimeError("maxpool_bwd_rows: x / dx [n_in, c] and y / dy [n_out, c] of one dtype")
+    check(lib().doda_maxpool_bwd(_p(x), _p(y), _p(dy), x.shape[1], _esz(x), _p(tbl_rev), tbl_rev.shape[1], tbl_rev.shape[0],
+                                 x.shape[0], y.shape[0], _p(dx), _stream()), "doda_maxpool_bwd")
+    return dx
+
+
+def _dense_args(what, rows, indices, batch_size, spatial_shape):
+    _feat_ok(rows, what + ": rows")
+    indices = _check_indices(indices)
+    if indices.shape[0] != rows.shape[0]:
+        raise RuntimeError("%s: one index row per feature row" % what)
+    shape_c, s = _shape3(spatial_shape)
+    return indices, shape_c, s
+
+
+def dense_scatter(rows, indices, batch_size, spatial_shape, channels_first):
+    """The dense volume of unique rows (doda_dense_scatter): [B, C, X, Y, Z] or [B, X, Y, Z, C], zero where no row lies."""
+    indices, shape_c, s = _dense_args("dense_scatter", rows, indices, batch_size, spatial_shape)
+    c = rows.shape[1]
+    out = torch.empty([int(batch_size), c] + s if channels_first else [int(batch_size)] + s + [c], dtype=rows.dtype, device=rows.device)
+    check(lib().doda_dense_scatter(_p(rows), _p(indices), rows.shape[0], c, _esz(rows), int(batch_size), shape_c,
+                                   int(bool(channels_first)), _p(out), _stream()), "doda_dense_scatter")
+    return out
+
+
+def dense_gather(volume, indices, channels_first):
+    """Rows [M, C] of a contiguous dense volume at `indices` (doda_dense_gather)."""
+    _need_cuda(volume)
+    indices = _check_indices(indices)
+    if volume.dim() != 5 or not volume.is_contiguous():
+        raise RuntimeError("dense_gather: a contiguous 5-D volume")
+    b = volume.shape[0]
+    c, s = (volume.shape[1], list(volume.shape[2:])) if channels_first else (volume.shape[4], list(volume.shape[1:4]))
+    shape_c, _ = _shape3(s)
+    rows = torch.empty((indices.shape[0], c), dtype=volume.dtype, device=volume.device)
+    check(lib().doda_dense_gather(_p(volume), _p(indices), indices.shape[0], c, _esz(volume), b, shape_c,
+                                  int(bool(channels_first)), _p(rows), _stream()), "doda_dense_gather")
+    return rows
+
+
+def from_dense(volume):
+    """(indices int32 [M, 4], rows [M, C]) of the active cells of a contiguous channels-last volume [B, X, Y, Z, C], in row-major
+    cell order (doda_from_dense_count / _emit).  One D2H sync (M)."""
+    _need_cuda(volume)
+    if volume.dim() != 5 or not volume.is_contiguous():
+        raise RuntimeError("from_dense: a contiguous [B, X, Y, Z, C] volume")
+    b, c = volume.shape[0], volume.shape[4]
+    shape_c, s = _shape3(list(volume.shape[1:4]))
+    dev = volume.device
+    nbytes = lib().doda_from_dense_workspace_bytes(b * s[0] * s[1] * s[2])
+    if nbytes == 0:
+        raise DodaNativeError("doda_from_dense: a volume of %d cells is not supported" % (b * s[0] * s[1] * s[2]))
+    ws = _ws(nbytes, dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().doda_from_dense_count(_p(volume), c, _esz(volume), b, shape_c, _p(count), _p(ws), ws.numel(), _stream()),
+          "doda_from_dense_count")
+    m = int(count.item())
+    indices = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((m, c), dtype=volume.dtype, device=dev)
+    check(lib().doda_from_dense_emit(_p(volume), c, _esz(volume), b, shape_c, m, _p(indices), _p(rows), _p(ws), ws.numel(),
+                                     _stream()), "doda_from_dense_emit")
+    return indices, rows

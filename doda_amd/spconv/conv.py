@@ -318,6 +318,9 @@ class SparseConvolution(SparseModule):
 
         data = input.find_indice_pair(self.indice_key)
         if self.inverse:
+            if data is not None and data.kind == "transpose":
+                raise NotImplementedError("SparseInverseConv3d over the indice_key %r of a SparseConvTranspose3d is not supported: "
+                                          "invert a strided SparseConv3d, or down-sample with SparseConv3d over the output" % (self.indice_key,))
             if data is None or data.kind != "down2":
                 raise RuntimeError("SparseInverseConv3d: no strided rulebook under indice_key %r"
                                    % (self.indice_key,))
@@ -327,6 +330,9 @@ class SparseConvolution(SparseModule):
             if data is None:
                 if self.subm:
                     data = ops.build_subm(indices, batch_size, spatial_shape, self.kernel_size)
+                elif self.transposed:
+                    data = ops.build_transpose(indices, batch_size, spatial_shape, self.kernel_size, self.stride,
+                                               self.padding, self.dilation, self.output_padding)
                 else:
                     data = ops.build_down2(indices, batch_size, spatial_shape, self.kernel_size,
                                            self.stride, self.padding, self.dilation)
@@ -369,6 +375,17 @@ class SparseConv3d(SparseConvolution):
                  groups=1, bias=True, indice_key=None, use_hash=False):
         super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation,
                          groups, bias, indice_key=indice_key, use_hash=use_hash)
+
+
+class SparseConvTranspose3d(SparseConvolution):
+    """Transposed sparse convolution: input p reaches q = p * stride - padding + k * dilation for every kernel offset k, and only
+    reached cells exist.  The rulebook is a pair of tables in the generic strided layout, so forward, data
+    gradient and weight gradient are SparseConv3d's own calls over them."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                 groups=1, bias=True, indice_key=None):
+        super().__init__(3, in_channels, out_channels, kernel_size, stride, padding, dilation,
+                         groups, bias, transposed=True, indice_key=indice_key)
 
 
 class SparseInverseConv3d(SparseConvolution):

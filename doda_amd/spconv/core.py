@@ -18,6 +18,8 @@ class IndiceData:
 
     kind 'subm' : tbl = nbr int32 [27, M]
     kind 'down2': tbl = child int32 [8, M_out]; tbl_rev = par_off int32 [8, M_in]
+                  (generic strided geometry: tbl int32 [K, M_out], tbl_rev int32 [K, M_in])
+    kind 'transpose': the generic pair of a SparseConvTranspose3d, tbl int32 [K, M_out], tbl_rev int32 [K, M_in]
     """
 
     def __init__(self, kind, outids, indices, spatial_shape, out_spatial_shape, tbl, tbl_rev=None):
@@ -95,6 +97,48 @@ class IndiceDict(dict):
         self.pack_gen = None
 
 
+def dense_torch(features, indices, batch_size, spatial_shape, channels_first=True):
+    """dense() as a torch expression: zeros, an indexed put in channels-last order, then the permutation."""
+    idx = indices.long()
+    shape = [batch_size] + list(spatial_shape) + [features.shape[1]]
+    out = torch.zeros(shape, dtype=features.dtype, device=features.device)
+    out[idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]] = features
+    if not channels_first:
+        return out
+    ndim = len(spatial_shape)
+    return out.permute(0, ndim + 1, *range(1, ndim + 1)).contiguous()
+
+
+class _Dense(torch.autograd.Function):
+    """rows -> volume by doda_dense_scatter; the gradient gathers the rows back (doda_dense_gather)."""
+
+    @staticmethod
+    def forward(ctx, features, indices, batch_size, spatial_shape, channels_first):
+        ctx.args = (indices, channels_first)
+        return _ops.dense_scatter(features.contiguous(), indices, batch_size, spatial_shape, channels_first)
+
+    @staticmethod
+    def backward(ctx, grad):
+        indices, channels_first = ctx.args
+        return _ops.dense_gather(grad.contiguous(), indices, channels_first), None, None, None, None
+
+
+class _FromDense(torch.autograd.Function):
+    """volume -> (rows, indices) by doda_from_dense_count / _emit; the gradient scatters the rows' gradient into a zero volume."""
+
+    @staticmethod
+    def forward(ctx, x):
+        indices, rows = _ops.from_dense(x.contiguous())
+        ctx.args = (indices, x.shape[0], tuple(x.shape[1:4]))
+        ctx.mark_non_differentiable(indices)
+        return rows, indices
+
+    @staticmethod
+    def backward(ctx, grad_rows, _grad_indices):
+        indices, batch, shape = ctx.args
+        return _ops.dense_scatter(grad_rows.contiguous(), indices, batch, shape, False)
+
+
 class SparseConvTensor:
     """features [M,C] + indices int32 [M,4] (batch,x,y,z) + spatial_shape + batch_size.
 
@@ -149,14 +193,32 @@ class SparseConvTensor:
         return self.indice_dict.get(key)
 
     def dense(self, channels_first=True):
-        idx = self.indices.long()
-        shape = [self.batch_size] + list(self.spatial_shape) + [self.features.shape[1]]
-        out = torch.zeros(shape, dtype=self.features.dtype, device=self.features.device)
-        out[idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]] = self.features
-        if not channels_first:
-            return out
-        ndim = len(self.spatial_shape)
-        return out.permute(0, ndim + 1, *range(1, ndim + 1)).contiguous()
+        """The dense volume [B, C, X, Y, Z] (channels_first) or [B, X, Y, Z, C]; the indices must be unique.  fp32 / bf16 device
+        features with int32 indices: one native scatter straight into the requested layout (doda_dense_scatter), differentiable
+        through the features; anything else: the torch expression, with the same bits."""
+        feats = self.features
+        if (feats.is_cuda and feats.dtype in (torch.float32, torch.bfloat16) and feats.dim() == 2 and feats.shape[1] > 0
+                and self.indices.is_cuda and self.indices.dtype == torch.int32 and len(self.spatial_shape) == 3
+                and self.batch_size > 0):
+            return _Dense.apply(feats, self.indices, self.batch_size, tuple(self.spatial_shape), bool(channels_first))
+        return dense_torch(feats, self.indices, self.batch_size, self.spatial_shape, channels_first)
+
+    @classmethod
+    def from_dense(cls, x):
+        """The sparse tensor of a channels-last dense volume x [B, X, Y, Z, C]: a cell is active iff any channel is non-zero; rows
+        in row-major (b, x, y, z) order (the coalesced order of x.to_sparse(4)), indices int32.  Device fp32 / bf16 volumes: flag,
+        stable compaction and row copy on the device with one size read-back.  Not differentiable through the indices;
+        differentiable through the features (a gather, whose gradient is the scatter)."""
+        if x.dim() != 5:
+            raise ValueError("from_dense expects [B, X, Y, Z, C], got %r" % (tuple(x.shape),))
+        shape, batch = [int(v) for v in x.shape[1:4]], int(x.shape[0])
+        if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0:
+            feats, indices = _FromDense.apply(x)
+        else:
+            mask = (x != 0).any(-1)
+            indices = mask.nonzero().int()
+            feats = x[mask]
+        return cls(feats, indices, shape, batch)
 
     @property
     def sparity(self):

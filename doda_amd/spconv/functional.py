@@ -232,5 +232,25 @@ class _IndiceMaxPool(Function):
         return _ops.maxpool_bwd(features.contiguous(), out, grad_output.contiguous(), tbl, n_out), None, None
 
 
+class _IndiceMaxPoolRows(Function):
+    """bf16 rows (doda_maxpool_fwd / _bwd, include/doda_spconv.h): the backward is input-stationary over the reverse table — fp32
+    sums in ascending offset, one rounding, every dx row written once, no atomic."""
+
+    @staticmethod
+    def forward(ctx, features, tbl, tbl_rev, n_out):
+        features = features.contiguous()
+        out = _ops.maxpool_fwd_rows(features, tbl, n_out)
+        ctx.save_for_backward(features, out)
+        ctx.tbl_rev = tbl_rev
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        features, out = ctx.saved_tensors
+        return _ops.maxpool_bwd_rows(features, out, grad_output.contiguous(), ctx.tbl_rev), None, None, None
+
+
 def indice_maxpool(features, data):
+    if features.dtype == torch.bfloat16:
+        return _IndiceMaxPoolRows.apply(features, data.tbl, data.tbl_rev, data.outids.shape[0])
     return _IndiceMaxPool.apply(features, data.tbl, data.outids.shape[0])

@@ -3,6 +3,7 @@ reference imports at model/unet_block.py:3-4, uses at model/unet.py:35,42 and
 model/unet_block.py:10,41,62-85)."""
 from collections import OrderedDict
 
+import torch
 from torch import nn
 from torch.nn.modules import module as _mod
 
@@ -119,3 +120,52 @@ class SparseSequential(SparseModule):
         if residual is not None:
             input.features = input.features + residual
         return input
+
+
+# ---- the plain modules of spconv v1.2 (spconv.modules / spconv.tables / spconv.identity): Python only, CPU tensors included ------
+class ToDense(SparseModule):
+    """SparseConvTensor -> dense [B, C, X, Y, Z] tensor (the usual end of a network with a dense head)."""
+
+    def forward(self, x):
+        return x.dense()
+
+
+class RemoveGrid(SparseModule):
+    """Drops the tensor's grid buffer."""
+
+    def forward(self, x):
+        x.grid = None
+        return x
+
+
+class Identity(SparseModule):
+    def forward(self, input):
+        return input
+
+
+class ConcatTable(SparseModule):
+    """Applies every child to the same input; returns the list of their outputs."""
+
+    def forward(self, input):
+        return [module(input) for module in self._modules.values()]
+
+    def add(self, module):
+        self._modules[str(len(self._modules))] = module
+        return self
+
+
+class AddTable(SparseModule):
+    """Sums the features of a list of tensors over the same voxels into a header of the first."""
+
+    def forward(self, input):
+        features = input[0].features
+        for t in input[1:]:
+            features = features + t.features
+        return input[0].header(features)
+
+
+class JoinTable(SparseModule):
+    """Concatenates the features of a list of tensors over the same voxels along the channel dimension."""
+
+    def forward(self, input):
+        return input[0].header(torch.cat([t.features for t in input], 1))

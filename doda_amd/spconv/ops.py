@@ -2,7 +2,8 @@
 get_indice_pairs).  The geometries DODA instantiates — SubM with a cubic kernel of 1 or 3 and the
 kernel-2 / stride-2 / padding-0 convolution (model/unet.py:36, model/unet_block.py:18-29,48,70,78) —
 have dedicated native builders; any other kernel_size / stride / padding / dilation with a kernel
-volume of at most 27 goes through the generic one (doda_rulebook_conv_*, doda_rulebook_subm_generic)."""
+volume of at most 27 goes through the generic one (doda_rulebook_conv_*, doda_rulebook_subm_generic), and the transposed
+convolution through the same builder's second enumeration (doda_rulebook_deconv_*, include/doda_spconv.h)."""
 import os
 
 import numpy as np
@@ -56,13 +57,35 @@ def build_down2(indices, batch_size, spatial_shape, ksize, stride, padding, dila
     return IndiceData("down2", outids, indices, list(spatial_shape), out_shape, child, par_off)
 
 
+def get_deconv_output_size(input_size, kernel_size, stride, padding, dilation, output_padding):
+    """Output shape of a transposed convolution: (in - 1) * stride - 2 * padding + kernel_size + output_padding per axis.
+    [MEM] upstream's spconv.ops.get_deconv_output_size, written from memory as in SURVEY §0 (spconv v1.2 is not vendored).  The
+    formula ignores dilation: positions a dilated kernel would reach beyond it are dropped by the rulebook builder."""
+    out = []
+    for i in range(len(input_size)):
+        if kernel_size[i] < 1:
+            raise ValueError("a transposed convolution needs kernel_size >= 1, got %r" % (kernel_size,))
+        out.append((input_size[i] - 1) * stride[i] - 2 * padding[i] + kernel_size[i] + output_padding[i])
+    return out
+
+
+def build_transpose(indices, batch_size, spatial_shape, ksize, stride, padding, dilation, output_padding):
+    """Rulebook of SparseConvTranspose3d (doda_rulebook_deconv_*): kind 'transpose', tables in the generic strided layout —
+    tbl [K, M_out] (the input row feeding output t through offset o), tbl_rev [K, M_in]."""
+    k, s, p, d, op = _triple(ksize), _triple(stride), _triple(padding), _triple(dilation), _triple(output_padding)
+    if k[0] * k[1] * k[2] > 27:
+        raise NotImplementedError("doda_amd SparseConvTranspose3d supports kernel volumes <= 27, got k=%r" % (k,))
+    outids, tbl, tbl_rev, out_shape = _ops.rulebook_deconv(indices, spatial_shape, batch_size, k, s, p, d, op)
+    return IndiceData("transpose", outids, indices, list(spatial_shape), out_shape, tbl, tbl_rev)
+
+
 def get_indice_pairs(indices, batch_size, spatial_shape, ksize=3, stride=1, padding=0, dilation=1,
                      out_padding=0, subm=False, transpose=False, grid=None, use_hash=False):
     """Upstream-shaped entry: returns (outids, indice_pairs [2,K,N], indice_pair_num [K])."""
-    if transpose:
-        raise NotImplementedError("transposed sparse convolution is not part of DODA's path")
     if subm:
         data = build_subm(indices, batch_size, spatial_shape, ksize)
+    elif transpose:
+        data = build_transpose(indices, batch_size, spatial_shape, ksize, stride, padding, dilation, out_padding)
     else:
         data = build_down2(indices, batch_size, spatial_shape, ksize, stride, padding, dilation)
     return data.outids, data.indice_pairs, data.indice_pair_num

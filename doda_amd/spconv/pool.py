@@ -1,6 +1,8 @@
 """SparseMaxPool3d (spconv v1.2 `spconv.pool`): indice-pair max pooling.  Not used by DODA's
 network (it down-samples with strided convolutions, model/unet_block.py:70); provided because
-north_star names indice-pair pooling.  Geometry: kernel 2, stride 2, padding 0."""
+north_star names indice-pair pooling.  Geometry: any kernel_size / stride / padding / dilation with a kernel volume of at most 27
+(ops.build_down2: kernel 2, stride 2, padding 0 has its dedicated builder, everything else the generic one).  fp32 features run
+doda_maxpool_*_f32; bf16 features run doda_maxpool_fwd / _bwd (include/doda_spconv.h), whose backward uses no atomic."""
 from . import functional as Fsp
 from . import ops
 from .core import SparseConvTensor

@@ -31,7 +31,7 @@ def _named(*names):
 
 
 # ---- include/doda_hip.h: the core ABI ----------------------------------------------------------------------------------------
-ABI_VERSION = 12
+ABI_VERSION = 13
 OPT_TILE_KERNEL, OPT_WLDS_KERNEL, OPT_WDMA_KERNEL, OPT_TILE_PIPELINE, OPT_TILE_DUAL, OPT_CONV_UP = 1, 2, 3, 4, 5, 6   # doda_set_option / doda_get_option
 OPT_PRE_FWD_ROWS, OPT_PRE_BWD_ROWS = 7, 8   # (row thresholds of doda_layers_run's BatchNorm folding)
 STATS_SLOTS = 8
@@ -89,6 +89,7 @@ ABIS.append(Abi("doda_hip.h", "doda_abi_version", ABI_VERSION, "ABI", {
     "doda_point_recover_fp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "doda_point_recover_bp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "doda_rulebook_workspace_bytes": (c_sz, [c_i32]),
+    "doda_rulebook_workspace_bytes_grid": (c_sz, [c_i32, c_i32, c_vp]),   # ABI 13
     "doda_rulebook_subm": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_sz, c_vp]),
     "doda_rulebook_down2_assign": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_sz, c_vp]),

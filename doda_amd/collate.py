@@ -178,5 +178,5 @@ def choose_voxel_order(batch, device=None):
     idx = vl.to(dev).int().contiguous()
     shape = [int(v) for v in batch["spatial_shape"]]
     nb = int(batch["offsets"].numel() - 1)
-    _, nt, _, over = sops._ext.build_pyramid_probe(idx, shape, nb, 1, -1, sops.TILE_MIN_ROWS, 1)
+    _, nt, _, over = sops._ext.build_pyramid_probe(idx, shape, nb, sops.level_policy(1, False, 1, True))
     return "morton" if (nt > 0 and over > TILE_OVERFLOW_SWITCH * nt) else "first"

@@ -33,19 +33,54 @@ __device__ __forceinline__ bool in_grid(const int4 c, int batch, const GridDesc 
     return (unsigned)c.x < (unsigned)batch && (unsigned)c.y < (unsigned)g.X && (unsigned)c.z < (unsigned)g.Y && (unsigned)c.w < (unsigned)g.Z;
 }
 
+// ---- the cell map ---------------------------------------------------------------------------
+// cell -> row (or touch key), in one of two forms with the same two operations: claim(cell, v) keeps the LOWEST v claimed for
+// a cell (first touch wins), find(cell) returns it or -1.  Every builder kernel below is written once over either form.
+// HashCells: the open-addressing table of 64-bit words (common.hpp), pre-filled with 0xFF bytes.
+struct HashCells {
+    unsigned long long *tab;
+    uint32_t mask;
+    HashFmt hf;
+    __device__ __forceinline__ void claim(cellkey_t cell, uint32_t v) const { hash_insert_min(tab, mask, hf, cell, v); }
+    __device__ __forceinline__ int find(cellkey_t cell) const { return hash_find(tab, mask, hf, cell); }
+    // replace the value of a PRESENT key (the generic builder turns touch keys into output ids)
+    __device__ __forceinline__ void replace(cellkey_t cell, uint32_t v) const {
+        uint32_t slot = hash_key(cell) & mask;
+        while ((tab[slot] >> hf.vbits) != cell) slot = (slot + 1) & mask;
+        tab[slot] = (cell << hf.vbits) | v;
+    }
+};
+
+// GridCells: the direct-address grid (round 4), grid[cell] = row or -1, pre-filled with 0xFF bytes.  For grids of up to
+// 2^DODA_RULEBOOK_GRID_MAX_LOG2 cells (a batch of 2 cm ScanNet scenes: 16.5 M cells = 66 MB of int32) a probe is ONE 4-byte
+// read instead of 1.3 eight-byte hash reads, and the three z-neighbours of a (dx, dy) pair are adjacent words: the 13 probes
+// of a voxel touch ~5 64-byte sectors instead of ~17 — the hash probe ran at the fabric's random-sector rate.
+// The caller opts in by handing over a workspace with room for the grid behind the hash workspace
+// (doda_rulebook_workspace_bytes_grid); larger grids (1 cm scenes: 2^34 cells) keep the hash.
+// (round 5: 2^28 cells = 1 GiB of grid — a batch of four 1 cm scenes has 8.5e7 cells; its level-1 probe took 1.1 ms on the
+// hash and the memset of the grid costs 45 us.)
+struct GridCells {
+    int32_t *grid;
+    __device__ __forceinline__ void claim(cellkey_t cell, uint32_t v) const { atomicMin((unsigned *)grid + (long long)cell, (unsigned)v); }
+    __device__ __forceinline__ int find(cellkey_t cell) const { return grid[(long long)cell]; }
+};
+
 // ---- SubM ---------------------------------------------------------------------------------
 // Also pre-fills column t of the table's mirrored half (offsets first_fill .. K3-1) with -1: the
 // probe kernel only writes hits there (saves a memset launch per rulebook).
-__global__ __launch_bounds__(256) void subm_insert(const int4 *__restrict__ indices, int m, int batch,
-                                                   GridDesc g, unsigned long long *tab,
-                                                   uint32_t mask, HashFmt hf, int32_t *__restrict__ nbr, int ld,
-                                                   int first_fill, int k3) {
+template <class Cells>
+__global__ __launch_bounds__(256) void subm_insert(const int4 *__restrict__ indices, int m, int batch, GridDesc g, Cells cells,
+                                                   int32_t *__restrict__ nbr, int ld, int first_fill, int k3) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= m) return;
     const int4 c = indices[t];
-    if (in_grid(c, batch, g)) hash_insert_min(tab, mask, hf, cell_id(c.x, c.y, c.z, c.w, g), (uint32_t)t);
+    if (in_grid(c, batch, g)) cells.claim(cell_id(c.x, c.y, c.z, c.w, g), (uint32_t)t);
     for (int o = first_fill; o < k3; ++o) nbr[(long long)o * ld + t] = -1;
 }
+
+// The probe stays two kernels, subm_probe over the hash words and subm_grid_probe over the grid: the first issues all
+// first-slot reads before it inspects any and walks a chain only on a collision, the second relies on the three z-neighbours
+// being adjacent words and needs no key — one body would have to branch on which map it serves.
 
 // One thread per voxel.  A SubM table is its own transpose under offset mirroring (nbr[o][t] = j  <=>
 // nbr[K3-1-o][j] = t), so only the first half of the offsets is probed: a hit writes both entries
@@ -101,31 +136,6 @@ __global__ __launch_bounds__(256) void subm_probe(const int4 *__restrict__ indic
     }
 }
 
-// ---- direct-address grid (round 4) ---------------------------------------------------------------
-// For grids of up to DODA_RULEBOOK_GRID_MAX_CELLS cells (a batch of 2 cm ScanNet scenes: 16.5 M cells = 66 MB of int32)
-// the cell -> row map is a plain array: grid[cell] = row or -1.  A probe is ONE 4-byte read instead of 1.3 eight-byte
-// hash reads, and the three z-neighbours of a (dx, dy) pair are adjacent words: the 13 probes of a voxel touch ~5
-// 64-byte sectors instead of ~17 — the hash probe ran at the fabric's random-sector rate.  The caller
-// opts in by handing over a workspace with room for the grid behind the hash workspace (doda_hip.h); larger grids
-// (1 cm scenes: 2^34 cells) keep the hash.  Same results: first-touch (lowest row) wins a cell, as hash_insert_min.
-// (round 5: 2^28 cells = 1 GiB of grid — a batch of four 1 cm scenes has 8.5e7 cells; its level-1 probe took 1.1 ms on the
-// hash and the memset of the grid costs 45 us.  DODA_RULEBOOK_GRID_MAX_LOG2 moves the limit; callers size the workspace.)
-static const long long GRID_MAX_CELLS = [] {
-    const char *e = getenv("DODA_RULEBOOK_GRID_MAX_LOG2");
-    const int b = e ? atoi(e) : 28;
-    return 1ll << (b < 0 ? 0 : b > 30 ? 30 : b);
-}();
-
-__global__ __launch_bounds__(256) void subm_grid_insert(const int4 *__restrict__ indices, int m, int batch, GridDesc g,
-                                                        int32_t *__restrict__ grid, int32_t *__restrict__ nbr, int ld,
-                                                        int first_fill, int k3) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= m) return;
-    const int4 c = indices[t];
-    if (in_grid(c, batch, g)) atomicMin((unsigned *)grid + (long long)cell_id(c.x, c.y, c.z, c.w, g), (unsigned)t);
-    for (int o = first_fill; o < k3; ++o) nbr[(long long)o * ld + t] = -1;
-}
-
 template <int KS>
 __global__ __launch_bounds__(256) void subm_grid_probe(const int4 *__restrict__ indices, int m, int batch, GridDesc g,
                                                        const int32_t *__restrict__ grid, int32_t *__restrict__ nbr, int ld) {
@@ -150,55 +160,35 @@ __global__ __launch_bounds__(256) void subm_grid_probe(const int4 *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void down2_grid_insert(const int4 *__restrict__ indices, int m, int batch, GridDesc go,
-                                                         int32_t *__restrict__ grid, int32_t *__restrict__ off) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= m) return;
-    const int4 c = indices[j];
-    off[j] = ((c.y & 1) * 2 + (c.z & 1)) * 2 + (c.w & 1);
-    const int4 q = make_int4(c.x, c.y >> 1, c.z >> 1, c.w >> 1);
-    if (c.y < 0 || c.z < 0 || c.w < 0 || !in_grid(q, batch, go)) return;
-    atomicMin((unsigned *)grid + (long long)cell_id(q.x, q.y, q.z, q.w, go), (unsigned)j);
-}
-
-__global__ __launch_bounds__(256) void down2_grid_first(const int4 *__restrict__ indices, int m, int batch, GridDesc go,
-                                                        const int32_t *__restrict__ grid, int32_t *__restrict__ firstj,
-                                                        int32_t *__restrict__ flag) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= m) return;
-    const int4 c = indices[j];
-    const int4 q = make_int4(c.x, c.y >> 1, c.z >> 1, c.w >> 1);
-    int f = -1;
-    if (!(c.y < 0 || c.z < 0 || c.w < 0) && in_grid(q, batch, go)) f = grid[(long long)cell_id(q.x, q.y, q.z, q.w, go)];
-    firstj[j] = f;
-    flag[j] = (f == j) ? 1 : 0;
-}
-
 // ---- Down2 (kernel 2, stride 2, pad 0) ------------------------------------------------------
-__global__ __launch_bounds__(256) void down2_insert(const int4 *__restrict__ indices, int m, int batch,
-                                                    GridDesc go, unsigned long long *tab,
-                                                    uint32_t mask, HashFmt hf, int32_t *__restrict__ off) {
+// the output cell of input row c, and whether it has one (a negative coordinate would shift into a valid one)
+__device__ __forceinline__ bool down2_cell(const int4 c, int batch, const GridDesc go, cellkey_t *cell) {
+    const int4 q = make_int4(c.x, c.y >> 1, c.z >> 1, c.w >> 1);
+    if (c.y < 0 || c.z < 0 || c.w < 0 || !in_grid(q, batch, go)) return false;
+    *cell = cell_id(q.x, q.y, q.z, q.w, go);
+    return true;
+}
+
+template <class Cells>
+__global__ __launch_bounds__(256) void down2_insert(const int4 *__restrict__ indices, int m, int batch, GridDesc go, Cells cells,
+                                                    int32_t *__restrict__ off) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
     off[j] = ((c.y & 1) * 2 + (c.z & 1)) * 2 + (c.w & 1);
-    const int qx = c.y >> 1, qy = c.z >> 1, qz = c.w >> 1;
-    if ((unsigned)c.x >= (unsigned)batch || c.y < 0 || c.z < 0 || c.w < 0 || qx >= go.X || qy >= go.Y || qz >= go.Z) return;
-    hash_insert_min(tab, mask, hf, cell_id(c.x, qx, qy, qz, go), (uint32_t)j);
+    cellkey_t cell;
+    if (down2_cell(c, batch, go, &cell)) cells.claim(cell, (uint32_t)j);
 }
 
-__global__ __launch_bounds__(256) void down2_first(const int4 *__restrict__ indices, int m, int batch,
-                                                   GridDesc go,
-                                                   const unsigned long long *__restrict__ tab,
-                                                   uint32_t mask, HashFmt hf, int32_t *__restrict__ firstj,
-                                                   int32_t *__restrict__ flag) {
+template <class Cells>
+__global__ __launch_bounds__(256) void down2_first(const int4 *__restrict__ indices, int m, int batch, GridDesc go, Cells cells,
+                                                   int32_t *__restrict__ firstj, int32_t *__restrict__ flag) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
-    const int qx = c.y >> 1, qy = c.z >> 1, qz = c.w >> 1;
+    cellkey_t cell;
     int f = -1;
-    if (!((unsigned)c.x >= (unsigned)batch || c.y < 0 || c.z < 0 || c.w < 0 || qx >= go.X || qy >= go.Y || qz >= go.Z))
-        f = hash_find(tab, mask, hf, cell_id(c.x, qx, qy, qz, go));
+    if (down2_cell(c, batch, go, &cell)) f = cells.find(cell);
     firstj[j] = f;
     flag[j] = (f == j) ? 1 : 0;
 }
@@ -358,36 +348,33 @@ __device__ __forceinline__ void for_valid_out(const int4 c, const ConvGeo &g, F 
 }
 
 template <bool TR>
-__global__ __launch_bounds__(256) void conv_touch(const int4 *__restrict__ indices, int m, ConvGeo g,
-                                                  unsigned long long *tab, uint32_t mask, HashFmt hf) {
+__global__ __launch_bounds__(256) void conv_touch(const int4 *__restrict__ indices, int m, ConvGeo g, HashCells cells) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
     for_valid_out<TR>(c, g, [&](int rank, int ox, int oy, int oz, int) {
-        hash_insert_min(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out), (uint32_t)j * (uint32_t)g.K + (uint32_t)rank);
+        cells.claim(cell_id(c.x, ox, oy, oz, g.out), (uint32_t)j * (uint32_t)g.K + (uint32_t)rank);
     });
 }
 
 // flag[j*K + rank] = 1 where that candidate is the first touch of its output cell
 template <bool TR>
-__global__ __launch_bounds__(256) void conv_first(const int4 *__restrict__ indices, int m, ConvGeo g,
-                                                  const unsigned long long *__restrict__ tab,
-                                                  uint32_t mask, HashFmt hf, int32_t *__restrict__ flag) {
+__global__ __launch_bounds__(256) void conv_first(const int4 *__restrict__ indices, int m, ConvGeo g, HashCells cells,
+                                                  int32_t *__restrict__ flag) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
     for (int r = 0; r < g.K; ++r) flag[(long long)j * g.K + r] = 0;
     for_valid_out<TR>(c, g, [&](int rank, int ox, int oy, int oz, int) {
         const uint32_t mine = (uint32_t)j * (uint32_t)g.K + (uint32_t)rank;
-        if ((uint32_t)hash_find(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out)) == mine) flag[mine] = 1;
+        if ((uint32_t)cells.find(cell_id(c.x, ox, oy, oz, g.out)) == mine) flag[mine] = 1;
     });
 }
 
 // the first-touch candidates write their output's coordinates and replace the table value (touch
 // key) of their cell by the output id
 template <bool TR>
-__global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indices, int m, ConvGeo g,
-                                                   unsigned long long *tab, uint32_t mask, HashFmt hf,
+__global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indices, int m, ConvGeo g, HashCells cells,
                                                    const int32_t *__restrict__ flag,
                                                    const int32_t *__restrict__ rank_of,
                                                    int4 *__restrict__ out_indices) {
@@ -399,25 +386,21 @@ __global__ __launch_bounds__(256) void conv_number(const int4 *__restrict__ indi
         if (!flag[e]) return;
         const int id = rank_of[e];
         out_indices[id] = make_int4(c.x, ox, oy, oz);
-        const cellkey_t key = cell_id(c.x, ox, oy, oz, g.out);
-        uint32_t slot = hash_key(key) & mask;
-        while ((tab[slot] >> hf.vbits) != key) slot = (slot + 1) & mask;   // present by construction
-        tab[slot] = (key << hf.vbits) | (uint32_t)id;
+        cells.replace(cell_id(c.x, ox, oy, oz, g.out), (uint32_t)id);   // present by construction
     });
 }
 
 // tbl[off][out] = j and tbl_rev[off][j] = out for every (input, output, offset) triple
 template <bool TR>
-__global__ __launch_bounds__(256) void conv_tables(const int4 *__restrict__ indices, int m, ConvGeo g,
-                                                   const unsigned long long *__restrict__ tab,
-                                                   uint32_t mask, HashFmt hf, int32_t *__restrict__ tbl, int ld_out,
+__global__ __launch_bounds__(256) void conv_tables(const int4 *__restrict__ indices, int m, ConvGeo g, HashCells cells,
+                                                   int32_t *__restrict__ tbl, int ld_out,
                                                    int32_t *__restrict__ tbl_rev, int ld_in) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     const int4 c = indices[j];
     for (int o = 0; o < g.K; ++o) tbl_rev[(long long)o * ld_in + j] = -1;
     for_valid_out<TR>(c, g, [&](int, int ox, int oy, int oz, int off) {
-        const int out = hash_find(tab, mask, hf, cell_id(c.x, ox, oy, oz, g.out));
+        const int out = cells.find(cell_id(c.x, ox, oy, oz, g.out));
         tbl_rev[(long long)off * ld_in + j] = out;
         tbl[(long long)off * ld_out + out] = j;
     });
@@ -425,9 +408,8 @@ __global__ __launch_bounds__(256) void conv_tables(const int4 *__restrict__ indi
 
 // SubM with a non-cubic odd kernel: plain per-offset lookups (offset = row-major kernel index)
 __global__ __launch_bounds__(256) void subm_probe_generic(const int4 *__restrict__ indices, int m, int batch,
-                                                          GridDesc g, int k0, int k1, int k2,
-                                                          const unsigned long long *__restrict__ tab,
-                                                          uint32_t mask, HashFmt hf, int32_t *__restrict__ nbr, int ld) {
+                                                          GridDesc g, int k0, int k1, int k2, HashCells cells,
+                                                          int32_t *__restrict__ nbr, int ld) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= m) return;
     const int4 c = indices[t];
@@ -439,36 +421,38 @@ __global__ __launch_bounds__(256) void subm_probe_generic(const int4 *__restrict
                 const int x = c.y + a - k0 / 2, y = c.z + b - k1 / 2, z = c.w + d - k2 / 2;
                 int v = -1;
                 if (own_ok && x >= 0 && x < g.X && y >= 0 && y < g.Y && z >= 0 && z < g.Z)
-                    v = hash_find(tab, mask, hf, cell_id(c.x, x, y, z, g));
+                    v = cells.find(cell_id(c.x, x, y, z, g));
                 if (!own_ok && a == k0 / 2 && b == k1 / 2 && d == k2 / 2) v = t;   // centre only
                 nbr[(long long)o * ld + t] = v;
             }
 }
 
+// The workspace of a build: a hash table of at least two slots per candidate, `n_arrays` (<= 3) int arrays of one entry per
+// candidate and the scratch of a prefix sum over the candidates.  A row has `per_row` candidates: itself (SubM, Down2: three
+// arrays — firstj, flag, rank) or its K touch keys (the generic builder: two arrays — flag, rank); an empty build is laid
+// out as one row.
 struct RbWs {
     unsigned long long *tab;
     uint32_t cap;
-    int32_t *a, *b, *c, *scan;
+    int32_t *arr[3], *scan;
     size_t total;
+    HashCells cells(HashFmt hf) const { return HashCells{tab, cap - 1, hf}; }
 };
 
-RbWs carve(void *ws, int m) {
-    RbWs r;
-    const uint32_t cap = next_pow2((uint32_t)(2 * (m > 0 ? m : 1) < 1024 ? 1024 : 2 * m));
-    size_t off = 0;
+RbWs carve(void *ws, int m, int per_row, int n_arrays) {
+    RbWs r{};
+    const long long cand = (long long)(m > 0 ? m : 1) * per_row;
+    const long long slots = 2 * cand < 1024 ? 1024 : 2 * cand < (1ll << 31) ? 2 * cand : 1ll << 31;
     char *p = (char *)ws;
-    r.cap = cap;
-    r.tab = (unsigned long long *)(p + off);
-    off += (size_t)cap * 8;
-    const size_t mi = align_up((size_t)(m > 0 ? m : 1) * 4, 256);
-    r.a = (int32_t *)(p + off);
-    off += mi;
-    r.b = (int32_t *)(p + off);
-    off += mi;
-    r.c = (int32_t *)(p + off);
-    off += mi;
+    r.cap = next_pow2((uint32_t)slots);
+    r.tab = (unsigned long long *)p;
+    size_t off = (size_t)r.cap * 8;
+    for (int a = 0; a < n_arrays; ++a) {
+        r.arr[a] = (int32_t *)(p + off);
+        off += align_up((size_t)cand * 4, 256);
+    }
     r.scan = (int32_t *)(p + off);
-    off += align_up(scan_ws_ints(m) * 4, 256);
+    off += align_up(scan_ws_ints((int)cand) * 4, 256);
     r.total = off;
     return r;
 }
@@ -481,17 +465,37 @@ bool grid_fmt(int batch, int X, int Y, int Z, unsigned long long max_value, Hash
 }
 }  // namespace
 
-// the direct-address grid behind the hash workspace, or null (no room / grid too large / switched off)
-static int32_t *dense_grid(void *ws, size_t ws_bytes, size_t hash_total, int batch, const GridDesc g) {
+// THE workspace rule of the direct-address grid: the bytes of a workspace that holds the grid of this cell map behind a hash
+// workspace of `hash_total` bytes, or 0 when the library uses no grid for it (an empty extent, more than
+// 2^DODA_RULEBOOK_GRID_MAX_LOG2 cells (28; at most 30), or DODA_RULEBOOK_GRID=0).  The size query and dense_grid() below are
+// its only two readers, so what a caller allocates and what a build accepts cannot drift apart.
+static size_t grid_workspace_bytes(size_t hash_total, int batch, const GridDesc g) {
     static const bool off = getenv("DODA_RULEBOOK_GRID") && getenv("DODA_RULEBOOK_GRID")[0] == '0';
-    if (off || batch <= 0 || g.X <= 0 || g.Y <= 0 || g.Z <= 0) return nullptr;
+    static const long long max_cells = [] {
+        const char *e = getenv("DODA_RULEBOOK_GRID_MAX_LOG2");
+        const int b = e ? atoi(e) : 28;
+        return 1ll << (b < 0 ? 0 : b > 30 ? 30 : b);
+    }();
+    if (off || batch <= 0 || g.X <= 0 || g.Y <= 0 || g.Z <= 0) return 0;
     const long double cells = (long double)batch * g.X * g.Y * g.Z;
-    if (cells > (long double)GRID_MAX_CELLS) return nullptr;
-    const size_t at = align_up(hash_total, 256), need = at + (size_t)cells * 4;
-    return ws_bytes >= need ? (int32_t *)((char *)ws + at) : nullptr;
+    if (cells > (long double)max_cells) return 0;
+    return align_up(hash_total, 256) + (size_t)cells * 4;
 }
 
-extern "C" size_t doda_rulebook_workspace_bytes(int32_t m) { return carve(nullptr, m).total; }
+// the direct-address grid behind the hash workspace, or null (no room / grid too large / switched off)
+static int32_t *dense_grid(void *ws, size_t ws_bytes, size_t hash_total, int batch, const GridDesc g) {
+    const size_t need = grid_workspace_bytes(hash_total, batch, g);
+    return need && ws_bytes >= need ? (int32_t *)((char *)ws + align_up(hash_total, 256)) : nullptr;
+}
+
+extern "C" size_t doda_rulebook_workspace_bytes(int32_t m) { return carve(nullptr, m, 1, 3).total; }
+
+extern "C" size_t doda_rulebook_workspace_bytes_grid(int32_t m, int32_t batch, const int32_t *shape_h) {
+    const size_t base = doda_rulebook_workspace_bytes(m);
+    if (m <= 0 || !shape_h) return base;
+    const size_t with_grid = grid_workspace_bytes(base, batch, GridDesc{shape_h[0], shape_h[1], shape_h[2]});
+    return with_grid ? with_grid : base;
+}
 
 extern "C" int doda_rulebook_subm(const int32_t *indices, int32_t m, const int32_t *shape_h,
                                   int32_t batch, int32_t ksize, int32_t *nbr, int32_t ld,
@@ -502,7 +506,7 @@ extern "C" int doda_rulebook_subm(const int32_t *indices, int32_t m, const int32
     if (!indices || !nbr || !ws) return DODA_ERR_INVALID;
     HashFmt hf;
     if (!grid_fmt(batch, shape_h[0], shape_h[1], shape_h[2], (unsigned long long)m, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const RbWs w = carve(ws, m);
+    const RbWs w = carve(ws, m, 1, 3);
     if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     const GridDesc g{shape_h[0], shape_h[1], shape_h[2]};
@@ -516,15 +520,15 @@ extern "C" int doda_rulebook_subm(const int32_t *indices, int32_t m, const int32
     int32_t *dgrid = dense_grid(ws, ws_bytes, w.total, batch, g);
     if (dgrid) {      // direct-address grid: the caller's workspace has room for it (and the grid is small enough)
         hipMemsetAsync(dgrid, 0xFF, (size_t)batch * g.X * g.Y * g.Z * 4, s);
-        hipLaunchKernelGGL(subm_grid_insert, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g, dgrid,
-                           nbr, ld, 14, 27);
+        hipLaunchKernelGGL(subm_insert<GridCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g,
+                           GridCells{dgrid}, nbr, ld, 14, 27);   // + mirrored half := -1
         hipLaunchKernelGGL((subm_grid_probe<3>), dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g, dgrid,
                            nbr, ld);
         return doda_check_launch();
     }
     hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
-    hipLaunchKernelGGL(subm_insert, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g,
-                       w.tab, w.cap - 1, hf, nbr, ld, 14, 27);   // + mirrored half := -1
+    hipLaunchKernelGGL(subm_insert<HashCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g,
+                       w.cells(hf), nbr, ld, 14, 27);
     hipLaunchKernelGGL((subm_probe<3>), dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g,
                        w.tab, w.cap - 1, hf, nbr, ld);
     return doda_check_launch();
@@ -549,26 +553,28 @@ extern "C" int doda_rulebook_down2_assign(const int32_t *indices, int32_t m,
     if (shape_h[0] < 2 || shape_h[1] < 2 || shape_h[2] < 2) return DODA_ERR_INVALID;
     HashFmt hf;
     if (!grid_fmt(batch, go.X, go.Y, go.Z, (unsigned long long)m, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const RbWs w = carve(ws, m);
+    const RbWs w = carve(ws, m, 1, 3);
     if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
     const int grid = div_up(m, 256);
+    int32_t *const firstj = w.arr[0], *const flag = w.arr[1], *const rank = w.arr[2];
     int32_t *dgrid = dense_grid(ws, ws_bytes, w.total, batch, go);
     if (dgrid) {
         hipMemsetAsync(dgrid, 0xFF, (size_t)batch * go.X * go.Y * go.Z * 4, s);
-        hipLaunchKernelGGL(down2_grid_insert, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go, dgrid, off);
-        hipLaunchKernelGGL(down2_grid_first, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go, dgrid,
-                           w.a /*firstj*/, w.b /*flag*/);
+        hipLaunchKernelGGL(down2_insert<GridCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
+                           GridCells{dgrid}, off);
+        hipLaunchKernelGGL(down2_first<GridCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
+                           GridCells{dgrid}, firstj, flag);
     } else {
         hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
-        hipLaunchKernelGGL(down2_insert, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
-                           w.tab, w.cap - 1, hf, off);
-        hipLaunchKernelGGL(down2_first, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
-                           w.tab, w.cap - 1, hf, w.a /*firstj*/, w.b /*flag*/);
+        hipLaunchKernelGGL(down2_insert<HashCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
+                           w.cells(hf), off);
+        hipLaunchKernelGGL(down2_first<HashCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, go,
+                           w.cells(hf), firstj, flag);
     }
-    int st = exclusive_scan_i32(w.b, w.c /*rank*/, m, counts_out, w.scan, s);
+    int st = exclusive_scan_i32(flag, rank, m, counts_out, w.scan, s);
     if (st != DODA_OK) return st;
-    hipLaunchKernelGGL(down2_finalize, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, w.a,
-                       w.c, parent, (int4 *)out_indices);
+    hipLaunchKernelGGL(down2_finalize, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, firstj,
+                       rank, parent, (int4 *)out_indices);
     return doda_check_launch();
 }
 
@@ -620,36 +626,22 @@ extern "C" int doda_rulebook_pairs(const int32_t *tbl, int32_t ld, int32_t K, in
 
 // ---- generic geometry: host entry points ------------------------------------------------------
 namespace {
-struct ConvWs {
-    unsigned long long *tab;
-    uint32_t cap;
-    int32_t *flag, *rank, *scan;
-    size_t total;
-};
-ConvWs carve_conv(void *ws, int m, int K) {
-    ConvWs r;
-    const long long cand = (long long)(m > 0 ? m : 1) * K;
-    const uint32_t cap = next_pow2((uint32_t)(2 * cand < 1024 ? 1024 : 2 * cand));
-    size_t off = 0;
-    char *p = (char *)ws;
-    r.cap = cap;
-    r.tab = (unsigned long long *)(p + off);
-    off += (size_t)cap * 8;
-    const size_t ci = align_up((size_t)cand * 4, 256);
-    r.flag = (int32_t *)(p + off); off += ci;
-    r.rank = (int32_t *)(p + off); off += ci;
-    r.scan = (int32_t *)(p + off); off += align_up(scan_ws_ints((int)cand) * 4, 256);
-    r.total = off;
-    return r;
-}
-bool make_geo(const int32_t *shape, const int32_t *k, const int32_t *s, const int32_t *p, const int32_t *d,
-              ConvGeo *g) {
+// what both geometries ask of every axis, and the kernel volume K (false: a bad value, or a volume beyond an int)
+bool geo_axes(const int32_t *shape, const int32_t *k, const int32_t *s, const int32_t *p, const int32_t *d, ConvGeo *g) {
     g->K = 1;
-    int o[3];
     for (int a = 0; a < 3; ++a) {
         if (k[a] < 1 || s[a] < 1 || p[a] < 0 || d[a] < 1 || shape[a] < 1) return false;
         g->k[a] = k[a]; g->s[a] = s[a]; g->p[a] = p[a]; g->d[a] = d[a];
+        if ((long long)g->K * k[a] > 0x7fffffffll) return false;
         g->K *= k[a];
+    }
+    return true;
+}
+bool make_geo(const int32_t *shape, const int32_t *k, const int32_t *s, const int32_t *p, const int32_t *d,
+              ConvGeo *g) {
+    if (!geo_axes(shape, k, s, p, d, g)) return false;
+    int o[3];
+    for (int a = 0; a < 3; ++a) {
         o[a] = (shape[a] + 2 * p[a] - d[a] * (k[a] - 1) - 1) / s[a] + 1;   // spconv get_conv_output_size
         if (o[a] < 1) return false;
     }
@@ -660,13 +652,10 @@ bool make_geo(const int32_t *shape, const int32_t *k, const int32_t *s, const in
 // transposed geometry: out = (in - 1) * stride - 2 * padding + kernel + output_padding (include/doda_spconv.h)
 bool make_geo_transposed(const int32_t *shape, const int32_t *k, const int32_t *s, const int32_t *p, const int32_t *d,
                          const int32_t *op, ConvGeo *g) {
-    g->K = 1;
+    if (!geo_axes(shape, k, s, p, d, g)) return false;
     int o[3];
     for (int a = 0; a < 3; ++a) {
-        if (k[a] < 1 || s[a] < 1 || p[a] < 0 || d[a] < 1 || op[a] < 0 || shape[a] < 1) return false;
-        g->k[a] = k[a]; g->s[a] = s[a]; g->p[a] = p[a]; g->d[a] = d[a];
-        if ((long long)g->K * k[a] > 0x7fffffffll) return false;
-        g->K *= k[a];
+        if (op[a] < 0) return false;
         const long long e = ((long long)shape[a] - 1) * s[a] - 2ll * p[a] + k[a] + op[a];
         // (the upper bound of an input position, (in - 1) * stride - padding + (kernel - 1) * dilation, stays an int as well)
         const long long hi = ((long long)shape[a] - 1) * s[a] + ((long long)k[a] - 1) * d[a];
@@ -688,14 +677,13 @@ int conv_assign(const int32_t *indices, int32_t m, int32_t batch, const ConvGeo 
     if (!indices || !ws) return DODA_ERR_INVALID;
     HashFmt hf;   // values are touch keys j * K + rank
     if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const ConvWs w = carve_conv(ws, m, g.K);
+    const RbWs w = carve(ws, m, g.K, 2);
     if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
     const int grid = div_up(m, 256);
     hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
-    hipLaunchKernelGGL(conv_touch<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf);
-    hipLaunchKernelGGL(conv_first<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
-                       w.flag);
-    return exclusive_scan_i32(w.flag, w.rank, m * g.K, count_out, w.scan, s);
+    hipLaunchKernelGGL(conv_touch<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.cells(hf));
+    hipLaunchKernelGGL(conv_first<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.cells(hf), w.arr[0] /*flag*/);
+    return exclusive_scan_i32(w.arr[0], w.arr[1] /*rank*/, m * g.K, count_out, w.scan, s);
 }
 
 template <bool TR>
@@ -705,14 +693,14 @@ int conv_fill(const int32_t *indices, int32_t m, int32_t batch, const ConvGeo &g
     if (!indices || !out_indices || !tbl || !tbl_rev || !ws) return DODA_ERR_INVALID;
     HashFmt hf;   // the split the assign half used for this table
     if (!grid_fmt(batch, g.out.X, g.out.Y, g.out.Z, (unsigned long long)m * g.K, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const ConvWs w = carve_conv(ws, m, g.K);
+    const RbWs w = carve(ws, m, g.K, 2);
     if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     const int grid = div_up(m, 256);
     if (m_out > 0) hipMemsetAsync(tbl, 0xFF, (size_t)g.K * ld_out * 4, s);
-    hipLaunchKernelGGL(conv_number<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
-                       w.flag, w.rank, (int4 *)out_indices);
-    hipLaunchKernelGGL(conv_tables<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.tab, w.cap - 1, hf,
+    hipLaunchKernelGGL(conv_number<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.cells(hf),
+                       w.arr[0] /*flag*/, w.arr[1] /*rank*/, (int4 *)out_indices);
+    hipLaunchKernelGGL(conv_tables<TR>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, g, w.cells(hf),
                        tbl, ld_out, tbl_rev, ld_in);
     return doda_check_launch();
 }
@@ -720,7 +708,7 @@ int conv_fill(const int32_t *indices, int32_t m, int32_t batch, const ConvGeo &g
 
 extern "C" size_t doda_rulebook_conv_workspace_bytes(int32_t m, int32_t K) {
     if (m < 0 || K < 1 || K > 27 || (long long)m * K > 0x3fffffffll) return 0;
-    return carve_conv(nullptr, m, K).total;
+    return carve(nullptr, m, K, 2).total;
 }
 
 extern "C" int doda_rulebook_conv_assign(const int32_t *indices, int32_t m, const int32_t *shape_h,
@@ -788,15 +776,15 @@ extern "C" int doda_rulebook_subm_generic(const int32_t *indices, int32_t m, con
     if (!indices || !nbr || !ws) return DODA_ERR_INVALID;
     HashFmt hf;
     if (!grid_fmt(batch, shape_h[0], shape_h[1], shape_h[2], (unsigned long long)m, &hf)) return DODA_ERR_GRID_TOO_LARGE;
-    const RbWs w = carve(ws, m);
+    const RbWs w = carve(ws, m, 1, 3);
     if (ws_bytes < w.total) return DODA_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     const GridDesc g{shape_h[0], shape_h[1], shape_h[2]};
     const int grid = div_up(m, 256);
     hipMemsetAsync(w.tab, 0xFF, (size_t)w.cap * 8, s);
-    hipLaunchKernelGGL(subm_insert, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g, w.tab,
-                       w.cap - 1, hf, nbr, ld, K, K);   // no prefill
+    hipLaunchKernelGGL(subm_insert<HashCells>, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g, w.cells(hf),
+                       nbr, ld, K, K);   // no prefill
     hipLaunchKernelGGL(subm_probe_generic, dim3(grid), dim3(256), 0, s, (const int4 *)indices, m, (int)batch, g,
-                       ksize_h[0], ksize_h[1], ksize_h[2], w.tab, w.cap - 1, hf, nbr, ld);
+                       ksize_h[0], ksize_h[1], ksize_h[2], w.cells(hf), nbr, ld);
     return doda_check_launch();
 }

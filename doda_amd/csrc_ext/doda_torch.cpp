@@ -18,6 +18,7 @@
 #include <c10/hip/HIPCachingAllocator.h>
 #include <hip/hip_runtime_api.h>
 
+#include <array>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -401,56 +402,41 @@ int32_t read_back_i32(const at::Tensor &t, void *st) {
     return t.item<int32_t>();
 }
 
-// with_pairs: also export every rulebook's pair lists (SubM: [2,27,M] from nbr; k2s2: [2,8,M] from par_off)
-// for the pair-list weight gradient — on the same (side) stream, off the critical path.
-typedef std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<int64_t>, at::Tensor, at::Tensor,
-                   at::Tensor, at::Tensor, at::Tensor, at::Tensor> PyramidLevel;
-// pairs_min_rows < 0: no lists; else lists for rulebooks of at least that many rows.
+// One level of the pyramid: SubM table, then the k2 s2 rulebook below it (outids, child, par_off, output shape; undefined on
+// the last level), then the SubM rulebook's pair lists, counts and segments (undefined where it gets none).
+typedef std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, std::vector<int64_t>, at::Tensor, at::Tensor, at::Tensor>
+    PyramidLevel;
+// policy: one (tile_lo, tile_hi, pairs_min) row per level, decided by doda_amd.spconv.ops.level_policy — this function only
+// applies it to the row count m it reads back.  The SubM rulebook gets a tilebook where tile_lo <= m < tile_hi, and otherwise
+// pair lists (SubM: [2,27,M] from nbr, for the pair-list weight gradient; on the same (side) stream, off the critical path)
+// where m >= pairs_min; a negative tile_lo / pairs_min means never.
 std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vector<int64_t> shape, int64_t batch,
-                                        int64_t n_levels, int64_t pairs_min_rows, int64_t tile_min_rows,
-                                        int64_t tile_levels, int64_t wgrad_tile_levels) {
+                                        const std::vector<std::array<int64_t, 3>> &policy) {
     TORCH_CHECK(indices_in.is_cuda() && indices_in.scalar_type() == at::kInt && indices_in.dim() == 2 &&
                 indices_in.size(1) == 4 && shape.size() == 3, "doda build_pyramid: indices must be int32 [M,4] on the GPU");
     std::vector<PyramidLevel> out;
     at::Tensor indices = indices_in.contiguous();
     const auto iopt = indices.options();
     void *st = stream_of(indices);
+    const int64_t n_levels = (int64_t)policy.size();
     for (int64_t lvl = 0; lvl < n_levels; ++lvl) {
         const int32_t m = (int32_t)indices.size(0);
         int32_t shp[3] = {(int32_t)shape[0], (int32_t)shape[1], (int32_t)shape[2]};
-        size_t wsb = doda_rulebook_workspace_bytes(m);
-        {   // room for the direct-address grid behind it (doda_hip.h: grids of <= 2^28 cells; larger ones keep the hash)
-            const long double cells = (long double)batch * shape[0] * shape[1] * shape[2];
-            static const long long grid_max = [] {      // (csrc/rulebook.hip GRID_MAX_CELLS: the same switch)
-                const long long b = env_int("DODA_RULEBOOK_GRID_MAX_LOG2", 28);
-                return 1ll << (b < 0 ? 0 : b > 30 ? 30 : b);
-            }();
-            if (m > 0 && cells > 0 && cells <= (long double)grid_max) wsb = (wsb + 255) / 256 * 256 + (size_t)cells * 4;
-        }
+        // one workspace for the level's SubM and k2 s2 builds, with room for the direct-address grid where the library would
+        // use one: asked with the input shape, the larger of the two cell maps
+        const size_t wsb = doda_rulebook_workspace_bytes_grid(m, (int32_t)batch, shp);
         at::Tensor ws = pempty({(int64_t)(wsb > 256 ? wsb : 256)}, iopt.dtype(at::kByte));
-        // tilebooks for the finest `tile_levels` levels: DODA's 16- and 32-channel bf16 layers (2) or the 16-channel
-        // fp32 layers (1) — rows of 32 or 64 bytes, what the tile kernel stages
-        // and, for the weight gradient only, the coarser levels below `wgrad_tile_levels` (48 .. 224-channel bf16 layers:
-        // csrc/spconv_wwide.hip; the forward kernels take a tilebook for 16 / 32 channels only).  Independent of
-        // tile_min_rows and of the finest levels' overflow backoff: a coarse tile above the list capacity is served from the
-        // dense table inside the kernel.
-        // (a rulebook that gets pair lists keeps them: its layers stay on the pair-list kernel)
-        const bool tiled = (lvl < tile_levels && tile_min_rows >= 0 && m >= tile_min_rows) ||
-                           (lvl >= tile_levels && lvl < wgrad_tile_levels && m > 0 && !(pairs_min_rows >= 0 && m >= pairs_min_rows));
+        const int64_t tile_lo = policy[lvl][0], tile_hi = policy[lvl][1], pairs_min = policy[lvl][2];
+        const bool tiled = tile_lo >= 0 && m >= tile_lo && m < tile_hi;
         at::Tensor nbr = tiled ? table_with_tilebook(27, m, iopt) : pempty({27, m}, iopt);
         check(doda_rulebook_subm((const int32_t *)indices.data_ptr(), m, shp, (int32_t)batch, 3,
                                  (int32_t *)nbr.data_ptr(), m, ws.data_ptr(), (size_t)ws.numel(), st),
               "doda_rulebook_subm");
         if (tiled) build_tilebook(nbr, st);
-        at::Tensor sp, sn, sh, dp, dn, dh;
-        const bool with_pairs = pairs_min_rows >= 0 && m >= pairs_min_rows;
-        // (round 4) a SubM rulebook with a tilebook needs no pair lists: every bf16 layer of 16 / 32 channels on either side
-        // takes the LDS-staged weight gradient over the tilebook (csrc/spconv_wgrad.hip classify(): from 32 768 rows, the
-        // smallest rulebook that gets a tilebook; a layer it does not take falls back to the gather table)
-        const bool subm_pairs = with_pairs && !tiled;
-        if (subm_pairs) std::tie(sp, sn, sh) = export_pairs(nbr, m, true, st);
+        at::Tensor sp, sn, sh;
+        if (!tiled && pairs_min >= 0 && m >= pairs_min) std::tie(sp, sn, sh) = export_pairs(nbr, m, true, st);
         if (lvl == n_levels - 1) {
-            out.emplace_back(nbr, at::Tensor(), at::Tensor(), at::Tensor(), std::vector<int64_t>(), sp, sn, sh, dp, dn, dh);
+            out.emplace_back(nbr, at::Tensor(), at::Tensor(), at::Tensor(), std::vector<int64_t>(), sp, sn, sh);
             break;
         }
         at::Tensor parent = pempty({m > 0 ? m : 1}, iopt), off = pempty({m > 0 ? m : 1}, iopt);
@@ -464,15 +450,11 @@ std::vector<PyramidLevel> build_pyramid(const at::Tensor &indices_in, std::vecto
         check(doda_rulebook_down2_tables((const int32_t *)parent.data_ptr(), (const int32_t *)off.data_ptr(), m, m_out,
                                          (int32_t *)child.data_ptr(), m_out, (int32_t *)par_off.data_ptr(), m, st),
               "doda_rulebook_down2_tables");
-        // (round 5) the strided rulebooks' lists are no longer exported by default: since the SubM layers of levels 1-2 take the
-        // tile weight gradient, the only consumers left were the six k2 s2 / inverse layers of levels 1-3, and the export (three
-        // launches per rulebook on the rulebook stream, 230 us per step) cost four times what the pair-list kernels saved over
-        // the gather-table kernel (54 us): 5.2-5.6 -> 5.0 ms per step in alternating runs (tools/pairs_ab.sh).
-        static const bool down_pairs = env_flag("DODA_WGRAD_PAIRS_DOWN", false);
-        if (with_pairs && down_pairs) std::tie(dp, dn, dh) = export_pairs(par_off, m, false, st);
+        // (the strided rulebooks' lists are never exported here: the export cost four times what the pair-list kernels saved
+        // on their six layers)
         std::vector<int64_t> oshape = {(shape[0] - 2) / 2 + 1, (shape[1] - 2) / 2 + 1, (shape[2] - 2) / 2 + 1};
         at::Tensor outids = out_idx.narrow(0, 0, m_out);
-        out.emplace_back(nbr, outids, child, par_off, oshape, sp, sn, sh, dp, dn, dh);
+        out.emplace_back(nbr, outids, child, par_off, oshape, sp, sn, sh);
         indices = outids;
         shape = oshape;
     }
@@ -1963,21 +1945,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }, "raw weight gradient");
     m.def("build_pyramid", &build_pyramid,
           "all SubM k3 and k2s2 rulebooks of an n-level U-Net in one call (13 native builds, 6 size read-backs)",
-          py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("n_levels"), py::arg("pairs_min_rows") = -1,
-          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::arg("wgrad_tile_levels") = 0,
+          py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("policy"),
           py::call_guard<py::gil_scoped_release>());   // its size read-backs block: let other Python threads run
-    m.def("build_pyramid_probe", [](const at::Tensor &indices, std::vector<int64_t> shape, int64_t batch, int64_t n_levels,
-                                    int64_t pairs_min_rows, int64_t tile_min_rows, int64_t tile_levels,
-                                    int64_t wgrad_tile_levels) {
+    m.def("build_pyramid_probe", [](const at::Tensor &indices, std::vector<int64_t> shape, int64_t batch,
+                                    const std::vector<std::array<int64_t, 3>> &policy) {
               // build_pyramid + the finest tilebook's overflow counters (tiles, above the 64-byte capacity, above the list)
               // in ONE call without the GIL: the rulebook thread's read-back does not stall the issuing thread
-              auto levels = build_pyramid(indices, shape, batch, n_levels, pairs_min_rows, tile_min_rows, tile_levels,
-                                          wgrad_tile_levels);
+              auto levels = build_pyramid(indices, shape, batch, policy);
               std::tuple<int64_t, int64_t, int64_t> over{-1, 0, 0};
               if (!levels.empty()) tilebook_overflow(std::get<0>(levels[0]), over);
               return std::make_tuple(levels, std::get<0>(over), std::get<1>(over), std::get<2>(over));
-          }, py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("n_levels"), py::arg("pairs_min_rows") = -1,
-          py::arg("tile_min_rows") = -1, py::arg("tile_levels") = 2, py::arg("wgrad_tile_levels") = 0,
+          }, py::arg("indices"), py::arg("shape"), py::arg("batch"), py::arg("policy"),
           py::call_guard<py::gil_scoped_release>());
     m.def("with_tilebook", [](const at::Tensor &tbl) {
               TORCH_CHECK(tbl.is_cuda() && tbl.scalar_type() == at::kInt && tbl.dim() == 2, "doda with_tilebook: int32 [K, M] table");

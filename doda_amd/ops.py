@@ -5,7 +5,6 @@ and makes exactly the native calls — no arithmetic happens in Python and there
 (device tensors are required wherever the ABI takes device pointers).
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -185,17 +184,11 @@ def _check_indices(indices):
     return indices.contiguous()
 
 
-RULEBOOK_GRID_MAX_CELLS = 1 << min(30, max(0, int(os.environ.get("DODA_RULEBOOK_GRID_MAX_LOG2", "28"))))   # csrc/rulebook.hip GRID_MAX_CELLS
-
-
 def _rulebook_ws(m, batch_size, shape3, device):
-    """Workspace of a rulebook build: doda_rulebook_workspace_bytes(m), plus — for grids of up to 2^26 cells — room for the
-    direct-address grid behind it (include/doda_hip.h: the build then replaces the hash table by a plain cell -> row array)."""
-    nbytes = lib().doda_rulebook_workspace_bytes(m)
-    cells = int(batch_size) * int(shape3[0]) * int(shape3[1]) * int(shape3[2])
-    if m > 0 and 0 < cells <= RULEBOOK_GRID_MAX_CELLS:
-        nbytes = (nbytes + 255) // 256 * 256 + 4 * cells
-    return _ws(nbytes, device)
+    """Workspace of a rulebook build over the cell map batch_size x shape3, sized by the library's own rule
+    (doda_rulebook_workspace_bytes_grid, include/doda_hip.h): with room for the direct-address grid where the build would use
+    one, the minimum (hash) workspace otherwise."""
+    return _ws(lib().doda_rulebook_workspace_bytes_grid(m, int(batch_size), _shape3(shape3)[0]), device)
 
 
 def rulebook_subm(indices, spatial_shape, batch_size, ksize=3):

@@ -16,6 +16,7 @@ from torch.autograd import Function
 
 from .. import ops as _ops
 from .._ext import ext as _ext
+from .ops import PAIRS_MIN_ROWS   # (one definition: pair lists only for large rulebooks)
 
 # Backward of a sparse conv = two independent native ops on the same inputs: the data-grad gather
 # (on the critical path of the chain rule) and the weight-grad reduction.  With DODA_OVERLAP_BWD=1
@@ -161,12 +162,6 @@ def _conv(features, weight, fwd_tbl, bwd_tbl, n_out, bwd_layout, packed, residua
 WGRAD_PAIRS = os.environ.get("DODA_WGRAD_PAIRS", "1") == "1"
 
 
-# (round 5) lists of the STRIDED rulebooks (k2 s2 conv / inverse conv): off by default — once the SubM layers of levels 1-2 took
-# the tile weight gradient, these six layers were the only consumers left and the export of their lists (pairs_count / _scan /
-# _fill per rulebook: 230 us per step on the rulebook stream) cost four times what the pair-list kernels saved (54 us)
-WGRAD_PAIRS_DOWN = os.environ.get("DODA_WGRAD_PAIRS_DOWN", "0") == "1"
-PAIRS_MIN_ROWS = 65536   # smaller rulebooks stay on the gather-table kernel: the list export (three launches
-#                          per rulebook, issued by a host that is as busy as the GPU) would cost more than it saves
 
 
 def _want_pairs(features, weight, n_rows=None):
@@ -178,18 +173,15 @@ def _want_pairs(features, weight, n_rows=None):
 
 
 def _lists(data, features, weight, inverse=False, n_rows=None):
-    """The rulebook's pair lists for a layer's weight gradient, or None: lists that already exist are used; a SubM rulebook
-    with a tilebook needs none (its layers take the tile weight gradient or the gather table) and a strided rulebook gets none
-    unless DODA_WGRAD_PAIRS_DOWN=1 — nothing is exported just in case (round 5: four such exports per step ran on the
-    step's own stream, 230 us of kernels and twelve launches, for jobs that did not read them)."""
+    """The rulebook's pair lists for a layer's weight gradient, or None.  Lists that exist on the record are used: whoever
+    built the rulebook decided (spconv.ops.level_policy, or an explicit IndiceData.wgrad_lists()).  The one export made here
+    is the first use of a SubM rulebook that a module built by itself — no pyramid, hence no tilebook and no lists yet.
+    Nothing else is exported just in case (round 5: four such exports per step ran on the step's own stream, 230 us of
+    kernels and twelve launches, for jobs that did not read them)."""
     if not _want_pairs(features, weight, n_rows):
         return None
-    if data._wpairs is None:
-        if data.kind == "subm":
-            if _ext is not None and _ext.has_tilebook(data.tbl):
-                return None
-        elif not WGRAD_PAIRS_DOWN:
-            return None
+    if data._wpairs is None and (data.kind != "subm" or (_ext is not None and _ext.has_tilebook(data.tbl))):
+        return None
     return data.wgrad_lists(inverse=inverse)
 
 

@@ -14,9 +14,6 @@ from .. import ops as _ops
 from .._ext import ext as _ext
 from .core import IndiceData
 
-PAIRS_MIN_ROWS = 65536   # as doda_amd.spconv.functional.PAIRS_MIN_ROWS (pair lists only for large rulebooks)
-WGRAD_PAIRS_DOWN = os.environ.get("DODA_WGRAD_PAIRS_DOWN", "0") == "1"   # (as doda_amd.spconv.functional: strided rulebooks' lists)
-
 
 def _triple(v):
     if isinstance(v, (list, tuple, np.ndarray)):
@@ -104,6 +101,35 @@ _tile_state = {"skip": 0, "last": None}   # batches still to skip; (tiles, over 
 # (48 .. 224 channels: csrc/spconv_wwide.hip).  Their overflow does not feed the backoff above: a coarse tile above the
 # list capacity is served from the dense table inside that kernel.  0: none (DODA_WGRAD_TILE_LEVELS).
 WGRAD_TILE_LEVELS = int(os.environ.get("DODA_WGRAD_TILE_LEVELS", "7"))
+PAIRS_MIN_ROWS = 65536   # smaller rulebooks stay on the gather-table kernel: the list export (three launches
+#                          per rulebook, issued by a host that is as busy as the GPU) would cost more than it saves
+_NEVER, _NO_LIMIT = -1, 1 << 62
+
+
+def level_policy(n_levels, with_pairs, n_tile_levels, tiles_on):
+    """THE decision which SubM rulebook of a pyramid gets a tilebook and which gets pair lists: one (tile_lo, tile_hi,
+    pairs_min) row per level, applied by whoever knows the level's row count m (the extension's build_pyramid after its
+    read-back, the loop at the end of build_pyramid below).  A tilebook where tile_lo <= m < tile_hi; otherwise pair lists
+    where m >= pairs_min; -1 = never.  Strided rulebooks get neither (their lists cost more than they saved).
+      * the n_tile_levels finest levels (16 / 32 channels: rows of 32 or 64 bytes, what the tile kernels stage) take a
+        tilebook from TILE_MIN_ROWS rows, unless tiles are off (tiles_on False: DODA_NO_TILE=1 or the overflow back-off);
+      * bf16 training with tiles: the coarser levels below WGRAD_TILE_LEVELS take one for the weight gradient only
+        (csrc/spconv_wwide.hip), whatever tiles_on says (their overflow is served inside the kernel), up to the size from
+        which the rulebook gets lists instead — its layers then stay on the pair-list kernel;
+      * lists (with_pairs) go to rulebooks of at least PAIRS_MIN_ROWS rows that got no tilebook: with one, every bf16 layer
+        takes the tile weight gradient or falls back to the gather table."""
+    pairs_min = PAIRS_MIN_ROWS if with_pairs else _NEVER
+    wgrad_levels = WGRAD_TILE_LEVELS if (with_pairs and n_tile_levels > 0) else 0
+    rows = []
+    for k in range(n_levels):
+        if k < n_tile_levels:
+            tile = (TILE_MIN_ROWS, _NO_LIMIT) if tiles_on else (_NEVER, _NO_LIMIT)
+        elif k < wgrad_levels:
+            tile = (1, pairs_min)
+        else:
+            tile = (_NEVER, _NO_LIMIT)
+        rows.append(tile + (pairs_min,))
+    return rows
 
 
 def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", first_level=1, with_pairs=False,
@@ -112,8 +138,8 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
     (SubM k3 under subm_key % i, k2s2 under down_key % i), so the convolutions find them cached.
     Rulebooks depend only on the voxel indices; building them before any feature kernel is queued
     means the size read-backs of the strided levels wait on an almost empty stream instead of
-    stalling the host in the middle of the forward pass.  with_pairs: also export every rulebook's pair
-    lists for the pair-list weight gradient (training with bf16 features)."""
+    stalling the host in the middle of the forward pass.  with_pairs: also export the pair lists of the SubM
+    rulebooks that level_policy gives them to, for the pair-list weight gradient (training with bf16 features)."""
     indices, shape = tensor.indices, tensor.spatial_shape
     # with_tiles: number of finest levels that get a tilebook (True = 2: bf16 rows of 32 / 64 bytes at DODA's
     # widths; 1 for fp32 features); None follows with_pairs (bf16 training)
@@ -126,9 +152,7 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
             tiles_on = False
         # (one call without the GIL: the builds, their six size read-backs and the tilebook's overflow counters)
         levels, nt, over64, over32 = _ext.build_pyramid_probe(indices, [int(v) for v in shape], int(tensor.batch_size),
-                                                              int(n_levels), PAIRS_MIN_ROWS if with_pairs else -1,
-                                                              TILE_MIN_ROWS if tiles_on else -1, n_tile_levels,
-                                                              WGRAD_TILE_LEVELS if (with_pairs and n_tile_levels > 0) else 0)
+                                                              level_policy(int(n_levels), with_pairs, n_tile_levels, tiles_on))
         if tiles_on and nt >= 0:
             _tile_state["last"] = (nt, over64, over32)
             if over32 > TILE_OVERFLOW_MAX * nt:
@@ -136,7 +160,7 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
                 # this batch too: plain copies of the tables (no tilebook behind them) keep it on the dense kernels
                 levels = [((lv[0].clone() if k < n_tile_levels and _ext.has_tilebook(lv[0]) else lv[0]),) + tuple(lv[1:])
                           for k, lv in enumerate(levels)]
-        for k, (nbr, outids, child, par_off, oshape, sp, sn, sh, dp, dn, dh) in enumerate(levels):   # s*/d*: lists, counts, segments
+        for k, (nbr, outids, child, par_off, oshape, sp, sn, sh) in enumerate(levels):   # sp, sn, sh: lists, counts, segments
             lvl = first_level + k
             data = tensor.indice_dict[subm_key % lvl] = IndiceData("subm", indices, indices, list(shape),
                                                                    list(shape), nbr)
@@ -144,17 +168,16 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
                 data._wpairs = (sp, sn, sh)
             if k == len(levels) - 1:
                 break
-            data = tensor.indice_dict[down_key % lvl] = IndiceData("down2", outids, indices, list(shape),
-                                                                   list(oshape), child, par_off)
-            if dp is not None:
-                data._wpairs = (dp, dn, dh)
+            tensor.indice_dict[down_key % lvl] = IndiceData("down2", outids, indices, list(shape), list(oshape), child, par_off)
             indices, shape = outids, list(oshape)
         return tensor.indice_dict
-    for lvl in range(first_level, first_level + n_levels):
+    # the module-by-module builders make no tilebook: the same policy with tiles off (a record found in place keeps what it has)
+    policy = level_policy(int(n_levels), with_pairs, 0, False)
+    for lvl, (_, _, pairs_min) in zip(range(first_level, first_level + n_levels), policy):
         key = subm_key % lvl
         if key not in tensor.indice_dict:
             tensor.indice_dict[key] = build_subm(indices, tensor.batch_size, shape, 3)
-        if (with_pairs and indices.shape[0] >= PAIRS_MIN_ROWS
+        if (0 <= pairs_min <= indices.shape[0]
                 and not (_ext is not None and _ext.has_tilebook(tensor.indice_dict[key].tbl))):   # (tiled: no consumer)
             tensor.indice_dict[key].wgrad_lists()
         if lvl == first_level + n_levels - 1:
@@ -164,7 +187,5 @@ def build_pyramid(tensor, n_levels, subm_key="subm%d", down_key="spconv%d", firs
         if data is None:
             data = build_down2(indices, tensor.batch_size, shape, 2, 2, 0, 1)
             tensor.indice_dict[key] = data
-        if with_pairs and WGRAD_PAIRS_DOWN and indices.shape[0] >= PAIRS_MIN_ROWS:
-            data.wgrad_lists()
         indices, shape = data.outids, data.out_spatial_shape
     return tensor.indice_dict

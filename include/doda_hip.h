@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define DODA_ABI_VERSION 12
+#define DODA_ABI_VERSION 13
 
 #define DODA_OK 0
 #define DODA_ERR_INVALID (-1)        /* bad argument (null pointer, negative size, bad mode) */
@@ -106,14 +106,20 @@ int doda_point_recover_bp(const float *d_out, float *d_feats, const int32_t *rul
  * feature matrix that output row t reads for kernel offset o, or -1.  Offsets are numbered
  * row-major over (k0,k1,k2) exactly as spconv numbers them.
  * ---------------------------------------------------------------------------------------- */
+/* The MINIMUM workspace of doda_rulebook_subm, _subm_generic and _down2_assign over m rows.  With it, doda_rulebook_subm
+ * (ksize 3) and doda_rulebook_down2_assign look voxels up through a 64-bit hash table inside `ws`. */
 size_t doda_rulebook_workspace_bytes(int32_t m);
-/* ABI 7 (round 4).  doda_rulebook_subm (ksize 3) and doda_rulebook_down2_assign look voxels up through a 64-bit hash table
- * inside `ws`.  A caller that hands over a LARGER workspace — align256(doda_rulebook_workspace_bytes(m)) + 4 * cells bytes,
- * cells = batch * X * Y * Z of the grid the call looks up in (the input shape for subm, the output shape (s - 2) / 2 + 1
- * for down2), cells <= 2^28 (ABI 9; 2^26 before; DODA_RULEBOOK_GRID_MAX_LOG2) — gets a direct-address grid instead (grid[cell] = row
- * or -1: one 4-byte read per probe, the three z-neighbours adjacent; a batch of 2 cm scenes is 16.5 M cells = 66 MB, of four 1 cm
- * scenes 85 M cells = 340 MB).  Same tables, same first-touch numbering; larger grids and the minimum workspace keep the hash.
- * DODA_RULEBOOK_GRID=0 disables the grid. */
+/* ABI 13.  The workspace that selects the direct-address grid (ABI 7, round 4) for a cell map of batch * shape_h[0..2] cells:
+ * grid[cell] = row or -1 behind the hash workspace — one 4-byte read per probe, the three z-neighbours adjacent; a batch of
+ * 2 cm scenes is 16.5 M cells = 66 MB, of four 1 cm scenes 85 M cells = 340 MB.  `shape_h` is the shape the call looks
+ * voxels up in: the input shape for subm, the output shape (s - 2) / 2 + 1 for down2; a caller that shares one workspace
+ * between both asks with the larger (the input shape).  Returns align256(doda_rulebook_workspace_bytes(m)) + 4 * cells, or
+ * doda_rulebook_workspace_bytes(m) itself where the library would not use a grid: m == 0, an extent or the batch <= 0, more
+ * than 2^28 cells (2^N with DODA_RULEBOOK_GRID_MAX_LOG2=N, at most 30), or DODA_RULEBOOK_GRID=0 — so nobody allocates a grid
+ * that nothing reads.  Both environment variables are read once, by the library alone.  The build decides by ws_bytes: at
+ * least this answer selects the grid, anything smaller down to the minimum keeps the hash.  Same tables, same first-touch
+ * numbering either way. */
+size_t doda_rulebook_workspace_bytes_grid(int32_t m, int32_t batch, const int32_t *shape_h);
 
 /* SubMConv3d, odd cubic kernel `ksize` (1 or 3), stride 1, padding ksize/2, dilation 1.
  * indices: int32 [m,4] = (batch, x, y, z).  nbr: int32 [ksize^3][ld], ld >= m.

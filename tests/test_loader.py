@@ -213,5 +213,5 @@ def test_choose_voxel_order_follows_the_tile_overflow():
     r = reorder_voxels(b, "morton")
     assert choose_voxel_order(r, d) == "first"
     idx = r["voxel_locs"].int().to(d)
-    _, nt, _, over = sops._ext.build_pyramid_probe(idx, [int(v) for v in r["spatial_shape"]], 1, 1, -1, sops.TILE_MIN_ROWS, 1)
+    _, nt, _, over = sops._ext.build_pyramid_probe(idx, [int(v) for v in r["spatial_shape"]], 1, sops.level_policy(1, False, 1, True))
     assert nt > 1000 and over == 0

@@ -118,5 +118,5 @@ def test_default_and_cross_entropy_keep_the_parents_objects():
 
 
 def test_loss_abi_version(native_lib):
-    assert native_lib.doda_loss_abi_version() == 1 and native_lib.doda_abi_version() == 12
+    assert native_lib.doda_loss_abi_version() == 1 and native_lib.doda_abi_version() == 13
     assert native_lib.doda_lovasz_workspace_bytes(1000, 11) > 0 and native_lib.doda_lovasz_workspace_bytes(1 << 30, 32) == 0

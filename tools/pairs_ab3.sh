@@ -10,6 +10,5 @@ PY
 for r in 1 2 3; do
 EXTRA="" run new_$r A=1
 EXTRA="" run nopairs_$r DODA_WGRAD_PAIRS=0
-EXTRA="" run down_$r DODA_WGRAD_PAIRS_DOWN=1
 done
 DODA_TRACE_PAIRS=1 timeout 300 python bench.py --steps 1 --warmup 1 --fp32-steps 0 --no-train-entry --no-cpu-baseline --kernel-reps 0 --config5-steps 0 2>&1 | grep -c "lazy pair"
